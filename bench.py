@@ -35,6 +35,13 @@ MI355X at 1.5 M img/s (65536-image steps fell below 1 s once the pipeline passed
 131072-image steps let single host hiccups swing a step's rate by 10-20 %). The K timed steps are bracketed by a barrier + ``torch.cuda.synchronize()``; ``value``
 is the whole-job images/s (sum over ranks of the images completed in the window / the slowest
 rank's window). The per-step rates give the within-run spread.
+
+A plain run ends there: set-up, warm-up, the K timed steps, the result line (its p50 / p99 are
+then fetch -> ack under the backlog). ``--full`` adds the latency half of the metric: a second
+phase at a fixed offered load (``--latency-load``, default 0.8 of the measured throughput) with
+per-record append -> produce-ack latencies, and the ``--latency-sweep`` / ``--latency-dump``
+phases. ``--dump-outputs DIR`` writes the last timed step's predictions, ordered by input image,
+to ``DIR/predictions.npy`` so that two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -197,8 +204,23 @@ def parse_args(argv=None):
     ap.add_argument("--all-stats", action="store_true",
                     help="add every engine statistic of rank 0 (queue / device / e2e quantiles, "
                          "lag, thread seconds) to the JSON line")
-    ap.add_argument("--latency-load", type=float, default=0.8,
-                    help="after the throughput window, offer this fraction of the measured "
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline images/s does not "
+                         "need: the offered-load latency phase (--latency-load and the other "
+                         "--latency-* options). A plain run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the predictions of the last timed step, "
+                         "as a consumer of the output topic receives them, to DIR/predictions.npy "
+                         "(predictions_rank<R>.npy with several ranks): float32 [images, "
+                         "classes], row i = the i-th distinct synthetic image (a fixed seeded "
+                         "sample of the rows above 64 MB). The synthetic records are then keyed "
+                         "by their index and the outputs carry their input's key (output_key "
+                         "input), which orders the rows; inputs and weights are seeded, so two "
+                         "runs with the same arguments are comparable row by row")
+    ap.add_argument("--latency-load", type=float, default=None,
+                    help="with --full (default 0.8 there): after the throughput window, offer "
+                         "this fraction of the measured "
                          "throughput at a fixed rate (native open-loop producer) and report "
                          "p50/p99 of record append -> produce ack at microsecond resolution "
                          "(BASELINE's latency half); 0 = skip (p50 is then fetch -> ack under "
@@ -240,7 +262,16 @@ def parse_args(argv=None):
     ap.add_argument("--print-config", action="store_true",
                     help="print the per-rank configuration (pipeline sizing, CPU slices) this "
                          "command would run, then exit without running it")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    # the latency phases are measurements of their own: they run only behind --full
+    if not a.full and ((a.latency_load or 0.0) > 0 or a.latency_sweep or a.latency_dump):
+        ap.error("--latency-load / --latency-sweep / --latency-dump need --full")
+    if a.latency_load is None:
+        a.latency_load = 0.8 if a.full else 0.0
+    if a.dump_outputs and a.gpus > 1 and not a.single_process and not a.local_output:
+        ap.error("--dump-outputs with several ranks needs --local-output (each rank reads the "
+                 "output partition its own broker leads)")
+    return a
 
 
 def _cgroup_cpu_stat() -> dict:
@@ -575,6 +606,56 @@ def outlier_attribution(stages, over_us=2000.0, bucket_ms=10.0):
     return out
 
 
+DUMP_KEY = "i"          # --dump-outputs: record r of the distinct set is keyed b"i<r>"
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(broker, partition, first, end, n_records, ipr, classes, path) -> dict:
+    """--dump-outputs: the prediction records at offsets [first, end) of the output partition
+    (the last timed step's acknowledged outputs, read back as a consumer would), parsed from
+    their JSON text and ordered by their input's key into float32 [n_records * ipr, classes];
+    an image answered several times in the step keeps its last answer. Returns what was written:
+    rows never answered in the window (left 0) and the largest difference between two answers
+    for the same image (0 when the forward does not depend on the batch an image rode in)."""
+    out = np.zeros((n_records, ipr * classes), dtype=np.float32)
+    idx, rows = [], []
+    off = max(first, broker.log_start("gale-out", partition))
+    while off < end:
+        recs = broker.read("gale-out", partition, off, 32 << 20)
+        if not recs:
+            break
+        for r in recs:
+            if r["offset"] >= end:
+                break
+            v = json.loads(r["value"]) if r["value"] else None
+            if not v or not r["key"]:
+                continue
+            p = v["predictions"]
+            if len(p) == ipr and all(len(q) == classes for q in p):
+                idx.append(int(r["key"][len(DUMP_KEY):]))
+                rows.append(p)
+        off = recs[-1]["offset"] + 1
+    seen = np.zeros(n_records, dtype=bool)
+    repeat_diff = 0.0
+    if rows:
+        idx = np.asarray(idx)
+        rows = np.asarray(rows, dtype=np.float32).reshape(len(idx), ipr * classes)
+        out[idx] = rows
+        seen[idx] = True
+        repeat_diff = float(np.abs(rows - out[idx]).max())
+    out = out.reshape(n_records * ipr, classes)
+    sampled = False
+    if out.nbytes > DUMP_MAX_BYTES:  # a fixed, seeded sample of the rows, in image order
+        keep = np.sort(np.random.default_rng(0).choice(
+            len(out), DUMP_MAX_BYTES // (4 * classes), replace=False))
+        out, sampled = out[keep], True
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.save(path, out)
+    return {"file": os.path.basename(path), "shape": list(out.shape), "dtype": "float32",
+            "output_records": len(idx), "images_unanswered": int((~seen).sum()) * ipr,
+            "repeat_max_abs_diff": repeat_diff, "row_sample": sampled}
+
+
 def pipeline_path(a, st) -> str:
     """What the timed window actually ran, from the engine's own counters (not the flags)."""
     if a.stub:
@@ -835,7 +916,9 @@ def main(argv=None) -> int:
     t_enc = time.perf_counter()
     imgs = synthetic_images(distinct, net.input_shape, seed=1234 + rank)
     enc_threads = a.encode_threads or max(1, int(host_cpus_per_rank()))
-    bset = K.synthetic_batches(imgs, ipr, rpb, enc_threads)
+    # --dump-outputs: keyed records (their index in the distinct set), echoed on the outputs
+    bset = K.synthetic_batches(imgs, ipr, rpb, enc_threads,
+                               key_prefix=DUMP_KEY if a.dump_outputs else "")
     # the latency phase's producer batches (--latency-batch-records; 0 = the same batches as the
     # backlog): smaller batches make arrivals less bursty, as a kafka-clients producer with its
     # 16 KB batch.size sends one ~35 KB record per batch
@@ -894,7 +977,8 @@ def main(argv=None) -> int:
                      locality_split=a.locality_split, fetch_min_bytes=a.fetch_min_bytes,
                      fetch_max_wait_ms=a.fetch_max_wait_ms, recv_lowat_kb=a.recv_lowat_kb,
                      use_graph=a.graph, graph_step=a.graph_step,
-                     producer_request_kb=a.producer_request_kb)
+                     producer_request_kb=a.producer_request_kb,
+                     output_key="input" if a.dump_outputs else "none")
     devices = (list(range(local_gpus)) if local_gpus > 1 else [local_rank]) if use_gpu else None
     # ONE engine: warm-up and timed window are the same steady-state pipeline (connections,
     # pinned fetch buffers, captured graphs all warm); the timed window starts at a barrier
@@ -959,6 +1043,16 @@ def main(argv=None) -> int:
     if not reached:
         raise SystemExit(f"rank {rank}: timed out after {elapsed:.1f}s "
                          f"({done_records}/{a.steps * step_records} records)")
+    dumped = None
+    if a.dump_outputs:
+        # every completed record is one acknowledged output record, so the last timed step's
+        # outputs are the step_records offsets below c0 + K * step_records of this engine's
+        # output partition (the engine runs on meanwhile; nothing timed is left)
+        end = c0 + a.steps * step_records
+        name = "predictions.npy" if world == 1 else f"predictions_rank{rank}.npy"
+        dumped = dump_outputs(broker, max(cfg.output_partition, 0), end - step_records, end,
+                              distinct // ipr, ipr, net.classes,
+                              os.path.join(a.dump_outputs, name))
     images = done_records * ipr  # >= K steps (completions arrive a micro-batch at a time)
     t = torch.tensor([elapsed, float(images)], dtype=torch.float64)
     if world > 1:
@@ -1075,9 +1169,15 @@ def main(argv=None) -> int:
                        "path": pipeline_path(a, st)},
             "load": (f"offered {a.rate:.0f} images/s per GPU" if a.rate > 0
                      else "value: backlog kept ahead of the consumers (max throughput); "
-                          "latency: a second phase at a fixed offered load"),
+                          + ("latency: a second phase at a fixed offered load"
+                             if a.latency_load > 0 else
+                             "latency: fetch -> ack under that backlog (--full adds the phase "
+                             "at a fixed offered load)")),
             "timed_s": round(elapsed_max, 3),
+            "full": a.full,
         }
+        if dumped:
+            out["dump_outputs"] = dict(dumped, dir=a.dump_outputs)
         if per_rank:
             out["ranks"] = per_rank
         if lat_us is not None and len(lat_us):

@@ -646,6 +646,12 @@ def test_gpu_locality_split_steals_parse_from_host_pinned():
                          bootstrap=f"127.0.0.1:{b.port}", start_offset="earliest",
                          max_batch=32, max_wait_us=300, output_key="input", replicas=2,
                          source_parallelism=2, locality_split=2, decode_threads=2,
+                         # a replica notices a finished batch only every 5 ms, so slot 0 serves
+                         # ~3 batches per 5 ms whatever the GPU's speed: a 200-record fetch
+                         # outlasts several of slot 1's 2 ms idle checks (at the device's own
+                         # speed slot 0 drains a fetch in under 1 ms and outruns its source, and
+                         # whether slot 1 ever saw a backlog was left to timing)
+                         gpu_wait_poll_us=5000,
                          text_pack=False)  # (a stolen record is parsed from its host text)
         eng = Engine(cfg, devices=[0], max_records=n, params=params)
         eng.start()

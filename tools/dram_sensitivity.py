@@ -4,7 +4,7 @@ when the other ranks of a socket load the same memory controllers?
 
 profiles/r5_host_budget.txt §4 projects N = 8 from one rank's CPU slice and assumes the socket's
 DRAM keeps up with four ranks (~0.55 TB/s of ~0.61 TB/s peak). This tool tests that assumption
-on the one-GPU box: bench.py runs next to tools/bin/dram_antagonist, pinned to the GPU's NUMA
+on the one-GPU box: bench.py --full runs next to tools/bin/dram_antagonist, pinned to the GPU's NUMA
 node, at several levels of extra DRAM traffic ("stream": T threads of read + non-temporal-write
 copies, one core each) and - the control - the same T threads burning CPU with no memory traffic
 ("burn"). Both take T cores of the job's CPU quota, so the difference between a stream level and
@@ -59,7 +59,9 @@ def run_level(mode: str, threads: int, rnd: int, a, cpus: str, tmp: str) -> dict
         time.sleep(2.0)  # buffers touched, streams at speed
     t0 = time.time()
     try:
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *a.bench_args],
+        # --full: the rows report the latency phase's p50 / p99 / p999 next to the images/s
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full",
+                            *a.bench_args],
                            cwd=ROOT, capture_output=True, text=True, timeout=a.bench_timeout)
         r = last_json(p.stdout)
         err = "" if r else (p.stderr or p.stdout)[-1500:]

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Place a latency tail in time: per window of the latency phase, the record latency quantiles
-and each stage's p99 (from ``bench.py --latency-dump``), next to what the host did in that
-window (from ``bench.py --timeline``: completion rate, cgroup cores and throttling, queue).
+and each stage's p99 (from ``bench.py --full --latency-dump``), next to what the host did in
+that window (from ``bench.py --timeline``: completion rate, cgroup cores and throttling, queue).
 
-    python tools/latency_report.py gpurun_out/lat/lat.npz [gpurun_out/lat/tl.jsonl] [--ms 100]
+    python tools/latency_report.py lat.npz [timeline.jsonl] [--ms 100]
 """
 
 from __future__ import annotations

@@ -2,7 +2,7 @@
 """Scaling curve of the headline benchmark (BASELINE.json: whole-node images/s + p50 latency,
 CIFAR-10 ResNet-20 at 1/2/4/8 GPUs).
 
-Runs ``bench.py --gpus N`` once per GPU count N on ONE node, exactly as the round driver does:
+Runs ``bench.py --full --gpus N`` once per GPU count N on ONE node, started as the driver does:
 a plain process, which for N > 1 starts ``torch.distributed.run`` itself (one rank per GPU, RCCL
 over xGMI, rendezvous on 127.0.0.1; bench.py ``launch_ranks``) -- and
 prints one JSON line per N plus a summary with the per-N images/s, p50/p99 latency and the
@@ -48,7 +48,8 @@ def plan(counts: list, placements: list) -> list:
 
 def bench_cmd(n: int, steps: int, warmup: int, extra: list, stub: bool = False,
               single_process: bool = False, placement: str = "floating") -> list:
-    args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps),
+    # --full: the curve reports the latency phase's p50 / p99 next to the images/s
+    args = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--steps", str(steps),
             "--warmup", str(warmup)] + (["--stub"] if stub else []) + list(extra)
     if n > 1 and not single_process:
         args += PLACEMENT_FLAGS[placement]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Latency-SLO sweep (BASELINE config 5: "ResNet-20 with fp8 weights, high-QPS latency-SLO mode").
 
-One ``bench.py`` run per dtype: the backlog phase measures the maximum throughput T, then the
+One ``bench.py --full`` run per dtype: the backlog phase measures the maximum throughput T, then the
 latency phases run at fixed offered loads (``--latency-sweep``, fractions of T, each
 ``--latency-repeat`` times). A latency phase's numbers are per-record Kafka append ->
 prediction produce-ack latencies at microsecond resolution (a native open-loop producer logs
@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(dtype: str, loads: str, repeat: int, slo: float, controller: bool, extra: list,
         timeout: float) -> dict:
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dtype", dtype,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dtype", dtype,
            "--steps", "10", "--warmup", "3", "--latency-sweep", loads,
            "--latency-repeat", str(repeat)] + extra
     if controller:
