@@ -72,6 +72,17 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "W", c.W);
   opt(d, "C", c.C);
   opt(d, "classes", c.classes);
+  // input preprocessing (gale/models/preprocess.py InputPrep.engine_entries)
+  std::vector<float> pa, pb;
+  bool nchw = false;
+  opt(d, "input_a", pa);
+  opt(d, "input_b", pb);
+  opt(d, "input_nchw", nchw);
+  if ((!pa.empty() && pa.size() != 4) || (!pb.empty() && pb.size() != 4))
+    throw std::invalid_argument("input_a / input_b: four coefficients each");
+  for (size_t i = 0; i < pa.size(); ++i) c.prep.a[i] = pa[i];
+  for (size_t i = 0; i < pb.size(); ++i) c.prep.b[i] = pb[i];
+  c.prep.nchw = nchw ? 1 : 0;
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
   opt(d, "slo_p99_ms", c.slo_p99_ms);
@@ -94,8 +105,10 @@ void bind_engine(py::module_& m) {
       .def("add_stub_replica",
            [](Engine& e, int max_images, int delay_us, bool compute, int locality) {
              const EngineConfig& c = e.config();
-             e.add_replica(std::make_shared<StubReplica>(c.H, c.W, c.C, c.classes, max_images,
-                                                         delay_us, compute, locality));
+             auto rep = std::make_shared<StubReplica>(c.H, c.W, c.C, c.classes, max_images,
+                                                      delay_us, compute, locality);
+             rep->set_input_prep(c.prep);
+             e.add_replica(std::move(rep));
            },
            py::arg("max_images") = 256, py::arg("delay_us") = 0, py::arg("compute") = true,
            py::arg("locality") = -1)
@@ -104,17 +117,21 @@ void bind_engine(py::module_& m) {
               bool gpu_encode, int locality, bool step_graph, bool high_priority,
               bool step_direct) {
              const EngineConfig& c = e.config();
-             e.add_replica(std::make_shared<GpuReplica>(std::move(exec), c.H, c.W, c.C,
-                                                        c.classes, use_graph, wait_poll_us,
-                                                        gpu_encode, locality, step_graph,
-                                                        high_priority, step_direct));
+             auto rep = std::make_shared<GpuReplica>(std::move(exec), c.H, c.W, c.C, c.classes,
+                                                     use_graph, wait_poll_us, gpu_encode,
+                                                     locality, step_graph, high_priority,
+                                                     step_direct);
+             rep->set_input_prep(c.prep);
+             e.add_replica(std::move(rep));
            },
            py::arg("executor"), py::arg("use_graph") = true, py::arg("wait_poll_us") = 0,
            py::arg("gpu_encode") = false, py::arg("locality") = -1, py::arg("step_graph") = true,
            py::arg("high_priority") = false, py::arg("step_direct") = false)
       .def("enable_gpu_ingest",
            [](Engine& e, int device, int lanes, int poll_us) {
-             e.set_ingest(std::make_shared<GpuIngest>(device, lanes, poll_us));
+             auto ing = std::make_shared<GpuIngest>(device, lanes, poll_us);
+             ing->set_input_prep(e.config().prep);
+             e.set_ingest(std::move(ing));
            },
            py::arg("device"), py::arg("lanes") = 2, py::arg("poll_us") = 20)
       .def("start",

@@ -434,6 +434,21 @@ void bind_host(py::module_& m) {
                                        C, out.mutable_data(), max_images, &images);
     return py::make_tuple(st, out);
   }, py::arg("data"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("max_images") = -1);
+  m.def("apply_input_prep",
+        [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
+           bool nchw, std::vector<float> a, std::vector<float> b) {
+          // x: images as parsed in record order ([N][H][W][C], or [N][C][H][W] with nchw)
+          const size_t per = (size_t)H * W * C;
+          if (a.size() != 4 || b.size() != 4 || per == 0 || (size_t)x.size() % per != 0)
+            throw std::invalid_argument("apply_input_prep: four coefficients, whole images");
+          const py::ssize_t n = x.size() / (py::ssize_t)per;
+          py::array_t<float> out({n, (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
+          memcpy(out.mutable_data(), x.data(), (size_t)x.size() * sizeof(float));
+          codec::apply_input_prep(out.mutable_data(), (int)n, H, W, C, nchw, a.data(), b.data());
+          return out;
+        },
+        py::arg("x"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("nchw"), py::arg("a"),
+        py::arg("b"));
   // ---- nibble transport (text_pack.h) ----
   m.def("text_pack_fast", &codec::text_pack_fast);
   // L3-domain pairing (gale/llc_pair.h), for tests: each call acts on the calling thread

@@ -7,6 +7,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <optional>
+#include <stdexcept>
+#include <vector>
+
 #include "../comm/rccl.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
@@ -225,17 +229,30 @@ PYBIND11_MODULE(_C, m) {
   m.def("json_parse_instances",
         [](int nrec, int ntiles, uintptr_t recs, uintptr_t tile_rec, uintptr_t bytes, int H,
            int W, int C, uintptr_t tile_counts, uintptr_t out, uintptr_t stream,
-           bool count_pass) {
+           bool count_pass, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b, bool nchw) {
+          // a / b (four coefficients each) or nchw: an InputPrep is passed (identity ones too)
+          gale::InputPrep prep;
+          const bool with_prep = a || b || nchw;
+          if ((a && a->size() != 4) || (b && b->size() != 4))
+            throw std::invalid_argument("json_parse_instances: a / b take four coefficients");
+          for (int i = 0; i < 4; ++i) {
+            if (a) prep.a[i] = (*a)[i];
+            if (b) prep.b[i] = (*b)[i];
+          }
+          prep.nchw = nchw ? 1 : 0;
           chk(gale::json_parse_instances(nrec, ntiles, static_cast<gale::JsonRecord*>(P(recs)),
                                          static_cast<const int*>(P(tile_rec)),
                                          static_cast<const uint8_t*>(P(bytes)), H, W, C,
                                          static_cast<int*>(P(tile_counts)),
-                                         static_cast<float*>(P(out)), S(stream), count_pass),
+                                         static_cast<float*>(P(out)), S(stream), count_pass,
+                                         nullptr, nullptr, nullptr, with_prep ? &prep : nullptr),
               "json_parse_instances");
         },
         py::arg("nrec"), py::arg("ntiles"), py::arg("recs"), py::arg("tile_rec"),
         py::arg("bytes"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("tile_counts"),
-        py::arg("out"), py::arg("stream"), py::arg("count_pass") = true);
+        py::arg("out"), py::arg("stream"), py::arg("count_pass") = true,
+        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("json_tile_count", &gale::json_tile_count);
   py::module_ comm = m.def_submodule("comm", "in-process RCCL communicator (ncclCommInitAll)");
   py::class_<gale::CommGroup, std::shared_ptr<gale::CommGroup>>(comm, "CommGroup")

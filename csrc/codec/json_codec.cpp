@@ -315,6 +315,28 @@ int parse_instances_host(const uint8_t* p, size_t n, int H, int W, int C, float*
   return OK;
 }
 
+void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
+                      const float* b) {
+  const size_t hw = (size_t)H * W, per = hw * (size_t)C;
+  std::vector<float> tmp(nchw ? per : 0);
+  for (int n = 0; n < images; ++n) {
+    float* img = x + (size_t)n * per;
+    if (nchw) {
+      memcpy(tmp.data(), img, per * sizeof(float));
+      for (int c = 0; c < C; ++c) {
+        const float ac = a[std::min(c, 3)], bc = b[std::min(c, 3)];
+        for (size_t p = 0; p < hw; ++p)
+          img[p * (size_t)C + c] = __builtin_fmaf(tmp[(size_t)c * hw + p], ac, bc);
+      }
+    } else {
+      for (size_t p = 0; p < hw; ++p)
+        for (int c = 0; c < C; ++c)
+          img[p * (size_t)C + c] =
+              __builtin_fmaf(img[p * (size_t)C + c], a[std::min(c, 3)], b[std::min(c, 3)]);
+    }
+  }
+}
+
 int format_float_java(float v, char* out) {
   char* o = out;
   if (isnan(v)) { memcpy(o, "NaN", 3); return 3; }

@@ -72,6 +72,14 @@ bool split_instances(const uint8_t* arr, size_t len,
 int parse_instances_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
                          int max_images, int* images);
 
+// The GPU parse's input preprocessing (InputPrep, gale/kernels.h) on a host-parsed block of
+// `images` images, in place: y = fmaf(x, a[c], b[c]) in binary32 with one rounding (a, b: four
+// coefficients, channels >= 3 take the last), bit-identical to the device. nchw: x holds each
+// image as parsed from a [C][H][W] nesting (parse_instances_host with the dims permuted to
+// (C, H, W)) and is transposed to [H][W][C].
+void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
+                      const float* b);
+
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.
 int format_float_java(float v, char* out);

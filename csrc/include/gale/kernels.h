@@ -244,6 +244,21 @@ struct JsonRecord {
 };
 static_assert(sizeof(JsonRecord) == 48, "JsonRecord layout (host <-> device tables)");
 int json_tile_count(int64_t off, int32_t len);
+// Input preprocessing applied at the parse's store: the model input for the record value x at
+// channel c is fmaf(x, a[c], b[c]) (binary32, one rounding; a = scale / std, b = -mean / std,
+// gale/models/preprocess.py). The coefficients travel by value in the kernel arguments (C <= 4
+// per-channel; a scalar is broadcast into all four). nchw: the record's instances array is
+// nested [N][C][H][W]; the stored tensor stays NHWC.
+struct InputPrep {
+  int nchw = 0;
+  float a[4] = {1.f, 1.f, 1.f, 1.f};
+  float b[4] = {0.f, 0.f, 0.f, 0.f};
+  bool identity() const {
+    for (int i = 0; i < 4; ++i)
+      if (a[i] != 1.f || b[i] != 0.f) return false;
+    return !nchw;
+  }
+};
 // tile_rec[t]: index of the record owning global tile t. tile_counts: device scratch of
 // >= ntiles ints.
 // count_pass = false: every record has_cnt (the counting kernel is not launched at all).
@@ -259,11 +274,15 @@ int json_tile_count(int64_t off, int32_t len);
 // tile_bad non-null (count_pass false): each tile's verdict (0 / 1 / 2 / 3) goes to
 // tile_bad[tile] by a plain store instead of raising a record status, so it may be host-mapped
 // memory; a record's verdict is the max over its tiles.
+// prep null or identity: the values are stored as parsed (the kernel instantiation without the
+// preprocessing code). Otherwise each value is stored as fmaf(x, a[c], b[c]), and with nchw the
+// structure is checked against [N][C][H][W] nesting and the store transposed to NHWC; needs
+// H * W * C < 2^20, and C <= 4 unless a / b are uniform.
 hipError_t json_parse_instances(int nrec, int ntiles, JsonRecord* recs, const int* tile_rec,
                                 const uint8_t* bytes, int H, int W, int C, int* tile_counts,
                                 float* out, hipStream_t stream, bool count_pass = true,
                                 const int* d_ntiles = nullptr, int* status = nullptr,
-                                int* tile_bad = nullptr);
+                                int* tile_bad = nullptr, const InputPrep* prep = nullptr);
 
 // Raw (zero initial state, no final inversion) CRC32C of byte windows [end - len, end) of a
 // device buffer, one wave per window (len <= kCrcChunkBytes): each lane folds 64 bytes with

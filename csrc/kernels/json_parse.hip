@@ -796,11 +796,15 @@ __global__ __launch_bounds__(256) void ingest_crc_count_kernel(
   count_group<PACKED>(recs, groups, g, bytes, pt, counts, gsum, gbad, reinterpret_cast<int*>(T));
 }
 
-__global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const int* tile_rec,
-                                                         int ntiles, const uint8_t* bytes, int H,
-                                                         int W, int C, const int* counts,
-                                                         float* out, const int* d_ntiles,
-                                                         int* status, int* tile_bad) {
+// The parse of one tile by one wave: the body of both parse kernels below. PREP: the input
+// preprocessing of InputPrep (gale/kernels.h) at the store; PREP = false is the parse without
+// it (`prep` is never read there).
+template <bool PREP>
+__device__ __forceinline__ void json_parse_tile(JsonRecord* recs, const int* tile_rec, int ntiles,
+                                                const uint8_t* bytes, int H, int W, int C,
+                                                const int* counts, float* out,
+                                                const int* d_ntiles, int* status, int* tile_bad,
+                                                const InputPrep& prep) {
   __shared__ __attribute__((aligned(16))) uint8_t lds_text[kWaves][kText];
   __shared__ uint16_t lds_tok[kWaves][kMaxTok];
   __shared__ uint32_t lds_cm[kWaves][kTile / 16 + 1];  // packed masks of the tile's chunks + 1
@@ -904,9 +908,12 @@ __global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const
   wave_lds_sync();
 
   // parse: lane handles tokens lane, lane + 64, ... (consecutive lanes -> consecutive elements)
+  // the nesting dims, innermost first; an NCHW record nests [N][C][H][W]: W, H, C
+  const bool nchw = PREP && prep.nchw;
+  const int d0 = nchw ? W : C, d1 = nchw ? H : W, d2 = nchw ? C : H;
   Dims dims;
-  dims.C = (uint32_t)C; dims.W = (uint32_t)W; dims.H = (uint32_t)H;
-  dims.rC = 1.0 / C; dims.rW = 1.0 / W; dims.rH = 1.0 / H;
+  dims.C = (uint32_t)d0; dims.W = (uint32_t)d1; dims.H = (uint32_t)d2;
+  dims.rC = 1.0 / d0; dims.rW = 1.0 / d1; dims.rH = 1.0 / d2;
   float* dst = out + (int64_t)r.slot * per_image;
   int bad = 0;
   for (int j = lane; j < ntok; j += 64) {
@@ -924,10 +931,33 @@ __global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const
       ok = false;
       val = parse_number(tx, pos, end, &ok, &len);
     }
+    // PREP: the element's channel and where it is stored (NCHW records: transposed to NHWC),
+    // from the same reciprocal-multiply divisions as wraps(); kn = wraps(idx) of an NCHW record.
+    // Stored here, ahead of the structure checks, so only kn stays live across them.
+    int kn = 0;
+    if (PREP) {
+      const uint32_t px = udiv_rcp((uint32_t)idx, dims.C, dims.rC);
+      const uint32_t i0 = (uint32_t)idx - px * dims.C;
+      uint32_t sidx = (uint32_t)idx, ch = i0;
+      if (prep.nchw) {
+        const uint32_t row = udiv_rcp(px, dims.W, dims.rW);
+        const uint32_t i1 = px - row * dims.W;
+        const uint32_t img = udiv_rcp(row, dims.H, dims.rH);
+        ch = row - img * dims.H;
+        kn = i0 ? 0 : i1 ? 1 : ch ? 2 : 3;
+        sidx = img * (uint32_t)per_image + (i1 * (uint32_t)W + i0) * (uint32_t)C + ch;
+      }
+      if (idx < expected) {
+        // (selects on the by-value coefficients: a dynamic index would spill them to scratch)
+        const float a = ch == 0 ? prep.a[0] : ch == 1 ? prep.a[1] : ch == 2 ? prep.a[2] : prep.a[3];
+        const float b = ch == 0 ? prep.b[0] : ch == 1 ? prep.b[1] : ch == 2 ? prep.b[2] : prep.b[3];
+        dst[sidx] = __builtin_fmaf(val, a, b);
+      }
+    }
     if (!ok) {
       bad = max(bad, 2);
     } else {
-      const int k = idx > 0 ? wraps((uint32_t)idx, dims) : 0;
+      const int k = idx <= 0 ? 0 : (PREP && prep.nchw) ? kn : wraps((uint32_t)idx, dims);
       const bool fast_gap = idx > 0 && pos - 8 >= tx.lo && pos - (2 * k + 2) >= beg &&
                             gap_window(text, x, k);
       if (!fast_gap && !gap_ok(tx, beg, pos, (uint32_t)idx, k)) {
@@ -937,7 +967,7 @@ __global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const
         if (!tail_ok(tx, pos + len, end)) bad = 3;
       }
     }
-    if (idx < expected) dst[idx] = val;
+    if (!PREP && idx < expected) dst[idx] = val;
   }
   if (last_tile && lane == 0 && base + ntok != expected) bad = max(bad, 1);
   if (tile_bad) {
@@ -948,6 +978,29 @@ __global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const
   } else if (bad) {
     atomicMax(status ? &status[ri] : &recs[ri].status, bad);
   }
+}
+
+__global__ __launch_bounds__(256) void json_parse_kernel(JsonRecord* recs, const int* tile_rec,
+                                                         int ntiles, const uint8_t* bytes, int H,
+                                                         int W, int C, const int* counts,
+                                                         float* out, const int* d_ntiles,
+                                                         int* status, int* tile_bad) {
+  json_parse_tile<false>(recs, tile_rec, ntiles, bytes, H, W, C, counts, out, d_ntiles, status,
+                         tile_bad, InputPrep());
+}
+
+// The parse with input preprocessing: `prep` arrives by value in the kernel arguments, so it is
+// captured into the step graph with the other scalars and needs no allocation.
+// waves_per_eu(4, 4): the channel / transposed-index arithmetic takes the allocation 3 VGPRs past
+// the 128 of four waves per SIMD (the plain parse sits at 126); held to 128 the compiler finds
+// them without a VGPR spill (scratch stays the 224 bytes of the exact-decimal path).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void json_parse_prep_kernel(JsonRecord* recs, const int* tile_rec, int ntiles,
+                            const uint8_t* bytes, int H, int W, int C, const int* counts,
+                            float* out, const int* d_ntiles, int* status, int* tile_bad,
+                            InputPrep prep) {
+  json_parse_tile<true>(recs, tile_rec, ntiles, bytes, H, W, C, counts, out, d_ntiles, status,
+                        tile_bad, prep);
 }
 
 }  // namespace
@@ -988,17 +1041,31 @@ hipError_t ingest_crc_count(const uint8_t* bytes, const CrcChunk* chunks, int nc
 hipError_t json_parse_instances(int nrec, int ntiles, JsonRecord* recs, const int* tile_rec,
                                 const uint8_t* bytes, int H, int W, int C, int* tile_counts,
                                 float* out, hipStream_t stream, bool count_pass,
-                                const int* d_ntiles, int* status, int* tile_bad) {
+                                const int* d_ntiles, int* status, int* tile_bad,
+                                const InputPrep* prep) {
   if (nrec <= 0 || ntiles <= 0) return hipSuccess;
   if (H <= 0 || W <= 0 || C <= 0) return hipErrorInvalidValue;
+  const bool with_prep = prep && !prep->identity();
+  if (with_prep) {
+    // udiv_rcp's divisors, and a channel index past the four coefficient slots
+    if ((int64_t)H * W * C >= (1 << 20)) return hipErrorInvalidValue;
+    if (C > 4)
+      for (int i = 1; i < 4; ++i)
+        if (prep->a[i] != prep->a[0] || prep->b[i] != prep->b[0]) return hipErrorInvalidValue;
+  }
   if (tile_bad && count_pass) return hipErrorInvalidValue;  // (per-tile verdicts: counted records)
   const int blocks = (ntiles + kWaves - 1) / kWaves;
   if (count_pass)
     hipLaunchKernelGGL(json_count_kernel, dim3(blocks), dim3(64 * kWaves), 0, stream, recs,
                        tile_rec, ntiles, bytes, tile_counts, d_ntiles, status);
-  hipLaunchKernelGGL(json_parse_kernel, dim3(blocks), dim3(64 * kWaves), 0, stream, recs,
-                     tile_rec, ntiles, bytes, H, W, C, tile_counts, out, d_ntiles, status,
-                     tile_bad);
+  if (with_prep)
+    hipLaunchKernelGGL(json_parse_prep_kernel, dim3(blocks), dim3(64 * kWaves), 0, stream, recs,
+                       tile_rec, ntiles, bytes, H, W, C, tile_counts, out, d_ntiles, status,
+                       tile_bad, *prep);
+  else
+    hipLaunchKernelGGL(json_parse_kernel, dim3(blocks), dim3(64 * kWaves), 0, stream, recs,
+                       tile_rec, ntiles, bytes, H, W, C, tile_counts, out, d_ntiles, status,
+                       tile_bad);
   return hipGetLastError();
 }
 

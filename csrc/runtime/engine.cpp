@@ -1022,6 +1022,10 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   // DRAM/L3 once instead of twice (per-socket memory bandwidth bounds the 8-GPU node)
   std::vector<codec::Scan> pre;
   std::vector<char> have_pre;
+  // the nesting dims of a record: (H, W, C), or (C, H, W) for NCHW input
+  const bool nchw = cfg_.prep.nchw != 0;
+  const int scan_h = nchw ? cfg_.C : cfg_.H, scan_w = nchw ? cfg_.H : cfg_.W,
+            scan_c = nchw ? cfg_.W : cfg_.C;
   if (cfg_.check_crcs && !f.crc_checked) {
     corrupt.assign(f.records.size(), 0);
     pre.resize(f.records.size());
@@ -1042,8 +1046,8 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
           crc = kafka::crc32c(pos, (size_t)(vend - pos), crc);
           pos = vend;
         }
-        pre[i] = codec::scan_instances(base + rr.value_off, (size_t)rr.value_len, cfg_.H,
-                                       cfg_.W, cfg_.C);
+        pre[i] = codec::scan_instances(base + rr.value_off, (size_t)rr.value_len, scan_h,
+                                       scan_w, scan_c);
         have_pre[i] = 1;
       }
       if (end > pos) crc = kafka::crc32c(pos, (size_t)(end - pos), crc);
@@ -1077,8 +1081,8 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       bytes_in_ += r.len;
       const codec::Scan s = !have_pre.empty() && have_pre[i]
                                 ? pre[i]
-                                : codec::scan_instances(r.value, (size_t)r.len, cfg_.H, cfg_.W,
-                                                        cfg_.C);
+                                : codec::scan_instances(r.value, (size_t)r.len, scan_h, scan_w,
+                                                        scan_c);
       r.status = s.status;
       r.arr_off = s.arr_off;
       r.arr_len = s.arr_len;

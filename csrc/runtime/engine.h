@@ -128,6 +128,9 @@ struct EngineConfig {
   std::string output_key = "none";
   // model I/O contract (InstObj [N][H][W][C] -> PredObj [N][classes])
   int H = 32, W = 32, C = 3, classes = 10;
+  // input preprocessing applied where the records are parsed (InputPrep, gale/kernels.h); with
+  // prep.nchw the records nest [N][C][H][W] and the host scans count their brackets that way
+  InputPrep prep;
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
   int max_wait_us = 2000;          // latency bound on batch formation

@@ -304,7 +304,7 @@ void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_
     check_hip(json_parse_instances((int)np, ptiles, reinterpret_cast<JsonRecord*>(dpl + o_precs),
                                    reinterpret_cast<const int*>(dpl + o_ptr), dev, H, W, C,
                                    L.d_counts, arena, st, /*count_pass=*/false, nullptr, nullptr,
-                                   d_pbad),
+                                   d_pbad, &input_prep_),
               "ingest: parse");
   if (timed) check_hip(hipEventRecord(L.tev[3], st), "ingest: timing event");
   check_hip(hipEventRecord(L.done, st), "ingest: event");

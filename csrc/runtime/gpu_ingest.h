@@ -27,6 +27,8 @@ class GpuIngest : public Ingest {
     text = text_bytes_.load();
     link = link_bytes_.load();
   }
+  // input preprocessing of the ingest parse (InputPrep, gale/kernels.h); before the first run()
+  void set_input_prep(const InputPrep& p) { input_prep_ = p; }
   Timing timing() const override {
     Timing t;
     t.runs = runs_.load();
@@ -66,6 +68,7 @@ class GpuIngest : public Ingest {
   void grow(Lane& L, size_t io_bytes, size_t tiles);
   void wait(Lane& L);
   int device_, poll_us_;
+  InputPrep input_prep_;
   std::atomic<int64_t> text_bytes_{0}, link_bytes_{0};
   std::atomic<int64_t> runs_{0}, prep_ns_{0}, plan_ns_{0}, wait_ns_{0}, post_ns_{0};
   std::atomic<int64_t> dev_runs_{0}, dev_copy_ns_{0}, dev_count_ns_{0}, dev_parse_ns_{0},

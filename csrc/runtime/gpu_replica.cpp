@@ -347,7 +347,8 @@ void GpuReplica::submit(Batch& b) {
             "H2D recs");
   check_hip(json_parse_instances(nrec, ntiles, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                                  s.d_tiles,
-                                 static_cast<float*>(exec_->input(slot)), stream_, count_pass),
+                                 static_cast<float*>(exec_->input(slot)), stream_, count_pass,
+                                 nullptr, nullptr, nullptr, &prep_),
             "json_parse_instances");
   exec_->run(slot, img, stream_, use_graph_);
   if (use_graph_ && exec_->graph_pays()) ++fwd_graph_batches_;
@@ -426,7 +427,7 @@ hipError_t GpuReplica::enqueue_step(Slot& s, int slot, bool count_pass, hipStrea
   if (parse)  // (a batch of records the ingest already parsed: the forward alone)
     c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                              s.d_tiles, static_cast<float*>(exec_->input(slot)), st, count_pass,
-                             s.d_hdr + 1, s.d_status);
+                             s.d_hdr + 1, s.d_status, nullptr, &prep_);
   const bool fused = exec_->step_out_ok();
   StepOut so;
   so.text = s.h_text;
@@ -470,7 +471,7 @@ hipGraphExec_t GpuReplica::step_for(Slot& s, int slot, bool count_pass) {
     if (c == hipSuccess)
       c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                                s.d_tiles, static_cast<float*>(exec_->input(slot)), cs,
-                               count_pass, s.d_hdr + 1);
+                               count_pass, s.d_hdr + 1, nullptr, nullptr, &prep_);
     if (c == hipSuccess) {
       try {
         exec_->launch_device_batch(slot, s.d_hdr + 2, cs);

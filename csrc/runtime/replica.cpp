@@ -40,10 +40,16 @@ void StubReplica::submit(Batch& b) {
   for (size_t ri = 0; ri < b.recs.size(); ++ri) {
     InRecord& r = b.recs[ri];
     int n = 0;
-    const int st = codec::parse_instances_host(r.value, (size_t)r.len, H_, W_, C_,
+    // an NCHW record is a rectangular array of dims (C, H, W) to the dims-agnostic decoder
+    const bool nchw = prep_.nchw != 0;
+    const int st = codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : H_,
+                                               nchw ? H_ : W_, nchw ? W_ : C_,
                                                x_.data() + (size_t)slot * per,
                                                max_images_ - slot, &n);
     if (st != codec::OK) b.dev_status[ri] = st;
+    else if (!prep_.identity())
+      codec::apply_input_prep(x_.data() + (size_t)slot * per, n, H_, W_, C_, nchw, prep_.a,
+                              prep_.b);
     for (int i = 0; i < r.images; ++i) {
       const float* img = x_.data() + (size_t)(slot + i) * per;
       float* out = probs_.data() + (size_t)(slot + i) * classes_;

@@ -113,8 +113,11 @@ class StubReplica : public Replica {
   int depth() const override { return 1; }
   void submit(Batch& b) override;
   void wait(Batch& b) override;
+  // input preprocessing (InputPrep, gale/kernels.h) on the host-parsed images; before submit()
+  void set_input_prep(const InputPrep& p) { prep_ = p; }
 
  private:
+  InputPrep prep_;
   int H_, W_, C_, classes_, max_images_, delay_us_;
   bool compute_;
   int locality_ = -1;  // false: a "null" replica (uniform softmax, no parsing) to measure host paths
@@ -163,6 +166,9 @@ class GpuReplica : public Replica {
   int64_t preparsed_records() const override { return preparsed_; }
   int64_t table_batches() const override { return table_batches_; }
   bool step_graph() const { return step_graph_; }
+  // input preprocessing of every parse this replica launches (InputPrep, gale/kernels.h): by
+  // value in the parse's kernel arguments, so it is part of a captured step; before submit()
+  void set_input_prep(const InputPrep& p) { prep_ = p; }
 
  private:
   static constexpr size_t kMetaHdr = 64;  // [nrec, ntiles, images, ...] ahead of the records
@@ -207,6 +213,7 @@ class GpuReplica : public Replica {
   size_t meta_rec_bytes() const;  // records + input pointer table of the metadata allocation
   static void* mapped_alloc(size_t bytes, const char* what);
   std::shared_ptr<Executor> exec_;
+  InputPrep prep_;
   int H_, W_, C_, classes_;
   bool use_graph_;
   int wait_poll_us_ = 0;

@@ -10,6 +10,7 @@
     python -m gale list
     python -m gale broker [--port 9092] [--partitions N]     embedded Kafka-protocol broker
     python -m gale produce <TOPIC> [--images N] [--model M] [--rate R]   synthetic InstObj load
+        [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
 
 ``--profile DIR`` re-runs the topology under ``rocprofv3 --kernel-trace --marker-trace --stats``
@@ -189,7 +190,8 @@ def cmd_broker(argv: List[str]) -> int:
 
 def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
-    from gale.data import encode_records, synthetic_images
+    from gale.data import (encode_records, encode_records_text, synthetic_images,
+                           synthetic_pixels)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -200,10 +202,20 @@ def cmd_produce(argv: List[str]) -> int:
     ap.add_argument("--model", default="resnet20", choices=CHOICES["model"])
     ap.add_argument("--rate", type=float, default=0, help="records/s (0 = as fast as possible)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--pixels", default="unit", choices=("unit", "byte"),
+                    help="unit: floats in [0, 1); byte: integers 0..255 without a decimal point "
+                         "(serve them with --input-scale 0.00392156862745098)")
+    ap.add_argument("--layout", default="nhwc", choices=CHOICES["input_layout"],
+                    help="nesting of each record's instances array (nchw: --input-layout nchw)")
     a = ap.parse_args(argv)
     net = get_model(a.model)
-    recs = encode_records(synthetic_images(a.images, net.input_shape, a.seed),
-                          a.images_per_record)
+    if a.pixels == "unit" and a.layout == "nhwc":
+        recs = encode_records(synthetic_images(a.images, net.input_shape, a.seed),
+                              a.images_per_record)
+    else:  # written by Python's compact json.dumps
+        imgs = (synthetic_pixels if a.pixels == "byte" else synthetic_images)(
+            a.images, net.input_shape, a.seed)
+        recs = encode_records_text(imgs, a.images_per_record, a.layout)
     p = native().kafka.Producer(a.bootstrap, linger_ms=5, batch_size=1 << 20)
     t0 = time.time()
     for i, r in enumerate(recs):

@@ -35,6 +35,8 @@ CHOICES = {
     # reference's TF graph, InferenceBolt.java:80-86); inputs and the softmax output are fp32
     "dtype": ("bf16", "fp8", "fp32"),
     "model": ("lenet5", "resnet20", "resnet50"),
+    # nesting order of a record's instances array (the model's tensors stay NHWC)
+    "input_layout": ("nhwc", "nchw"),
 }
 
 
@@ -141,6 +143,13 @@ class GaleConfig:
     dtype: str = "bf16"
     weights: str = ""                  # .npz / .safetensors (torch layout); empty = seeded init
     seed: int = 0
+    # input preprocessing, applied where the records are parsed (gale/models/preprocess.py):
+    # model input = (x * input_scale - mean[c]) / std[c]; mean / std are comma-separated lists of
+    # 1 value (broadcast) or one per channel (C <= 4), in the units after scaling
+    input_scale: float = 1.0
+    input_mean: str = ""
+    input_std: str = ""
+    input_layout: str = "nhwc"         # nchw: records nest [N][C][H][W]
     max_batch: int = 256
     max_wait_us: int = 2000
     slo_p99_ms: float = 0.0            # latency-SLO mode (config 5): adapt batch/wait to a p99
@@ -228,7 +237,18 @@ class GaleConfig:
             raise ValueError("topology name is required")
         if not self.fold_bn and self.dtype == "fp8":
             raise ValueError("--no-fold-bn (standalone BatchNorm plan) is bf16 / fp32 only")
+        self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
         return self
+
+    def input_prep(self, C: Optional[int] = None):
+        """The ``InputPrep`` of this configuration (C: the model's input channels)."""
+        from gale.models.preprocess import InputPrep
+
+        if C is None:
+            from gale.models import get_model
+
+            C = get_model(self.model).input_shape[2]
+        return InputPrep.from_config(self, C)
 
     @property
     def effective_group(self) -> str:
@@ -278,7 +298,7 @@ class GaleConfig:
             queue_depth=self.queue_depth,
             watchdog_ms=self.watchdog_ms, max_restarts=self.max_restarts,
             restart_backoff_ms=self.restart_backoff_ms, fault=self.fault, seed=self.seed,
-            trace=self.trace)
+            trace=self.trace, **self.input_prep(C).engine_entries())
 
 
 def _pack_fast() -> bool:

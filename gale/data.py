@@ -8,6 +8,7 @@ emit), one or more images per record.
 
 from __future__ import annotations
 
+import json
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -26,6 +27,29 @@ def encode_records(images: np.ndarray, images_per_record: int = 1) -> List[bytes
     out = []
     for i in range(0, images.shape[0], images_per_record):
         out.append(C.encode_instances(np.ascontiguousarray(images[i:i + images_per_record])))
+    return out
+
+
+def synthetic_pixels(n: int, shape: Sequence[int], seed: int = 0) -> np.ndarray:
+    """Raw 8-bit pixels (integers 0..255) of the model's input shape: what a client sends when
+    the topology scales and normalises on the GPU (--input-scale / --input-mean / --input-std)."""
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, 256, (n,) + tuple(shape), dtype=np.uint8)
+
+
+def encode_records_text(images: np.ndarray, images_per_record: int = 1,
+                        layout: str = "nhwc") -> List[bytes]:
+    """[N, H, W, C] -> InstObj records written by Python's compact ``json.dumps``: integer
+    arrays without a decimal point (``[[[[125,122,113],...``), and with ``layout="nchw"`` each
+    record's array nested [N][C][H][W] (what a PyTorch client holds; --input-layout nchw)."""
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"layout={layout!r}: expected nhwc or nchw")
+    if layout == "nchw":
+        images = images.transpose(0, 3, 1, 2)
+    out = []
+    for i in range(0, images.shape[0], images_per_record):
+        out.append(json.dumps({"instances": images[i:i + images_per_record].tolist()},
+                              separators=(",", ":")).encode())
     return out
 
 

@@ -111,6 +111,7 @@ class Engine:
     def _build_gpu_replicas(self, devices: Optional[Sequence[int]], params: Optional[dict]):
         import torch
 
+        from gale.models.preprocess import prep_or_none
         from gale.parallel.weights import materialize_weights
         from gale.runtime.replica import ModelReplica
 
@@ -128,7 +129,8 @@ class Engine:
         placement = replica_devices(n_rep, devices)
         used = sorted(set(placement), key=placement.index)
         src = materialize_weights(self.net, torch.device("cuda", used[0]), seed=self.cfg.seed,
-                                  wdtype=wdtype, params=params, fold_bn=self.cfg.fold_bn)
+                                  wdtype=wdtype, params=params, fold_bn=self.cfg.fold_bn,
+                                  prep=prep_or_none(self.cfg.input_prep(self.net.input_shape[2])))
         if len(used) > 1:  # one process, several GPUs: RCCL broadcast over xGMI
             from gale.parallel.weights import replicate_weights
 

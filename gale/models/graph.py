@@ -322,9 +322,10 @@ def pack_conv_weight(w: torch.Tensor, cin_s: int, Npad: int, Kpad: int) -> torch
 
 
 def pack_params(net: Network, folded: Dict[str, torch.Tensor], wdtype: str = "bf16",
-                fold_bn: bool = True) -> torch.Tensor:
+                fold_bn: bool = True, prep=None) -> torch.Tensor:
     """Fill the flat packed buffer (uint8 CPU tensor) from folded fp32 parameters
-    (``fold_params``), or with ``fold_bn=False`` from ``unfolded_params``."""
+    (``fold_params``), or with ``fold_bn=False`` from ``unfolded_params``. prep: the input
+    preprocessing the model is served behind (fp8: calibrates the activation scales on it)."""
     layout, total = param_layout(net, wdtype, fold_bn)
     buf = torch.zeros(total, dtype=torch.uint8)
 
@@ -371,7 +372,7 @@ def pack_params(net: Network, folded: Dict[str, torch.Tensor], wdtype: str = "bf
     if wdtype == "fp8":
         from gale.models.quant import activation_tensors, calibrate_act_scales
 
-        sc = calibrate_act_scales(net, folded)
+        sc = calibrate_act_scales(net, folded, prep)
         put("act_scales", torch.tensor([sc[n] for n in activation_tensors(net)],
                                        dtype=torch.float32))
     return buf

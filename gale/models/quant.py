@@ -64,8 +64,12 @@ def activation_tensors(net) -> list:
 
 
 @torch.no_grad()
-def calibrate_act_scales(net, folded: Dict[str, torch.Tensor]) -> Dict[str, float]:
+def calibrate_act_scales(net, folded: Dict[str, torch.Tensor], prep=None) -> Dict[str, float]:
     """Per-tensor e4m3 scales from the fp32 oracle on a seeded U[0,1) calibration batch.
+
+    prep (``gale.models.preprocess.InputPrep``): the model is served behind that input
+    preprocessing, so the calibration batch is the prep applied to ``U[0,1) / scale`` - that is
+    ``(u - mean) / std``, the range the input tensor really has. None: the batch as drawn.
 
     Pooling outputs inherit their input's scale (max / mean never leave its range), so pool ops
     pass codes through unchanged.
@@ -75,6 +79,8 @@ def calibrate_act_scales(net, folded: Dict[str, torch.Tensor]) -> Dict[str, floa
 
     g = torch.Generator().manual_seed(CALIB_SEED)
     x = torch.rand((CALIB_BATCH,) + tuple(net.input_shape), generator=g)
+    if prep is not None:
+        x = prep.apply((x.double() / prep.scale).float())
     tensors: Dict[str, torch.Tensor] = {}
     forward(net, folded, x, tensors=tensors)
     scales: Dict[str, float] = {}

@@ -19,23 +19,25 @@ from gale.models.graph import (Network, fold_params, init_params, pack_params, p
 
 
 def host_packed_params(net: Network, seed: int = 0, wdtype: str = "bf16",
-                       params: Optional[dict] = None, fold_bn: bool = True) -> torch.Tensor:
+                       params: Optional[dict] = None, fold_bn: bool = True,
+                       prep=None) -> torch.Tensor:
     if params is None:
         params = init_params(net, seed=seed)
     if not fold_bn:
         return pack_params(net, unfolded_params(net, params), wdtype, fold_bn=False)
-    return pack_params(net, fold_params(net, params), wdtype)
+    return pack_params(net, fold_params(net, params), wdtype, prep=prep)
 
 
 def materialize_weights(net: Network, device: torch.device, seed: int = 0, wdtype: str = "bf16",
                         src: int = 0, group=None, params: Optional[dict] = None,
-                        fold_bn: bool = True) -> torch.Tensor:
-    """Return the packed parameter buffer on ``device``, identical on every rank of ``group``."""
+                        fold_bn: bool = True, prep=None) -> torch.Tensor:
+    """Return the packed parameter buffer on ``device``, identical on every rank of ``group``.
+    prep: the served input preprocessing (``InputPrep`` or None; fp8 calibration)."""
     _, total = param_layout(net, wdtype, fold_bn)
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     rank = dist.get_rank() if distributed else src
     if rank == src:
-        buf = host_packed_params(net, seed, wdtype, params, fold_bn).to(device)
+        buf = host_packed_params(net, seed, wdtype, params, fold_bn, prep).to(device)
     else:
         buf = torch.empty(total, dtype=torch.uint8, device=device)
     if distributed:
