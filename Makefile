@@ -65,6 +65,15 @@ build/asan/engine_stress: $(SAN_SRC) $(HDRS)
 	@mkdir -p $(dir $@)
 	$(SAN_CXX) $(SAN_FLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined $(SAN_SRC) -o $@ $(SAN_LIBS)
 
+# the base64 record scanner / host decoder / splitter on mutated and truncated records
+# (csrc/tests/b64_scan_check.cpp): codec only, no engine
+build/asan/b64_scan_check: csrc/tests/b64_scan_check.cpp csrc/codec/json_codec.cpp \
+                           csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/b64_scan_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500
 

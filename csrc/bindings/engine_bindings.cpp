@@ -83,6 +83,11 @@ EngineConfig config_from_dict(const py::dict& d) {
   for (size_t i = 0; i < pa.size(); ++i) c.prep.a[i] = pa[i];
   for (size_t i = 0; i < pb.size(); ++i) c.prep.b[i] = pb[i];
   c.prep.nchw = nchw ? 1 : 0;
+  std::string input_format = "json";
+  opt(d, "input_format", input_format);
+  if (input_format != "json" && input_format != "b64")
+    throw std::invalid_argument("input_format: json or b64");
+  c.input_b64 = input_format == "b64";
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
   opt(d, "slo_p99_ms", c.slo_p99_ms);
@@ -108,6 +113,7 @@ void bind_engine(py::module_& m) {
              auto rep = std::make_shared<StubReplica>(c.H, c.W, c.C, c.classes, max_images,
                                                       delay_us, compute, locality);
              rep->set_input_prep(c.prep);
+             rep->set_input_b64(c.input_b64);
              e.add_replica(std::move(rep));
            },
            py::arg("max_images") = 256, py::arg("delay_us") = 0, py::arg("compute") = true,
@@ -122,6 +128,7 @@ void bind_engine(py::module_& m) {
                                                      locality, step_graph, high_priority,
                                                      step_direct);
              rep->set_input_prep(c.prep);
+             rep->set_input_b64(c.input_b64);
              e.add_replica(std::move(rep));
            },
            py::arg("executor"), py::arg("use_graph") = true, py::arg("wait_poll_us") = 0,
@@ -129,6 +136,9 @@ void bind_engine(py::module_& m) {
            py::arg("high_priority") = false, py::arg("step_direct") = false)
       .def("enable_gpu_ingest",
            [](Engine& e, int device, int lanes, int poll_us) {
+             if (e.config().input_b64)
+               throw std::invalid_argument("enable_gpu_ingest: not with input_format b64 (the "
+                                           "ingest's counting pass is a number-token pass)");
              auto ing = std::make_shared<GpuIngest>(device, lanes, poll_us);
              ing->set_input_prep(e.config().prep);
              e.set_ingest(std::move(ing));

@@ -434,6 +434,44 @@ void bind_host(py::module_& m) {
                                        C, out.mutable_data(), max_images, &images);
     return py::make_tuple(st, out);
   }, py::arg("data"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("max_images") = -1);
+  // ---- base64 uint8 image records (input format "b64") ----
+  m.def("scan_instances_b64", [](py::bytes b, int H, int W, int C) {
+    const std::string_view s = view(b);
+    const codec::Scan sc =
+        codec::scan_instances_b64(reinterpret_cast<const uint8_t*>(s.data()), s.size(), H, W, C);
+    return py::make_tuple(sc.status, sc.arr_off, sc.arr_len, sc.images);
+  });
+  m.def("parse_instances_b64_host", [](py::bytes b, int H, int W, int C, int max_images) {
+    // (status, float32 [N, H, W, C] in string order: [N][C][H][W] values for an NCHW record)
+    const std::string_view s = view(b);
+    const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+    const codec::Scan sc = codec::scan_instances_b64(p, s.size(), H, W, C);
+    const int n = sc.status == codec::OK ? sc.images : 0;
+    py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
+    int images = 0;
+    int st = sc.status;
+    if (st == codec::OK)
+      st = codec::parse_instances_b64_host(p, s.size(), H, W, C, out.mutable_data(), max_images,
+                                           &images);
+    return py::make_tuple(st, out);
+  }, py::arg("data"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("max_images") = -1);
+  m.def("b64_image_offsets", [](py::bytes arr, int H, int W, int C) -> py::object {
+    // of a scanned record's instances array: each image string's offset, None if it is broken
+    const std::string_view s = view(arr);
+    std::vector<uint32_t> offs;
+    if (!codec::b64_image_offsets(reinterpret_cast<const uint8_t*>(s.data()), s.size(), H, W, C,
+                                  offs))
+      return py::none();
+    return py::cast(offs);
+  });
+  m.def("split_instances_b64", [](py::bytes arr, int H, int W, int C) -> py::object {
+    const std::string_view s = view(arr);
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    if (!codec::split_instances_b64(reinterpret_cast<const uint8_t*>(s.data()), s.size(), H, W,
+                                    C, spans))
+      return py::none();
+    return py::cast(spans);
+  });
   m.def("apply_input_prep",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
            bool nchw, std::vector<float> a, std::vector<float> b) {

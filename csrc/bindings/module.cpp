@@ -254,6 +254,35 @@ PYBIND11_MODULE(_C, m) {
         py::arg("out"), py::arg("stream"), py::arg("count_pass") = true,
         py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("json_tile_count", &gale::json_tile_count);
+  m.def("b64_decode_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int H, int W, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images,
+           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b, bool nchw) {
+          // imgs: B64_IMAGE_BYTES-byte descriptors (int64 off, int32 slot, int32 rec); d_images
+          // non-zero: the image count is read there on the device (images = the launch size).
+          // a / b (four coefficients each) or nchw: an InputPrep is passed (identity ones too)
+          gale::InputPrep prep;
+          const bool with_prep = a || b || nchw;
+          if ((a && a->size() != 4) || (b && b->size() != 4))
+            throw std::invalid_argument("b64_decode_instances: a / b take four coefficients");
+          for (int i = 0; i < 4; ++i) {
+            if (a) prep.a[i] = (*a)[i];
+            if (b) prep.b[i] = (*b)[i];
+          }
+          prep.nchw = nchw ? 1 : 0;
+          chk(gale::b64_decode_instances(images, static_cast<const gale::B64Image*>(P(imgs)),
+                                         static_cast<const uint8_t*>(P(bytes)), H, W, C,
+                                         static_cast<float*>(P(out)),
+                                         static_cast<int*>(P(status)), S(stream),
+                                         static_cast<const int*>(P(d_images)),
+                                         with_prep ? &prep : nullptr),
+              "b64_decode_instances");
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("a") = py::none(), py::arg("b") = py::none(),
+        py::arg("nchw") = false);
+  m.attr("B64_IMAGE_BYTES") = (int)sizeof(gale::B64Image);
   py::module_ comm = m.def_submodule("comm", "in-process RCCL communicator (ncclCommInitAll)");
   py::class_<gale::CommGroup, std::shared_ptr<gale::CommGroup>>(comm, "CommGroup")
       .def(py::init([](std::vector<int> devices) {

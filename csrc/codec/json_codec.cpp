@@ -315,6 +315,199 @@ int parse_instances_host(const uint8_t* p, size_t n, int H, int W, int C, float*
   return OK;
 }
 
+// ---- base64 uint8 image records ------------------------------------------------------------------
+
+namespace {
+
+struct B64Elem {
+  size_t begin, str, end;  // the element's '{', its string's first character, one past its '}'
+};
+
+// A JSON value other than an object starts here (an element / b64 value of the wrong type).
+inline bool value_start(uint8_t c) {
+  return c == '[' || c == '"' || c == '-' || (c >= '0' && c <= '9') || c == 't' || c == 'f' ||
+         c == 'n' || c == '{';
+}
+
+// Walks the element list of a b64 instances array: p[i] is its '['. On OK *end is one past the
+// matching ']' and *images the element count; elems (optional) receives every element. Reads
+// nothing of a string's body; every access is below n.
+int walk_b64(const uint8_t* p, size_t i, size_t n, size_t L, size_t* end, int64_t* images,
+             std::vector<B64Elem>* elems) {
+  int64_t N = 0;
+  i = skip_ws(p, i + 1, n);
+  if (i < n && p[i] == ']') {
+    *end = i + 1;
+    *images = 0;
+    return OK;
+  }
+  for (;;) {
+    if (i >= n) return BAD_ENVELOPE;
+    if (p[i] != '{') return value_start(p[i]) ? BAD_SHAPE : BAD_ENVELOPE;
+    B64Elem e;
+    e.begin = i;
+    i = skip_ws(p, i + 1, n);
+    if (i >= n) return BAD_ENVELOPE;
+    if (p[i] == '}') return BAD_SHAPE;  // an object without the image
+    if (p[i] != '"') return BAD_ENVELOPE;
+    if (n - i < 5) return BAD_ENVELOPE;
+    if (memcmp(p + i + 1, "b64\"", 4) != 0) return UNKNOWN_KEY;
+    i = skip_ws(p, i + 5, n);
+    if (i >= n || p[i] != ':') return BAD_ENVELOPE;
+    i = skip_ws(p, i + 1, n);
+    if (i >= n) return BAD_ENVELOPE;
+    if (p[i] != '"') return value_start(p[i]) ? BAD_SHAPE : BAD_ENVELOPE;
+    e.str = i + 1;
+    if (n - e.str <= L || p[e.str + L] != '"') return BAD_SHAPE;
+    i = skip_ws(p, e.str + L + 1, n);
+    if (i >= n) return BAD_ENVELOPE;
+    if (p[i] == ',') return UNKNOWN_KEY;  // a second key
+    if (p[i] != '}') return BAD_ENVELOPE;
+    e.end = ++i;
+    if (++N > (1 << 30)) return TOO_LARGE;
+    if (elems) elems->push_back(e);
+    i = skip_ws(p, i, n);
+    if (i >= n) return BAD_ENVELOPE;
+    if (p[i] == ']') break;
+    if (p[i] != ',') return BAD_ENVELOPE;
+    i = skip_ws(p, i + 1, n);
+  }
+  *end = i + 1;
+  *images = N;
+  return OK;
+}
+
+// Sextet of a base64 character, 0xFF outside the alphabet.
+struct B64Table {
+  uint8_t v[256];
+  B64Table() {
+    memset(v, 0xFF, sizeof(v));
+    static const char kAlphabet[] =
+        "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+    for (int i = 0; i < 64; ++i) v[(uint8_t)kAlphabet[i]] = (uint8_t)i;
+  }
+};
+
+int walk_b64_array(const uint8_t* arr, size_t len, int H, int W, int C,
+                   std::vector<B64Elem>& elems) {
+  elems.clear();
+  if (len < 2 || arr[0] != '[' || H <= 0 || W <= 0 || C <= 0) return BAD_ENVELOPE;
+  size_t end = 0;
+  int64_t N = 0;
+  const int st = walk_b64(arr, 0, len, (size_t)b64_chars(H, W, C), &end, &N, &elems);
+  if (st != OK) return st;
+  return end == len ? OK : BAD_ENVELOPE;
+}
+
+}  // namespace
+
+Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C) {
+  Scan s;
+  if (H <= 0 || W <= 0 || C <= 0) { s.status = BAD_SHAPE; return s; }
+  // the {"instances": prefix (as scan_envelope reads it)
+  size_t i = skip_ws(p, 0, n);
+  if (i >= n || p[i] != '{') { s.status = BAD_ENVELOPE; return s; }
+  i = skip_ws(p, i + 1, n);
+  if (i < n && p[i] == '}') { s.status = NULL_INSTANCES; return s; }
+  if (i >= n || p[i] != '"') { s.status = BAD_ENVELOPE; return s; }
+  static const char kKey[] = "instances";
+  const size_t ks = i + 1;
+  size_t ke = ks;
+  while (ke < n && p[ke] != '"') {
+    if (p[ke] == '\\') ++ke;
+    ++ke;
+  }
+  if (ke >= n) { s.status = BAD_ENVELOPE; return s; }
+  if (ke - ks != sizeof(kKey) - 1 || memcmp(p + ks, kKey, sizeof(kKey) - 1) != 0) {
+    s.status = UNKNOWN_KEY;
+    return s;
+  }
+  i = skip_ws(p, ke + 1, n);
+  if (i >= n || p[i] != ':') { s.status = BAD_ENVELOPE; return s; }
+  i = skip_ws(p, i + 1, n);
+  if (n - i >= 4 && memcmp(p + i, "null", 4) == 0) {
+    const size_t j = skip_ws(p, i + 4, n);
+    s.status = (j < n && p[j] == '}') ? NULL_INSTANCES
+               : (j < n && p[j] == ',') ? UNKNOWN_KEY : BAD_ENVELOPE;
+    return s;
+  }
+  if (i >= n || p[i] != '[') { s.status = BAD_ENVELOPE; return s; }
+  const size_t beg = i;
+  size_t end = 0;
+  int64_t N = 0;
+  s.status = walk_b64(p, beg, n, (size_t)b64_chars(H, W, C), &end, &N, nullptr);
+  if (s.status != OK) return s;
+  // the "] ws } ws" suffix
+  i = skip_ws(p, end, n);
+  if (i >= n || p[i] != '}') {
+    s.status = (i < n && p[i] == ',') ? UNKNOWN_KEY : BAD_ENVELOPE;
+    return s;
+  }
+  if (skip_ws(p, i + 1, n) != n) { s.status = BAD_ENVELOPE; return s; }
+  if (N == 0) { s.status = EMPTY; return s; }
+  s.arr_off = (int64_t)beg;
+  s.arr_len = (int64_t)(end - beg);
+  s.images = (int)N;
+  return s;
+}
+
+bool b64_image_offsets(const uint8_t* arr, size_t len, int H, int W, int C,
+                       std::vector<uint32_t>& offs) {
+  std::vector<B64Elem> elems;
+  offs.clear();
+  if (len > UINT32_MAX || walk_b64_array(arr, len, H, W, C, elems) != OK) return false;
+  offs.reserve(elems.size());
+  for (const B64Elem& e : elems) offs.push_back((uint32_t)e.str);
+  return true;
+}
+
+bool split_instances_b64(const uint8_t* arr, size_t len, int H, int W, int C,
+                         std::vector<std::pair<uint32_t, uint32_t>>& spans) {
+  std::vector<B64Elem> elems;
+  spans.clear();
+  if (len > UINT32_MAX || walk_b64_array(arr, len, H, W, C, elems) != OK) return false;
+  spans.reserve(elems.size());
+  for (const B64Elem& e : elems) spans.emplace_back((uint32_t)e.begin, (uint32_t)e.end);
+  return true;
+}
+
+int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
+                             int max_images, int* images) {
+  static const B64Table table;
+  *images = 0;
+  const Scan s = scan_instances_b64(p, n, H, W, C);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  std::vector<B64Elem> elems;
+  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, H, W, C, elems);
+  if (st != OK) return st;
+  const size_t per = (size_t)H * W * C, L = (size_t)b64_chars(H, W, C);
+  const size_t pad = (3 - per % 3) % 3;
+  for (size_t e = 0; e < elems.size(); ++e) {
+    const uint8_t* q = p + s.arr_off + elems[e].str;
+    float* dst = out ? out + e * per : nullptr;
+    for (size_t g = 0; g < L; g += 4) {
+      uint32_t v = 0;
+      for (size_t j = 0; j < 4; ++j) {
+        uint8_t x = table.v[q[g + j]];
+        if (g + j >= L - pad) {
+          if (q[g + j] != '=') return BAD_NUMBER;
+          x = 0;
+        } else if (x == 0xFF) {
+          return BAD_NUMBER;
+        }
+        v = (v << 6) | x;
+      }
+      if (!dst) continue;
+      const size_t o = g / 4 * 3;
+      for (size_t j = 0; j < 3 && o + j < per; ++j)
+        dst[o + j] = (float)((v >> (16 - 8 * j)) & 0xFF);
+    }
+  }
+  *images = s.images;
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

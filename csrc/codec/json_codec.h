@@ -80,6 +80,41 @@ int parse_instances_host(const uint8_t* p, size_t n, int H, int W, int C, float*
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b);
 
+// ---- base64 uint8 image records (input format "b64") -------------------------------------------
+//     {"instances":[{"b64":"<base64 of image 0>"},{"b64":"..."}]}
+// One object per image with exactly one key, "b64"; its string is standard base64 (RFC 4648 §4)
+// of exactly H*W*C bytes, one uint8 value each, so its length is L = 4 * ceil(H*W*C / 3) with
+// the last (3 - H*W*C % 3) % 3 characters '='. The string body is never unescaped.
+
+// Characters of one image's string.
+inline int64_t b64_chars(int H, int W, int C) { return 4 * (((int64_t)H * W * C + 2) / 3); }
+
+// Envelope and element-list check + image count. Walks the elements and never reads a string's
+// body: after the opening quote it checks the closing quote L characters on. O(images), every
+// access bounded by n. Verdicts: BAD_ENVELOPE (not an object, no instances array, syntax around
+// the elements, a cut-off value), UNKNOWN_KEY (another top-level key; a key other than "b64" or
+// a second key in an element), NULL_INSTANCES, EMPTY, BAD_SHAPE (an element that is not an
+// object, a value that is not a string, a closing quote not at L characters), TOO_LARGE
+// (more than 2^30 images). The characters themselves are judged by the decoder (BAD_NUMBER).
+Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C);
+
+// Of a scanned record's instances array `arr[0..len)`: the offset (from arr) of the first
+// character of every image's string. false when the element list is not what the scan accepted.
+bool b64_image_offsets(const uint8_t* arr, size_t len, int H, int W, int C,
+                       std::vector<uint32_t>& offs);
+
+// split_instances for b64 records: the byte spans [begin, end) of the elements (each image's
+// {"b64":"..."} object).
+bool split_instances_b64(const uint8_t* arr, size_t len, int H, int W, int C,
+                         std::vector<std::pair<uint32_t, uint32_t>>& spans);
+
+// Full host decoder: the scan's verdicts, then every string decoded into out[N*H*W*C] as
+// (float)byte in string order (what parse_instances_host gives for the same pixels written as
+// numbers). A character outside the alphabet in the data part, or a non-'=' in the padding, is
+// BAD_NUMBER; unused low bits of the last data character are ignored. out may be null.
+int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
+                             int max_images, int* images);
+
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.
 int format_float_java(float v, char* out);

@@ -284,6 +284,33 @@ hipError_t json_parse_instances(int nrec, int ntiles, JsonRecord* recs, const in
                                 const int* d_ntiles = nullptr, int* status = nullptr,
                                 int* tile_bad = nullptr, const InputPrep* prep = nullptr);
 
+// GPU decoder of base64 uint8 image records (input format "b64", csrc/codec/json_codec.h): every
+// image's string - L = 4 * ceil(H*W*C / 3) characters of standard base64, the last
+// (3 - H*W*C % 3) % 3 of them '=' - becomes H*W*C floats (float)byte in the fp32 NHWC batch
+// tensor. A lane decodes 16 characters into 12 values, a 256-thread workgroup 4096 characters;
+// the grid is (chunks per image) x (images).
+constexpr int kB64ChunkChars = 4096;
+struct B64Image {
+  int64_t off;   // byte offset of the string's first character inside the staged byte buffer
+  int32_t slot;  // the image's slot in the batch
+  int32_t rec;   // index of the owning record in `status`
+};
+static_assert(sizeof(B64Image) == 16, "B64Image layout (host <-> device tables)");
+// status[rec] is set to 2 (host zeroes it) when a character outside the alphabet stands in the
+// data part of one of the record's strings or a non-'=' in its padding; the image is written
+// anyway (within its own slot). Any 16-byte phase of `off` is fine: the kernel loads the aligned
+// 16-byte words around a lane's window, so it reads at most 15 bytes before a string and fewer
+// than 16 bytes past it.
+// d_images non-null: the image count is read from device memory (images = the most the launch
+// is sized for; workgroups past the device count exit) - the captured step graph's form; imgs
+// and d_images may be host-mapped pinned memory.
+// prep null or identity: the instantiation without the preprocessing code. Otherwise the value v
+// of channel c is stored as fmaf(v, a[c], b[c]), and with nchw the string's bytes are ordered
+// [C][H][W] and the store transposes to NHWC; C <= 4 unless a / b are uniform.
+hipError_t b64_decode_instances(int images, const B64Image* imgs, const uint8_t* bytes, int H,
+                                int W, int C, float* out, int* status, hipStream_t stream,
+                                const int* d_images = nullptr, const InputPrep* prep = nullptr);
+
 // Raw (zero initial state, no final inversion) CRC32C of byte windows [end - len, end) of a
 // device buffer, one wave per window (len <= kCrcChunkBytes): each lane folds 64 bytes with
 // slicing-by-4 tables in LDS, shifts its register over the bytes after its piece (one GF(2)

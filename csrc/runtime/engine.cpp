@@ -223,6 +223,9 @@ void Engine::add_replica(std::shared_ptr<Replica> r) {
 
 void Engine::set_ingest(std::shared_ptr<Ingest> ing) {
   if (running_) throw std::logic_error("engine: set_ingest after start");
+  if (cfg_.input_b64)
+    throw std::invalid_argument("engine: no GPU ingest with input_format b64 (its counting pass "
+                                "is a number-token pass)");
   ingests_[ing->device()] = std::move(ing);
 }
 
@@ -1026,6 +1029,11 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   const bool nchw = cfg_.prep.nchw != 0;
   const int scan_h = nchw ? cfg_.C : cfg_.H, scan_w = nchw ? cfg_.H : cfg_.W,
             scan_c = nchw ? cfg_.W : cfg_.C;
+  const bool b64 = cfg_.input_b64;
+  auto scan = [&](const uint8_t* p, size_t n) {
+    return b64 ? codec::scan_instances_b64(p, n, cfg_.H, cfg_.W, cfg_.C)
+               : codec::scan_instances(p, n, scan_h, scan_w, scan_c);
+  };
   if (cfg_.check_crcs && !f.crc_checked) {
     corrupt.assign(f.records.size(), 0);
     pre.resize(f.records.size());
@@ -1046,8 +1054,7 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
           crc = kafka::crc32c(pos, (size_t)(vend - pos), crc);
           pos = vend;
         }
-        pre[i] = codec::scan_instances(base + rr.value_off, (size_t)rr.value_len, scan_h,
-                                       scan_w, scan_c);
+        pre[i] = scan(base + rr.value_off, (size_t)rr.value_len);
         have_pre[i] = 1;
       }
       if (end > pos) crc = kafka::crc32c(pos, (size_t)(end - pos), crc);
@@ -1079,15 +1086,14 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       r.status = codec::BAD_ENVELOPE;  // null value (Jackson would throw)
     } else {
       bytes_in_ += r.len;
-      const codec::Scan s = !have_pre.empty() && have_pre[i]
-                                ? pre[i]
-                                : codec::scan_instances(r.value, (size_t)r.len, scan_h, scan_w,
-                                                        scan_c);
+      const codec::Scan s =
+          !have_pre.empty() && have_pre[i] ? pre[i] : scan(r.value, (size_t)r.len);
       r.status = s.status;
       r.arr_off = s.arr_off;
       r.arr_len = s.arr_len;
       r.images = s.images;
       if (r.status == codec::OK && fault_hit(parse_error_p_)) r.status = codec::BAD_ENVELOPE;
+      if (b64 && r.status == codec::OK) ++b64_records_;
     }
     if (r.status == codec::OK && r.images > cfg_.max_batch) {
       images_in_ += r.images;
@@ -1606,8 +1612,10 @@ void Engine::emit(InRecord& r, std::string value, bool null_value, kafka::Produc
 bool Engine::split_record(InRecord& r, std::vector<InRecord>& good) {
   std::vector<std::pair<uint32_t, uint32_t>> spans;
   const uint8_t* arr = r.value + r.arr_off;
-  if (!codec::split_instances(arr, (size_t)r.arr_len, spans) || (int)spans.size() != r.images)
-    return false;
+  const bool ok = cfg_.input_b64 ? codec::split_instances_b64(arr, (size_t)r.arr_len, cfg_.H,
+                                                              cfg_.W, cfg_.C, spans)
+                                 : codec::split_instances(arr, (size_t)r.arr_len, spans);
+  if (!ok || (int)spans.size() != r.images) return false;
   const int mb = cfg_.max_batch;
   const int parts = (r.images + mb - 1) / mb;
   auto sp = std::make_shared<SplitRecord>();
@@ -1746,6 +1754,7 @@ std::map<std::string, double> Engine::stats() const {
   s["poison_records"] = (double)poison_records_;
   s["poison_unknown_span"] = (double)poison_unknown_span_;
   s["split_records"] = (double)split_records_;
+  s["b64_records"] = (double)b64_records_;
   s["sparse_fetches"] = (double)sparse_fetches_;
   s["restored_fetches"] = (double)restored_fetches_;
   {

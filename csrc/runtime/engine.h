@@ -131,6 +131,11 @@ struct EngineConfig {
   // input preprocessing applied where the records are parsed (InputPrep, gale/kernels.h); with
   // prep.nchw the records nest [N][C][H][W] and the host scans count their brackets that way
   InputPrep prep;
+  // input format "b64": a record's instances array holds one {"b64": "<base64 of H*W*C uint8
+  // values>"} object per image (csrc/codec/json_codec.h) instead of nested number arrays. The
+  // host scans with codec::scan_instances_b64 and the replicas decode the strings; no GPU ingest
+  // is attached in this mode (its counting pass is a number-token pass)
+  bool input_b64 = false;
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
   int max_wait_us = 2000;          // latency bound on batch formation
@@ -410,6 +415,7 @@ class Engine {
   std::atomic<int64_t> converted_batches_{0}, poison_batches_{0}, poison_records_{0};
   std::atomic<int64_t> poison_unknown_span_{0};  // legacy wrapper poison on an estimated span
   std::atomic<int64_t> split_records_{0}, split_fragments_{0};
+  std::atomic<int64_t> b64_records_{0};  // records the b64 scan accepted (handed to a decoder)
   std::atomic<int64_t> sparse_fetches_{0}, restored_fetches_{0};  // bounce receive (pack_tap.h)
   Histogram h_queue_us_, h_device_us_, h_engine_e2e_us_, h_record_e2e_ms_, h_batch_images_;
   Histogram h_slo_win_us_;  // e2e latency of the SLO controller's current window

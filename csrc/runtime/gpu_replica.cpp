@@ -260,6 +260,35 @@ void GpuReplica::submit(Batch& b) {
     if (ptr_input_)
       for (int k = 0; k < r.images; ++k) s.h_xs[img + k] = in + (int64_t)(img + k) * per;
     s.parse_idx[ri] = nrec;
+    if (b64_) {
+      // one descriptor per image: where its string starts in the staged bytes
+      const uint8_t* base = r.buf.get();
+      const size_t lo = (size_t)(r.value + r.arr_off - base);
+      int64_t off;
+      if (resident(r)) {
+        off = (int64_t)((r.dev_value + r.arr_off) - s.d_bytes);
+      } else if (r.pinned) {
+        size_t k = 0;
+        while (spans[k].base != base) ++k;
+        off = (int64_t)(span_dev[k] + (lo - spans[k].lo));
+      } else {
+        hoff += (lo - hoff) & 15;  // keep the record's alignment modulo 16
+        memcpy(s.h_bytes + hoff, r.value + r.arr_off, (size_t)r.arr_len);
+        off = (int64_t)(staged_dev + hoff);
+        hoff = (hoff + (size_t)r.arr_len + 15) & ~(size_t)15;
+      }
+      if (!codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, H_, W_, C_,
+                                    s.b64_offs) ||
+          (int)s.b64_offs.size() != r.images)
+        throw std::logic_error("GpuReplica: b64 record does not match its scan");
+      B64Image* tab = b64_table(s.h_recs);
+      for (int k = 0; k < r.images; ++k)
+        tab[img + k] = B64Image{off + (int64_t)s.b64_offs[(size_t)k], img + k, nrec};
+      b64_status(s.h_recs)[nrec] = 0;
+      ++nrec;
+      img += r.images;
+      continue;
+    }
     JsonRecord& jr = s.h_recs[nrec++];
     const uint8_t* base = r.buf.get();
     const size_t lo = (size_t)(r.value + r.arr_off - base);
@@ -327,6 +356,7 @@ void GpuReplica::submit(Batch& b) {
       const size_t rec_bytes = meta_rec_bytes();
       const size_t used = ntiles > 0 ? kMetaHdr + rec_bytes + sizeof(int) * (size_t)ntiles
                           : ptr_input_ ? kMetaHdr + rec_bytes
+                          : b64_       ? kMetaHdr + sizeof(B64Image) * (size_t)img
                                        : kMetaHdr + sizeof(JsonRecord) * (size_t)nrec;
       check_hip(hipMemcpyAsync(s.d_hdr, s.h_hdr, used, hipMemcpyHostToDevice, stream_),
                 "H2D step metadata");
@@ -341,15 +371,20 @@ void GpuReplica::submit(Batch& b) {
     s.t_submit_ns = mono_ns();
     return;
   }
-  const size_t meta = reinterpret_cast<char*>(s.h_tile_rec + ntiles) -
-                      reinterpret_cast<char*>(s.h_recs);
+  // (b64: the descriptor table and the status words behind it)
+  const size_t meta = b64_ ? (sizeof(B64Image) + sizeof(int)) * (size_t)exec_->max_batch()
+                           : (size_t)(reinterpret_cast<char*>(s.h_tile_rec + ntiles) -
+                                      reinterpret_cast<char*>(s.h_recs));
   check_hip(hipMemcpyAsync(s.d_recs, s.h_recs, meta, hipMemcpyHostToDevice, stream_),
             "H2D recs");
-  check_hip(json_parse_instances(nrec, ntiles, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
-                                 s.d_tiles,
-                                 static_cast<float*>(exec_->input(slot)), stream_, count_pass,
-                                 nullptr, nullptr, nullptr, &prep_),
-            "json_parse_instances");
+  if (b64_)
+    check_hip(launch_b64(s, slot, img, stream_, nullptr, nullptr), "b64_decode_instances");
+  else
+    check_hip(json_parse_instances(nrec, ntiles, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
+                                   s.d_tiles,
+                                   static_cast<float*>(exec_->input(slot)), stream_, count_pass,
+                                   nullptr, nullptr, nullptr, &prep_),
+              "json_parse_instances");
   exec_->run(slot, img, stream_, use_graph_);
   if (use_graph_ && exec_->graph_pays()) ++fwd_graph_batches_;
   if (gpu_encode_) {
@@ -365,11 +400,23 @@ void GpuReplica::submit(Batch& b) {
                              hipMemcpyDeviceToHost, stream_),
               "D2H probs");
   }
-  check_hip(hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * nrec, hipMemcpyDeviceToHost,
-                           stream_),
-            "D2H status");
+  if (b64_)
+    check_hip(hipMemcpyAsync(b64_status(s.h_recs), b64_status(s.d_recs), sizeof(int) * nrec,
+                             hipMemcpyDeviceToHost, stream_),
+              "D2H status");
+  else
+    check_hip(hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * nrec,
+                             hipMemcpyDeviceToHost, stream_),
+              "D2H status");
   check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
   s.t_submit_ns = mono_ns();
+}
+
+hipError_t GpuReplica::launch_b64(Slot& s, int slot, int images, hipStream_t st,
+                                  const int* d_images, int* status) {
+  return b64_decode_instances(images, b64_table(s.d_recs), s.d_bytes, H_, W_, C_,
+                              static_cast<float*>(exec_->input(slot)),
+                              status ? status : b64_status(s.d_recs), st, d_images, &prep_);
 }
 
 // Every record of the batch parsed by the ingest pass (into at most kInputTableBases arenas):
@@ -424,7 +471,9 @@ hipError_t GpuReplica::enqueue_step(Slot& s, int slot, bool count_pass, hipStrea
                                      bool parse, bool xs) {
   const int mb = exec_->max_batch();
   hipError_t c = hipSuccess;
-  if (parse)  // (a batch of records the ingest already parsed: the forward alone)
+  if (parse && b64_)
+    c = launch_b64(s, slot, mb, st, s.d_hdr + 2, s.d_status);
+  else if (parse)  // (a batch of records the ingest already parsed: the forward alone)
     c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                              s.d_tiles, static_cast<float*>(exec_->input(slot)), st, count_pass,
                              s.d_hdr + 1, s.d_status, nullptr, &prep_);
@@ -468,7 +517,9 @@ hipGraphExec_t GpuReplica::step_for(Slot& s, int slot, bool count_pass) {
     if (e == hipSuccess) e = c;
   } else if (e == hipSuccess) {
     hipError_t c = hipMemcpyAsync(s.d_hdr, s.h_hdr, meta, hipMemcpyHostToDevice, cs);
-    if (c == hipSuccess)
+    if (c == hipSuccess && b64_)
+      c = launch_b64(s, slot, mb, cs, s.d_hdr + 2, nullptr);
+    else if (c == hipSuccess)
       c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                                s.d_tiles, static_cast<float*>(exec_->input(slot)), cs,
                                count_pass, s.d_hdr + 1, nullptr, nullptr, &prep_);
@@ -487,7 +538,10 @@ hipGraphExec_t GpuReplica::step_for(Slot& s, int slot, bool count_pass) {
               : hipMemcpyAsync(s.h_out, exec_->output(slot), sizeof(float) * mb * classes_,
                                hipMemcpyDeviceToHost, cs);
     if (c == hipSuccess)
-      c = hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * mb, hipMemcpyDeviceToHost, cs);
+      c = b64_ ? hipMemcpyAsync(b64_status(s.h_recs), b64_status(s.d_recs), sizeof(int) * mb,
+                                hipMemcpyDeviceToHost, cs)
+               : hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * mb,
+                                hipMemcpyDeviceToHost, cs);
     e = hipStreamEndCapture(cs, &graph);
     if (e == hipSuccess) e = c;
   }
@@ -528,7 +582,9 @@ void GpuReplica::wait(Batch& b) {
   for (size_t i = 0; i < b.recs.size(); ++i) {
     const int k = i < s.parse_idx.size() ? s.parse_idx[i] : (int)i;
     if (k < 0) continue;  // parsed (and judged) by the ingest pass
-    const int st = copy_free ? s.h_status[k] : s.h_recs[k].status;
+    const int st = copy_free ? s.h_status[k]
+                   : b64_    ? b64_status(s.h_recs)[k]
+                             : s.h_recs[k].status;
     if (st == 1 || st == 3) b.dev_status[i] = codec::BAD_SHAPE;
     else if (st == 2) b.dev_status[i] = codec::BAD_NUMBER;
   }

@@ -42,10 +42,14 @@ void StubReplica::submit(Batch& b) {
     int n = 0;
     // an NCHW record is a rectangular array of dims (C, H, W) to the dims-agnostic decoder
     const bool nchw = prep_.nchw != 0;
-    const int st = codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : H_,
-                                               nchw ? H_ : W_, nchw ? W_ : C_,
-                                               x_.data() + (size_t)slot * per,
-                                               max_images_ - slot, &n);
+    // (a b64 string's bytes are in record order too: [C][H][W] with nchw)
+    const int st = b64_ ? codec::parse_instances_b64_host(r.value, (size_t)r.len, H_, W_, C_,
+                                                          x_.data() + (size_t)slot * per,
+                                                          max_images_ - slot, &n)
+                        : codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : H_,
+                                                      nchw ? H_ : W_, nchw ? W_ : C_,
+                                                      x_.data() + (size_t)slot * per,
+                                                      max_images_ - slot, &n);
     if (st != codec::OK) b.dev_status[ri] = st;
     else if (!prep_.identity())
       codec::apply_input_prep(x_.data() + (size_t)slot * per, n, H_, W_, C_, nchw, prep_.a,

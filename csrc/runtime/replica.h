@@ -115,9 +115,12 @@ class StubReplica : public Replica {
   void wait(Batch& b) override;
   // input preprocessing (InputPrep, gale/kernels.h) on the host-parsed images; before submit()
   void set_input_prep(const InputPrep& p) { prep_ = p; }
+  // base64 uint8 image records (EngineConfig::input_b64): decoded by the host decoder
+  void set_input_b64(bool on) { b64_ = on; }
 
  private:
   InputPrep prep_;
+  bool b64_ = false;
   int H_, W_, C_, classes_, max_images_, delay_us_;
   bool compute_;
   int locality_ = -1;  // false: a "null" replica (uniform softmax, no parsing) to measure host paths
@@ -169,6 +172,12 @@ class GpuReplica : public Replica {
   // input preprocessing of every parse this replica launches (InputPrep, gale/kernels.h): by
   // value in the parse's kernel arguments, so it is part of a captured step; before submit()
   void set_input_prep(const InputPrep& p) { prep_ = p; }
+  // base64 uint8 image records (EngineConfig::input_b64): the step runs b64_decode_instances
+  // where it runs json_parse_instances otherwise. The batch's image descriptor table and (for
+  // the steps that copy verdicts back) its status words take the place of the JsonRecord table
+  // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
+  // map, no count pass. Before submit()
+  void set_input_b64(bool on) { b64_ = on; }
 
  private:
   static constexpr size_t kMetaHdr = 64;  // [nrec, ntiles, images, ...] ahead of the records
@@ -198,6 +207,7 @@ class GpuReplica : public Replica {
     const float** d_xs = nullptr;
     // per batch record: its index among the records the step parses (-1: parsed at ingest)
     std::vector<int> parse_idx;
+    std::vector<uint32_t> b64_offs;  // (b64 mode) scratch: a record's string offsets
     hipEvent_t done = nullptr;
     int64_t t_submit_ns = 0;
   };
@@ -211,9 +221,19 @@ class GpuReplica : public Replica {
   template <typename Pre>
   bool try_table_step(Batch& b, Slot& s, int slot, const Pre& preparsed);
   size_t meta_rec_bytes() const;  // records + input pointer table of the metadata allocation
+  // b64 mode: the views of the record table's place (see set_input_b64)
+  B64Image* b64_table(JsonRecord* recs) const { return reinterpret_cast<B64Image*>(recs); }
+  int* b64_status(JsonRecord* recs) const {
+    return reinterpret_cast<int*>(b64_table(recs) + exec_->max_batch());
+  }
+  // the decode launch of a b64 step: `images` images, or with d_images the count read on the
+  // device; status null: the status words behind the descriptor table
+  hipError_t launch_b64(Slot& s, int slot, int images, hipStream_t st, const int* d_images,
+                        int* status);
   static void* mapped_alloc(size_t bytes, const char* what);
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
+  bool b64_ = false;
   int H_, W_, C_, classes_;
   bool use_graph_;
   int wait_poll_us_ = 0;

@@ -11,6 +11,7 @@
     python -m gale broker [--port 9092] [--partitions N]     embedded Kafka-protocol broker
     python -m gale produce <TOPIC> [--images N] [--model M] [--rate R]   synthetic InstObj load
         [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
+        [--encoding json|b64]                         b64: base64 uint8 records (--pixels byte)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
 
 ``--profile DIR`` re-runs the topology under ``rocprofv3 --kernel-trace --marker-trace --stats``
@@ -190,8 +191,8 @@ def cmd_broker(argv: List[str]) -> int:
 
 def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
-    from gale.data import (encode_records, encode_records_text, synthetic_images,
-                           synthetic_pixels)
+    from gale.data import (encode_records, encode_records_b64, encode_records_text,
+                           synthetic_images, synthetic_pixels)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -207,9 +208,17 @@ def cmd_produce(argv: List[str]) -> int:
                          "(serve them with --input-scale 0.00392156862745098)")
     ap.add_argument("--layout", default="nhwc", choices=CHOICES["input_layout"],
                     help="nesting of each record's instances array (nchw: --input-layout nchw)")
+    ap.add_argument("--encoding", default="json", choices=CHOICES["input_format"],
+                    help="b64: one {\"b64\": ...} object of base64 uint8 pixels per image "
+                         "(--input-format b64); needs --pixels byte")
     a = ap.parse_args(argv)
+    if a.encoding == "b64" and a.pixels != "byte":
+        ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
-    if a.pixels == "unit" and a.layout == "nhwc":
+    if a.encoding == "b64":
+        recs = encode_records_b64(synthetic_pixels(a.images, net.input_shape, a.seed),
+                                  a.images_per_record, a.layout)
+    elif a.pixels == "unit" and a.layout == "nhwc":
         recs = encode_records(synthetic_images(a.images, net.input_shape, a.seed),
                               a.images_per_record)
     else:  # written by Python's compact json.dumps

@@ -37,6 +37,9 @@ CHOICES = {
     "model": ("lenet5", "resnet20", "resnet50"),
     # nesting order of a record's instances array (the model's tensors stay NHWC)
     "input_layout": ("nhwc", "nchw"),
+    # what a record's instances array holds: "json" nested number arrays, "b64" one
+    # {"b64": "<base64 of H*W*C uint8 values>"} object per image, decoded on the GPU
+    "input_format": ("json", "b64"),
 }
 
 
@@ -150,6 +153,7 @@ class GaleConfig:
     input_mean: str = ""
     input_std: str = ""
     input_layout: str = "nhwc"         # nchw: records nest [N][C][H][W]
+    input_format: str = "json"         # b64: base64 uint8 image records (no GPU ingest / packing)
     max_batch: int = 256
     max_wait_us: int = 2000
     slo_p99_ms: float = 0.0            # latency-SLO mode (config 5): adapt batch/wait to a p99
@@ -284,7 +288,8 @@ class GaleConfig:
             lag_rebalance_records=self.lag_rebalance_records,
             rebalance_cooldown_ms=self.rebalance_cooldown_ms,
             decode_threads=self.decode_threads, check_crcs=self.check_crcs,
-            text_pack=bool(self.gpu_ingest and self.text_pack and _pack_fast()),
+            text_pack=bool(self.gpu_ingest and self.text_pack and self.input_format == "json"
+                           and _pack_fast()),
             text_pack_bounce=self.text_pack_bounce, text_pack_window_kb=self.text_pack_window_kb,
             acks=self.acks, sink_mode=self.sink_mode, linger_ms=self.linger_ms,
             compression=self.compression,
@@ -298,7 +303,8 @@ class GaleConfig:
             queue_depth=self.queue_depth,
             watchdog_ms=self.watchdog_ms, max_restarts=self.max_restarts,
             restart_backoff_ms=self.restart_backoff_ms, fault=self.fault, seed=self.seed,
-            trace=self.trace, **self.input_prep(C).engine_entries())
+            trace=self.trace, input_format=self.input_format,
+            **self.input_prep(C).engine_entries())
 
 
 def _pack_fast() -> bool:

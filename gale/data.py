@@ -8,6 +8,7 @@ emit), one or more images per record.
 
 from __future__ import annotations
 
+import base64
 import json
 from typing import List, Sequence, Tuple
 
@@ -50,6 +51,26 @@ def encode_records_text(images: np.ndarray, images_per_record: int = 1,
     for i in range(0, images.shape[0], images_per_record):
         out.append(json.dumps({"instances": images[i:i + images_per_record].tolist()},
                               separators=(",", ":")).encode())
+    return out
+
+
+def encode_records_b64(images_u8: np.ndarray, images_per_record: int = 1,
+                       layout: str = "nhwc") -> List[bytes]:
+    """uint8 [N, H, W, C] -> ``{"instances":[{"b64":"..."},...]}`` records (--input-format b64):
+    each image's H*W*C bytes in standard base64, ordered [H][W][C], or [C][H][W] with
+    ``layout="nchw"`` (--input-layout nchw)."""
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"layout={layout!r}: expected nhwc or nchw")
+    images_u8 = np.asarray(images_u8)
+    if images_u8.dtype != np.uint8 or images_u8.ndim != 4:
+        raise ValueError("encode_records_b64: uint8 [N, H, W, C] images")
+    if layout == "nchw":
+        images_u8 = images_u8.transpose(0, 3, 1, 2)
+    out = []
+    for i in range(0, images_u8.shape[0], images_per_record):
+        elems = [b'{"b64":"' + base64.b64encode(np.ascontiguousarray(im).tobytes()) + b'"}'
+                 for im in images_u8[i:i + images_per_record]]
+        out.append(b'{"instances":[' + b",".join(elems) + b"]}")
     return out
 
 

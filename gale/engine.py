@@ -16,12 +16,15 @@ threads all run natively; Python only starts/stops the engine and reads its metr
 
 from __future__ import annotations
 
+import logging
 import os
 from typing import Dict, List, Optional, Sequence
 
 from gale._native import native
 from gale.config import GaleConfig
 from gale.models import get_model
+
+log = logging.getLogger("gale.engine")
 
 
 def device_cpus(device: int) -> set:
@@ -55,6 +58,13 @@ class Engine:
         H, W, C = self.net.input_shape
         d = cfg.engine_dict(H, W, C, self.net.classes)
         d["max_records"] = max_records
+        # base64 records (--input-format b64) are decoded in the replica's step from the host's
+        # pinned fetch buffers: the GPU ingest counts number tokens and base64 text does not
+        # nibble-pack, so neither is set up
+        b64 = cfg.input_format == "b64"
+        if b64 and not cfg.stub and (cfg.gpu_ingest or cfg.text_pack):
+            log.info("input_format=b64: GPU ingest and text packing are not used (records are "
+                     "decoded in the batch step)")
         self.model_replicas: list = []
         self.devices: List[int] = []
         if cfg.stub:
@@ -74,7 +84,7 @@ class Engine:
         # can take the images from there: the direct-launch step of a whole-network plan with
         # the prediction text in its epilogue (GpuReplica ptr_input_)
         d["ingest_parse"] = bool(
-            cfg.ingest_parse and cfg.gpu_ingest and cfg.use_graph and cfg.graph_step
+            not b64 and cfg.ingest_parse and cfg.gpu_ingest and cfg.use_graph and cfg.graph_step
             and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"
             and reps and all(getattr(r.executor, "step_out_ok", False) for r in reps))
         if (len(devs) > 1 or cfg.locality_split > 1) and cfg.numa_pin:
@@ -97,7 +107,7 @@ class Engine:
                                          cfg.step_launch == "direct")
             self.model_replicas.append(rep)
             self.devices.append(dev)
-        if cfg.gpu_ingest:
+        if cfg.gpu_ingest and not b64:
             # fetch buffers of each device's sources are mirrored on that device once and
             # parsed in place
             # one lane (stream + staging) per thread that runs the ingest: the decode workers,

@@ -220,6 +220,39 @@ def cast_bf16(x: torch.Tensor, scale: float = 1.0, shift: float = 0.0) -> torch.
     return y
 
 
+def b64_decode_instances(staged: torch.Tensor, table: torch.Tensor, shape, out: torch.Tensor,
+                         status: torch.Tensor, images: Optional[int] = None,
+                         d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Decode base64 uint8 image strings (input format ``b64``) into the fp32 NHWC batch tensor
+    ``out`` [slots, H, W, C], in place; returns ``out``.
+
+    ``staged``: uint8 bytes holding the strings, with 16 readable bytes past the last one.
+    ``table``: int32 [n, 4] descriptors, one per image: the int64 byte offset of the string's
+    first character (low word, high word), its slot in ``out`` and its record's index in
+    ``status`` (int32, zeroed by the caller; a record with a bad character gets 2). ``d_images``:
+    an int32 device word holding the image count (the launch is then sized for ``images``, or
+    the whole table). ``prep``: a ``gale.models.preprocess.InputPrep``."""
+    H, W, C = (int(v) for v in shape)
+    _check(staged, torch.uint8, "staged")
+    _check(table, torch.int32, "table")
+    _check(out, torch.float32, "out")
+    _check(status, torch.int32, "status")
+    if table.dim() != 2 or table.shape[1] != native().B64_IMAGE_BYTES // 4:
+        raise ValueError("gale op: table must be int32 [images, 4]")
+    n = table.shape[0] if images is None else int(images)
+    if n > table.shape[0]:
+        raise ValueError("gale op: more images than descriptors")
+    if out.numel() % (H * W * C) != 0:
+        raise ValueError("gale op: out must hold whole [H, W, C] images")
+    if d_images is not None:
+        _check(d_images, torch.int32, "d_images")
+    kw = prep.kernel_kwargs() if prep is not None else {}
+    native().b64_decode_instances(n, table.data_ptr(), staged.data_ptr(), H, W, C,
+                                  out.data_ptr(), status.data_ptr(), _stream(),
+                                  d_images.data_ptr() if d_images is not None else 0, **kw)
+    return out
+
+
 # ---- fp8 (OCP e4m3fn) path: tensors of e4m3 codes are uint8 --------------------------------
 
 
