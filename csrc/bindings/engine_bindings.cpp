@@ -88,6 +88,9 @@ EngineConfig config_from_dict(const py::dict& d) {
   if (input_format != "json" && input_format != "b64")
     throw std::invalid_argument("input_format: json or b64");
   c.input_b64 = input_format == "b64";
+  opt(d, "b64_ingest", c.b64_ingest);
+  if (c.b64_ingest && !c.input_b64)
+    throw std::invalid_argument("b64_ingest needs input_format b64");
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
   opt(d, "slo_p99_ms", c.slo_p99_ms);
@@ -136,9 +139,10 @@ void bind_engine(py::module_& m) {
            py::arg("high_priority") = false, py::arg("step_direct") = false)
       .def("enable_gpu_ingest",
            [](Engine& e, int device, int lanes, int poll_us) {
-             if (e.config().input_b64)
-               throw std::invalid_argument("enable_gpu_ingest: not with input_format b64 (the "
-                                           "ingest's counting pass is a number-token pass)");
+             if (e.config().input_b64 && !e.config().b64_ingest)
+               throw std::invalid_argument("enable_gpu_ingest: input_format b64 needs b64_ingest "
+                                           "(without it the records are decoded in the batch "
+                                           "step)");
              auto ing = std::make_shared<GpuIngest>(device, lanes, poll_us);
              ing->set_input_prep(e.config().prep);
              e.set_ingest(std::move(ing));

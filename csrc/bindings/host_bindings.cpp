@@ -18,6 +18,7 @@
 #include "../kafka/client.h"
 #include "../kafka/compress.h"
 #include "../kafka/fetch_framing.h"
+#include "../runtime/b64_ingest_plan.h"
 #include "../runtime/pack_tap.h"
 #include "../kafka/protocol.h"
 #include "../kafka/wire.h"
@@ -464,6 +465,49 @@ void bind_host(py::module_& m) {
       return py::none();
     return py::cast(offs);
   });
+  m.def("plan_b64_ingest",
+        [](std::vector<std::pair<int64_t, int64_t>> batches,
+           std::vector<std::tuple<int, int, int64_t, int64_t, int64_t>> recs,
+           std::vector<uint32_t> offs, int H, int W, int C, size_t arena_bytes,
+           size_t fetch_size, bool check_crcs) {
+          // batches: (offset, length); recs: (status, images, value_off, value_len, arr_off);
+          // offs: the OK records' string offsets (b64_image_offsets), concatenated
+          std::vector<B64PlanRecord> rs(recs.size());
+          for (size_t i = 0; i < recs.size(); ++i) {
+            rs[i].status = std::get<0>(recs[i]);
+            rs[i].images = std::get<1>(recs[i]);
+            rs[i].value_off = std::get<2>(recs[i]);
+            rs[i].value_len = std::get<3>(recs[i]);
+            rs[i].arr_off = std::get<4>(recs[i]);
+          }
+          B64IngestPlan p;
+          plan_b64_ingest(batches, kafka::kBatchAttrOffset, check_crcs, rs, offs, H, W, C,
+                          arena_bytes, fetch_size, p);
+          py::list windows, imgs;
+          for (const CrcChunk& c : p.chunks) windows.append(py::make_tuple(c.end, c.len));
+          for (const B64Image& d : p.imgs) imgs.append(py::make_tuple(d.off, d.slot, d.rec));
+          py::dict out;
+          out["windows"] = windows;
+          out["batch_windows"] = py::cast(p.batch_chunks);
+          out["images"] = imgs;
+          out["slot0"] = py::cast(p.slot0);
+          out["img0"] = py::cast(p.img0);
+          out["chunks_per_image"] = p.chunks_per_image;
+          out["lo"] = p.lo;
+          out["hi"] = p.hi;
+          out["o_chunks"] = p.o_chunks;
+          out["o_imgs"] = p.o_imgs;
+          out["plan_bytes"] = p.plan_bytes;
+          out["o_crc"] = p.o_crc;
+          out["o_bad"] = p.o_bad;
+          out["result_bytes"] = p.result_bytes;
+          return out;
+        },
+        py::arg("batches"), py::arg("recs"), py::arg("offs"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("arena_bytes"), py::arg("fetch_size"),
+        py::arg("check_crcs") = true,
+        "The host plan of a b64 fetch's device ingest (csrc/runtime/b64_ingest_plan.h)");
+  m.attr("BATCH_ATTR_OFFSET") = (int)kafka::kBatchAttrOffset;
   m.def("split_instances_b64", [](py::bytes arr, int H, int W, int C) -> py::object {
     const std::string_view s = view(arr);
     std::vector<std::pair<uint32_t, uint32_t>> spans;

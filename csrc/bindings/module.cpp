@@ -347,6 +347,36 @@ PYBIND11_MODULE(_C, m) {
         "groups: int32 (record, first tile) pairs, GROUP_TILES tiles each; counts: per record "
         "tile0 + grp0 -> [tile counts][group sums]; gsum: one int per group");
   m.attr("GROUP_TILES") = gale::kGroupTiles;
+  m.def("ingest_crc_b64",
+        [](uintptr_t bytes, uintptr_t chunks, int nchunks, uintptr_t tables, uintptr_t crc_out,
+           int images, uintptr_t imgs, int H, int W, int C, uintptr_t arena, uintptr_t wg_bad,
+           uintptr_t stream, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b, bool nchw) {
+          // imgs: B64_IMAGE_BYTES-byte descriptors; wg_bad: one int per decode workgroup
+          // (images * ceil(L / B64_CHUNK_CHARS)). a / b / nchw: as b64_decode_instances
+          gale::InputPrep prep;
+          const bool with_prep = a || b || nchw;
+          if ((a && a->size() != 4) || (b && b->size() != 4))
+            throw std::invalid_argument("ingest_crc_b64: a / b take four coefficients");
+          for (int i = 0; i < 4; ++i) {
+            if (a) prep.a[i] = (*a)[i];
+            if (b) prep.b[i] = (*b)[i];
+          }
+          prep.nchw = nchw ? 1 : 0;
+          chk(gale::ingest_crc_b64(static_cast<const uint8_t*>(P(bytes)),
+                                   static_cast<const gale::CrcChunk*>(P(chunks)), nchunks,
+                                   static_cast<const uint32_t*>(P(tables)),
+                                   static_cast<uint32_t*>(P(crc_out)), images,
+                                   static_cast<const gale::B64Image*>(P(imgs)), H, W, C,
+                                   static_cast<float*>(P(arena)), static_cast<int*>(P(wg_bad)),
+                                   S(stream), with_prep ? &prep : nullptr),
+              "ingest_crc_b64");
+        },
+        py::arg("bytes"), py::arg("chunks"), py::arg("nchunks"), py::arg("tables"),
+        py::arg("crc_out"), py::arg("images"), py::arg("imgs"), py::arg("H"), py::arg("W"),
+        py::arg("C"), py::arg("arena"), py::arg("wg_bad"), py::arg("stream"),
+        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
+  m.attr("B64_CHUNK_CHARS") = gale::kB64ChunkChars;
   m.def("text_unpack", [](uintptr_t packed, uintptr_t tab, int64_t n, uintptr_t out,
                           uintptr_t stream) {
     if (out % 16 || packed % 8) throw std::invalid_argument("text_unpack: misaligned buffers");

@@ -346,6 +346,23 @@ hipError_t ingest_crc_count(const uint8_t* bytes, const CrcChunk* chunks, int nc
                             int* gbad, hipStream_t stream, const uint8_t* packed = nullptr,
                             const uint32_t* tab = nullptr, uint8_t* text_out = nullptr);
 
+// The GPU ingest pass of one fetch buffer of base64 image records (input format "b64") in ONE
+// launch (b64_ingest.hip): workgroups [0, crc blocks) fold the CRC windows (crc32c_chunks), and
+// workgroup crc blocks + g decodes chunk g % cpi of image g / cpi, cpi = ceil(L /
+// kB64ChunkChars), from the device mirror `bytes` into arena + imgs[i].slot * H*W*C exactly as
+// b64_decode_instances does (same read bounds, verdict rules, store paths and prep forms).
+// wg_bad[g] = 2 when a lane of that workgroup saw a bad character or bad padding, else 0: every
+// decode workgroup stores its word (plain store; the host never zeroes the array) and a
+// record's verdict is the max over its images' words - B64Image::rec is not read. chunks, imgs,
+// crc_out and wg_bad may be host-mapped pinned memory; bytes, tables and arena are device
+// memory. nchunks == 0 or images == 0 leaves that half out; both zero launches nothing.
+// hipErrorInvalidValue: more workgroups than a 1-D grid holds, or prep with C > 4 and
+// non-uniform coefficients.
+hipError_t ingest_crc_b64(const uint8_t* bytes, const CrcChunk* chunks, int nchunks,
+                          const uint32_t* tables, uint32_t* crc_out, int images,
+                          const B64Image* imgs, int H, int W, int C, float* arena, int* wg_bad,
+                          hipStream_t stream, const InputPrep* prep = nullptr);
+
 // Expands a nibble-packed span (csrc/codec/text_pack.h: 64-byte blocks, per-2-KiB-group
 // {base offset, packed-block mask} pairs in tab) into out[0, n). out must be 16-byte aligned,
 // packed 8-byte aligned. packed and tab may be host-mapped pinned memory (the GPU ingest reads the

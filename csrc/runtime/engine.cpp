@@ -223,9 +223,9 @@ void Engine::add_replica(std::shared_ptr<Replica> r) {
 
 void Engine::set_ingest(std::shared_ptr<Ingest> ing) {
   if (running_) throw std::logic_error("engine: set_ingest after start");
-  if (cfg_.input_b64)
-    throw std::invalid_argument("engine: no GPU ingest with input_format b64 (its counting pass "
-                                "is a number-token pass)");
+  if (cfg_.input_b64 && !cfg_.b64_ingest)
+    throw std::invalid_argument("engine: GPU ingest with input_format b64 needs b64_ingest "
+                                "(without it the records are decoded in the batch step)");
   ingests_[ing->device()] = std::move(ing);
 }
 
@@ -335,9 +335,13 @@ void Engine::start() {
                                              budget);
     if (ingest_for((int)i)) {
       // the image arena behind each mirror (ingest_parse): one fp32 image per 2 * H * W * C
-      // bytes of fetch body, the most images a body of that size can hold
+      // bytes of fetch body, the most images a body of that size can hold. b64: an image takes
+      // at least L + 10 bytes of body, L = 4 * ceil(H*W*C / 3) (its string and {"b64":""}), so
+      // body / L + 2 slots always do: ~3x the body in fp32, against 2x for JSON text
       const size_t per = (size_t)cfg_.H * cfg_.W * cfg_.C;
-      const size_t arena = cfg_.ingest_parse && per ? (body / (2 * per) + 2) * per * 4 : 0;
+      const size_t b64_L = 4 * ((per + 2) / 3);
+      const size_t slots = !per ? 0 : cfg_.input_b64 ? body / b64_L + 2 : body / (2 * per) + 2;
+      const size_t arena = cfg_.ingest_parse ? slots * per * 4 : 0;
       pools_[i]->set_mirror_device(slot_dev_[i], arena);
     }
     pools_[i]->set_wait_ms(200);
@@ -927,6 +931,12 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   io.status.assign(n, codec::OK);
   io.arr_off.assign(n, 0);
   io.arr_len.assign(n, 0);
+  const bool b64 = cfg_.input_b64;
+  // (b64 text is never packed, so the host buffer is whole: the scan walks every element)
+  if (b64 && f.sparse) throw std::logic_error("engine: sparse fetch buffer in b64 mode");
+  if (b64) io.images.assign(n, 0);
+  std::vector<uint32_t> offs;
+  int64_t b64_accepted = 0;
   for (size_t i = 0; i < n; ++i) {
     const kafka::RecordRef& rr = f.records[i];
     if (rr.poison) {
@@ -935,6 +945,24 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
     }
     if (rr.value_len < 0) {
       io.status[i] = codec::BAD_ENVELOPE;  // null value (Jackson would throw)
+      continue;
+    }
+    if (b64) {
+      // image count and string offsets from the host scan (~20 bytes touched per image)
+      const uint8_t* v = f.buf.get() + rr.value_off;
+      codec::Scan s = codec::scan_instances_b64(v, (size_t)rr.value_len, cfg_.H, cfg_.W, cfg_.C);
+      if (s.status == codec::OK &&
+          (!codec::b64_image_offsets(v + s.arr_off, (size_t)s.arr_len, cfg_.H, cfg_.W, cfg_.C,
+                                     offs) ||
+           (int64_t)offs.size() != s.images))
+        s.status = codec::BAD_SHAPE;
+      io.status[i] = s.status;
+      io.arr_off[i] = s.arr_off;
+      io.arr_len[i] = s.arr_len;
+      if (s.status != codec::OK) continue;
+      io.images[i] = (int32_t)s.images;
+      io.b64_offs.insert(io.b64_offs.end(), offs.begin(), offs.end());
+      ++b64_accepted;
       continue;
     }
     // (a sparse host copy holds only the ends of each value: the scan stays inside them)
@@ -951,13 +979,18 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   float* arena =
       arena_bytes ? reinterpret_cast<float*>(dev + pool.mirror_extra_offset()) : nullptr;
   try {
-    ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked, cfg_.H,
-                cfg_.W, cfg_.C, io, arena, arena_bytes);
+    if (b64)
+      ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
+                      cfg_.H, cfg_.W, cfg_.C, io, arena, arena_bytes);
+    else
+      ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked, cfg_.H,
+                  cfg_.W, cfg_.C, io, arena, arena_bytes);
   } catch (const std::exception& e) {
     if (!ingest_failed_.exchange(true))
       fprintf(stderr, "[gale decode] GPU ingest failed (%s): host decode from now on\n", e.what());
     return false;
   }
+  b64_records_ += b64_accepted;  // (as the host path: records the scan accepted)
   std::vector<char> corrupt(n, 0);
   for (size_t b = 0; b < f.batches.size(); ++b)
     if (!io.batch_ok[b])

@@ -133,9 +133,12 @@ struct EngineConfig {
   InputPrep prep;
   // input format "b64": a record's instances array holds one {"b64": "<base64 of H*W*C uint8
   // values>"} object per image (csrc/codec/json_codec.h) instead of nested number arrays. The
-  // host scans with codec::scan_instances_b64 and the replicas decode the strings; no GPU ingest
-  // is attached in this mode (its counting pass is a number-token pass)
+  // host scans with codec::scan_instances_b64 and the replicas decode the strings; a GPU ingest
+  // is attached in this mode only with b64_ingest (run()'s counting pass is a number-token pass)
   bool input_b64 = false;
+  // input_b64 with a GPU ingest attached (Ingest::run_b64): batch CRCs on the device and, with
+  // ingest_parse, every string decoded into the fetch's image arena - the table step
+  bool b64_ingest = false;
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
   int max_wait_us = 2000;          // latency bound on batch formation

@@ -95,6 +95,134 @@ namespace {
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 }  // namespace
 
+// Joins the window CRCs of each batch and compares with the batch header's (io.batch_ok).
+void GpuIngest::join_batch_crcs(const kafka::Fetched& f,
+                                const std::vector<std::pair<size_t, size_t>>& batch_chunks,
+                                const uint32_t* crc, IngestIO& io) {
+  for (size_t b = 0; b < batch_chunks.size(); ++b) {
+    const kafka::BatchSpan& bs = f.batches[b];
+    uint32_t raw = 0;
+    for (size_t k = 0; k < batch_chunks[b].second; ++k) {
+      const uint32_t c = crc[batch_chunks[b].first + k];
+      raw = k == 0 ? c : shift_chunk_(raw) ^ c;
+    }
+    // standard CRC32C = raw ^ (initial ~0 carried over the message) ^ final ~0
+    const uint64_t len = bs.len - (size_t)kafka::kBatchAttrOffset;
+    const uint32_t got = raw ^ kafka::crc32c_shift(0xffffffffu, len) ^ 0xffffffffu;
+    kafka::Reader cr(f.buf.get() + bs.off + kafka::kBatchCrcOffset, 4);
+    io.batch_ok[b] = got == cr.u32();
+  }
+}
+
+// The ingest of a fetch of base64 image records: ONE DMA (text + plan) and ONE launch
+// (ingest_crc_b64). The host scan already knows every image count and string offset, so there
+// is no counting pass, no count block in the mirror and no second launch.
+void GpuIngest::run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap,
+                        bool check_crcs, int H, int W, int C, IngestIO& io, float* arena,
+                        size_t arena_bytes) {
+  Lane& L = *lanes_[(size_t)lane % lanes_.size()];
+  std::lock_guard<std::mutex> lk(L.mu);
+  const int64_t t_start = mono_ns();
+  const size_t nrec_all = f.records.size();
+  io.cnt_off.assign(nrec_all, -1);
+  io.batch_ok.assign(f.batches.size(), 1);
+  io.img.assign(nrec_all, nullptr);
+  std::vector<std::pair<int64_t, int64_t>> batches;
+  for (const kafka::BatchSpan& b : f.batches) batches.emplace_back((int64_t)b.off, (int64_t)b.len);
+  std::vector<B64PlanRecord> recs(nrec_all);
+  for (size_t i = 0; i < nrec_all; ++i) {
+    const kafka::RecordRef& rr = f.records[i];
+    B64PlanRecord& r = recs[i];
+    r.status = io.status[i];
+    r.images = io.images[i];
+    r.value_off = rr.value_off;
+    r.value_len = rr.value_len;
+    r.arr_off = io.arr_off[i];
+  }
+  B64IngestPlan plan;
+  plan_b64_ingest(batches, kafka::kBatchAttrOffset, check_crcs, recs, io.b64_offs, H, W, C,
+                  arena ? arena_bytes : 0, f.size, plan);
+  const size_t nc = plan.chunks.size(), ni = plan.imgs.size();
+  if (nc == 0 && plan.ok_records == 0) return;
+  // the span holding batches and records, raw (base64 text does not nibble-pack)
+  const size_t lo = plan.lo & ~(size_t)15;
+  const size_t span = plan.hi - lo;
+  check_hip(hipSetDevice(device_), "ingest: hipSetDevice");
+  grow(L, plan.plan_bytes + plan.result_bytes + 16, 1);
+  // the plan: behind the fetch's bytes in its own pinned chunk when it fits (the chunk is pinned
+  // and mirrored at the same offsets), so ONE DMA carries text and plan; else the lane's buffer
+  // and a second copy. There is no packed body in this mode, so the plan cannot land on a pack
+  // table behind the body (the overlap run()'s `used` guards against does not exist here).
+  const size_t plan_off = ((size_t)f.size + 255) & ~(size_t)255;
+  const bool plan_in_chunk = !plan_separate_ && plan_off + plan.plan_bytes <= dev_cap;
+  uint8_t* hpl = plan_in_chunk ? f.buf.get() + plan_off : L.h_io;
+  uint8_t* dpl = plan_in_chunk ? dev + plan_off : L.d_io;
+  if (nc) memcpy(hpl + plan.o_chunks, plan.chunks.data(), nc * sizeof(CrcChunk));
+  if (ni) memcpy(hpl + plan.o_imgs, plan.imgs.data(), ni * sizeof(B64Image));
+  // the results behind the lane's plan area, host-mapped: the kernel stores them over the link
+  uint8_t* res = L.h_io + plan.plan_bytes;
+  hipStream_t st = L.stream;
+  const int64_t t_plan = mono_ns();
+  const bool timed = dev_every_ > 0 && L.nrun++ % dev_every_ == 0;
+  if (timed) check_hip(hipEventRecord(L.tev[0], st), "ingest: timing event");
+  const bool has_plan = plan.plan_bytes > 0;
+  if (plan_in_chunk && has_plan) {
+    check_hip(hipMemcpyAsync(dev + lo, f.buf.get() + lo, plan_off + plan.plan_bytes - lo,
+                             hipMemcpyHostToDevice, st),
+              "ingest: H2D text + plan");
+  } else {
+    check_hip(hipMemcpyAsync(dev + lo, f.buf.get() + lo, span, hipMemcpyHostToDevice, st),
+              "ingest: H2D text");
+    if (has_plan)
+      check_hip(hipMemcpyAsync(L.d_io, L.h_io, plan.plan_bytes, hipMemcpyHostToDevice, st),
+                "ingest: H2D plan");
+  }
+  plan_in_chunk_ += plan_in_chunk && has_plan;
+  if (timed) check_hip(hipEventRecord(L.tev[1], st), "ingest: timing event");
+  text_bytes_ += (int64_t)span;
+  link_bytes_ += (int64_t)span;
+  int* wg_bad = reinterpret_cast<int*>(res + plan.o_bad);
+  check_hip(ingest_crc_b64(dev, reinterpret_cast<const CrcChunk*>(dpl + plan.o_chunks), (int)nc,
+                           d_tables_, reinterpret_cast<uint32_t*>(res + plan.o_crc), (int)ni,
+                           reinterpret_cast<const B64Image*>(dpl + plan.o_imgs), H, W, C, arena,
+                           wg_bad, st, &input_prep_),
+            "ingest: crc32c + b64 decode");
+  if (timed) {
+    check_hip(hipEventRecord(L.tev[2], st), "ingest: timing event");
+    check_hip(hipEventRecord(L.tev[3], st), "ingest: timing event");  // (no parse launch)
+  }
+  check_hip(hipEventRecord(L.done, st), "ingest: event");
+  const int64_t t_wait = mono_ns();
+  wait(L);
+  const int64_t t_post = mono_ns();
+  ++runs_;
+  prep_ns_ += t_wait - t_start;
+  plan_ns_ += t_plan - t_start;
+  wait_ns_ += t_post - t_wait;
+  if (timed) {
+    float ms[2] = {0.f, 0.f};
+    for (int k = 0; k < 2; ++k)
+      check_hip(hipEventElapsedTime(&ms[k], L.tev[k], L.tev[k + 1]), "ingest: event time");
+    ++dev_runs_;
+    dev_copy_ns_ += (int64_t)(ms[0] * 1e6);
+    dev_count_ns_ += (int64_t)(ms[1] * 1e6);
+    dev_wait_ns_ += t_post - t_wait;
+  }
+  // ---- host: batch CRCs; a record's verdict is the worst of its images' workgroup words
+  join_batch_crcs(f, plan.batch_chunks, reinterpret_cast<const uint32_t*>(res + plan.o_crc), io);
+  const int64_t per = (int64_t)H * W * C;
+  const int cpi = plan.chunks_per_image;
+  for (size_t i = 0; i < nrec_all; ++i) {
+    if (plan.img0[i] < 0) continue;
+    const int* w = wg_bad + (size_t)plan.img0[i] * cpi;
+    int v = 0;
+    for (int64_t g = 0; g < (int64_t)io.images[i] * cpi; ++g) v = std::max(v, w[g]);
+    if (v == 2) io.status[i] = codec::BAD_NUMBER;
+    else io.img[i] = arena + (int64_t)plan.slot0[i] * per;
+  }
+  post_ns_ += mono_ns() - t_post;
+}
+
 void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap,
                     bool check_crcs, int H, int W, int C, IngestIO& io, float* arena,
                     size_t arena_bytes) {
@@ -114,17 +242,10 @@ void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_
     lo = std::min(lo, b.off);
     hi = std::max(hi, b.off + b.len);
     if (!check_crcs) continue;
-    const int64_t rs = (int64_t)b.off + kafka::kBatchAttrOffset, re = (int64_t)(b.off + b.len);
-    const int64_t len = re - rs;
-    const int64_t n = (len + kCrcChunkBytes - 1) / kCrcChunkBytes;
-    batch_chunks.emplace_back(chunks.size(), (size_t)n);
-    for (int64_t k = 0; k < n; ++k) {
-      CrcChunk c;
-      c.end = re - (int64_t)kCrcChunkBytes * (n - 1 - k);
-      c.len = k == 0 ? (int32_t)(len - (int64_t)kCrcChunkBytes * (n - 1)) : kCrcChunkBytes;
-      c.pad_ = 0;
-      chunks.push_back(c);
-    }
+    const size_t first = chunks.size();
+    const size_t n = append_crc_windows((int64_t)b.off + kafka::kBatchAttrOffset,
+                                        (int64_t)(b.off + b.len), chunks);
+    batch_chunks.emplace_back(first, n);
   }
   std::vector<int> rec_of;  // JsonRecord j -> record index
   int ntiles = 0, ngroups = 0;
@@ -326,20 +447,7 @@ void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_
     dev_wait_ns_ += t_post - t_wait;
   }
   // ---- host: join the windows of each batch and compare; images from the element counts
-  const uint32_t* crc = reinterpret_cast<const uint32_t*>(L.h_io + o_crc);
-  for (size_t b = 0; b < batch_chunks.size(); ++b) {
-    const kafka::BatchSpan& bs = f.batches[b];
-    uint32_t raw = 0;
-    for (size_t k = 0; k < batch_chunks[b].second; ++k) {
-      const uint32_t c = crc[batch_chunks[b].first + k];
-      raw = k == 0 ? c : shift_chunk_(raw) ^ c;
-    }
-    // standard CRC32C = raw ^ (initial ~0 carried over the message) ^ final ~0
-    const uint64_t len = bs.len - (size_t)kafka::kBatchAttrOffset;
-    const uint32_t got = raw ^ kafka::crc32c_shift(0xffffffffu, len) ^ 0xffffffffu;
-    kafka::Reader cr(f.buf.get() + bs.off + kafka::kBatchCrcOffset, 4);
-    io.batch_ok[b] = got == cr.u32();
-  }
+  join_batch_crcs(f, batch_chunks, reinterpret_cast<const uint32_t*>(L.h_io + o_crc), io);
   // a record's tokens: the sums of its tile groups (and its verdict: the worst group's)
   const int* gsum = reinterpret_cast<const int*>(L.h_io + o_gsum);
   const int* gbad = reinterpret_cast<const int*>(L.h_io + o_gbad);

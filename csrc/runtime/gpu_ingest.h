@@ -6,9 +6,11 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "gale/kernels.h"
+#include "b64_ingest_plan.h"
 #include "ingest.h"
 
 namespace gale {
@@ -23,6 +25,9 @@ class GpuIngest : public Ingest {
   void run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap, bool check_crcs,
            int H, int W, int C, IngestIO& io, float* arena = nullptr,
            size_t arena_bytes = 0) override;
+  void run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap, bool check_crcs,
+               int H, int W, int C, IngestIO& io, float* arena = nullptr,
+               size_t arena_bytes = 0) override;
   void link_bytes(int64_t& text, int64_t& link) const override {
     text = text_bytes_.load();
     link = link_bytes_.load();
@@ -57,6 +62,8 @@ class GpuIngest : public Ingest {
     // the host writes the plan, ONE H2D copies it (up to the group sums) into d_io, and
     // ingest_crc_count stores the results (group sums and verdicts, window CRCs) straight into
     // the host buffer: no D2H copy
+    // run_b64: [CrcChunk x nc][B64Image x ni] (the plan, when it does not ride in the fetch's
+    // chunk) [crc u32 x nc][workgroup verdict i32 x ni * chunks per image]
     uint8_t* h_io = nullptr;
     uint8_t* d_io = nullptr;
     size_t io_cap = 0;
@@ -67,6 +74,9 @@ class GpuIngest : public Ingest {
   };
   void grow(Lane& L, size_t io_bytes, size_t tiles);
   void wait(Lane& L);
+  void join_batch_crcs(const kafka::Fetched& f,
+                       const std::vector<std::pair<size_t, size_t>>& batch_chunks,
+                       const uint32_t* crc, IngestIO& io);
   int device_, poll_us_;
   InputPrep input_prep_;
   std::atomic<int64_t> text_bytes_{0}, link_bytes_{0};

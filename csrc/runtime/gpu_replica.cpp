@@ -242,6 +242,11 @@ void GpuReplica::submit(Batch& b) {
   const size_t staged_dev = doff;
   size_t hoff = 0;
   int nrec = 0, img = 0, ntiles = 0, npre = 0;
+  // b64: descriptors written so far. The table is dense over the images decoded in this step:
+  // a batch can mix them with images the ingest already decoded (a split record's fragments
+  // next to preparsed records), which have no descriptor - the decode launch takes this count,
+  // not the batch's image count
+  int b64n = 0;
   bool count_pass = false;
   const int64_t per = (int64_t)H_ * W_ * C_;
   const float* in = static_cast<const float*>(exec_->input(slot));
@@ -283,7 +288,8 @@ void GpuReplica::submit(Batch& b) {
         throw std::logic_error("GpuReplica: b64 record does not match its scan");
       B64Image* tab = b64_table(s.h_recs);
       for (int k = 0; k < r.images; ++k)
-        tab[img + k] = B64Image{off + (int64_t)s.b64_offs[(size_t)k], img + k, nrec};
+        tab[b64n + k] = B64Image{off + (int64_t)s.b64_offs[(size_t)k], img + k, nrec};
+      b64n += r.images;
       b64_status(s.h_recs)[nrec] = 0;
       ++nrec;
       img += r.images;
@@ -349,6 +355,7 @@ void GpuReplica::submit(Batch& b) {
     s.h_hdr[0] = nrec;
     s.h_hdr[1] = ntiles;
     s.h_hdr[2] = img;
+    s.h_hdr[3] = b64n;
     hipGraphExec_t g = (gpu_encode_ && step_direct_) ? nullptr : step_for(s, slot, count_pass);
     if (gpu_encode_) {
       // the metadata this batch uses (header, its records, the input pointer table, its tile
@@ -356,7 +363,7 @@ void GpuReplica::submit(Batch& b) {
       const size_t rec_bytes = meta_rec_bytes();
       const size_t used = ntiles > 0 ? kMetaHdr + rec_bytes + sizeof(int) * (size_t)ntiles
                           : ptr_input_ ? kMetaHdr + rec_bytes
-                          : b64_       ? kMetaHdr + sizeof(B64Image) * (size_t)img
+                          : b64_       ? kMetaHdr + sizeof(B64Image) * (size_t)b64n
                                        : kMetaHdr + sizeof(JsonRecord) * (size_t)nrec;
       check_hip(hipMemcpyAsync(s.d_hdr, s.h_hdr, used, hipMemcpyHostToDevice, stream_),
                 "H2D step metadata");
@@ -378,7 +385,7 @@ void GpuReplica::submit(Batch& b) {
   check_hip(hipMemcpyAsync(s.d_recs, s.h_recs, meta, hipMemcpyHostToDevice, stream_),
             "H2D recs");
   if (b64_)
-    check_hip(launch_b64(s, slot, img, stream_, nullptr, nullptr), "b64_decode_instances");
+    check_hip(launch_b64(s, slot, b64n, stream_, nullptr, nullptr), "b64_decode_instances");
   else
     check_hip(json_parse_instances(nrec, ntiles, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                                    s.d_tiles,
@@ -472,7 +479,7 @@ hipError_t GpuReplica::enqueue_step(Slot& s, int slot, bool count_pass, hipStrea
   const int mb = exec_->max_batch();
   hipError_t c = hipSuccess;
   if (parse && b64_)
-    c = launch_b64(s, slot, mb, st, s.d_hdr + 2, s.d_status);
+    c = launch_b64(s, slot, mb, st, s.d_hdr + 3, s.d_status);
   else if (parse)  // (a batch of records the ingest already parsed: the forward alone)
     c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                              s.d_tiles, static_cast<float*>(exec_->input(slot)), st, count_pass,
@@ -518,7 +525,7 @@ hipGraphExec_t GpuReplica::step_for(Slot& s, int slot, bool count_pass) {
   } else if (e == hipSuccess) {
     hipError_t c = hipMemcpyAsync(s.d_hdr, s.h_hdr, meta, hipMemcpyHostToDevice, cs);
     if (c == hipSuccess && b64_)
-      c = launch_b64(s, slot, mb, cs, s.d_hdr + 2, nullptr);
+      c = launch_b64(s, slot, mb, cs, s.d_hdr + 3, nullptr);
     else if (c == hipSuccess)
       c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
                                s.d_tiles, static_cast<float*>(exec_->input(slot)), cs,

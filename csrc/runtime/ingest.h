@@ -31,6 +31,10 @@ struct IngestIO {
   // out (run() with an image arena): per record, its first image already parsed into the arena
   // as fp32 [H][W][C] (device pointer; its images follow contiguously), null: not parsed
   std::vector<const float*> img;
+  // in (run_b64): for every record with status OK, in order, `images` offsets of its strings'
+  // first characters relative to its instances array (codec::b64_image_offsets); `images` is
+  // then an input too - the host scan counted it
+  std::vector<uint32_t> b64_offs;
 };
 
 class Ingest {
@@ -47,6 +51,20 @@ class Ingest {
   virtual void run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap,
                    bool check_crcs, int H, int W, int C, IngestIO& io, float* arena = nullptr,
                    size_t arena_bytes = 0) = 0;
+  // The same for a fetch of base64 image records (input format "b64"): the host scan has set
+  // io.status / arr_off / arr_len / images / b64_offs; the device folds the batch CRCs and, with
+  // an arena, decodes every image's string into a dense arena slot (io.img; a record whose
+  // images do not fit, and every later one, stays without and is decoded by the replica from
+  // the resident mirror). A bad character raises the record's status. Default: nothing.
+  virtual void run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap,
+                       bool check_crcs, int H, int W, int C, IngestIO& io,
+                       float* arena = nullptr, size_t arena_bytes = 0) {
+    (void)lane, (void)f, (void)dev, (void)dev_cap, (void)check_crcs, (void)H, (void)W, (void)C;
+    (void)arena, (void)arena_bytes;
+    io.cnt_off.assign(f.records.size(), -1);
+    io.batch_ok.assign(f.batches.size(), 1);
+    io.img.assign(f.records.size(), nullptr);
+  }
   // fetched text bytes staged so far, and the bytes that crossed the host link for them (less
   // when the text is nibble-packed, csrc/codec/text_pack.h)
   virtual void link_bytes(int64_t& text, int64_t& link) const { text = link = 0; }

@@ -180,7 +180,8 @@ class GpuReplica : public Replica {
   void set_input_b64(bool on) { b64_ = on; }
 
  private:
-  static constexpr size_t kMetaHdr = 64;  // [nrec, ntiles, images, ...] ahead of the records
+  // [nrec, ntiles, images, b64 descriptors, ...] ahead of the records
+  static constexpr size_t kMetaHdr = 64;
   struct Slot {
     uint8_t* h_bytes = nullptr;  // pinned staging for records that arrived in pageable memory
     uint8_t* d_bytes = nullptr;  // device copy of the batch's JSON text

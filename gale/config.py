@@ -153,7 +153,12 @@ class GaleConfig:
     input_mean: str = ""
     input_std: str = ""
     input_layout: str = "nhwc"         # nchw: records nest [N][C][H][W]
-    input_format: str = "json"         # b64: base64 uint8 image records (no GPU ingest / packing)
+    input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
+                                       # ingest only with b64_ingest)
+    b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
+                                       # the device, strings decoded into the fetch's image
+                                       # arena, the table step); needs gpu_ingest, no effect
+                                       # with stub replicas
     max_batch: int = 256
     max_wait_us: int = 2000
     slo_p99_ms: float = 0.0            # latency-SLO mode (config 5): adapt batch/wait to a p99
@@ -241,6 +246,8 @@ class GaleConfig:
             raise ValueError("topology name is required")
         if not self.fold_bn and self.dtype == "fp8":
             raise ValueError("--no-fold-bn (standalone BatchNorm plan) is bf16 / fp32 only")
+        if self.b64_ingest and self.input_format != "b64":
+            raise ValueError("--b64-ingest needs --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
         return self
 
@@ -303,7 +310,7 @@ class GaleConfig:
             queue_depth=self.queue_depth,
             watchdog_ms=self.watchdog_ms, max_restarts=self.max_restarts,
             restart_backoff_ms=self.restart_backoff_ms, fault=self.fault, seed=self.seed,
-            trace=self.trace, input_format=self.input_format,
+            trace=self.trace, input_format=self.input_format, b64_ingest=self.b64_ingest,
             **self.input_prep(C).engine_entries())
 
 

@@ -59,12 +59,17 @@ class Engine:
         d = cfg.engine_dict(H, W, C, self.net.classes)
         d["max_records"] = max_records
         # base64 records (--input-format b64) are decoded in the replica's step from the host's
-        # pinned fetch buffers: the GPU ingest counts number tokens and base64 text does not
-        # nibble-pack, so neither is set up
+        # pinned fetch buffers unless --b64-ingest attaches the GPU ingest's b64 form (batch CRCs
+        # on the device, strings decoded into the fetch's image arena); base64 text does not
+        # nibble-pack either way
         b64 = cfg.input_format == "b64"
-        if b64 and not cfg.stub and (cfg.gpu_ingest or cfg.text_pack):
+        ingest = cfg.gpu_ingest and (not b64 or cfg.b64_ingest)
+        if b64 and not cfg.b64_ingest and not cfg.stub and (cfg.gpu_ingest or cfg.text_pack):
             log.info("input_format=b64: GPU ingest and text packing are not used (records are "
                      "decoded in the batch step)")
+        if cfg.b64_ingest and (cfg.stub or not cfg.gpu_ingest):
+            log.info("b64_ingest has no effect %s", "with stub replicas" if cfg.stub
+                     else "without gpu_ingest")
         self.model_replicas: list = []
         self.devices: List[int] = []
         if cfg.stub:
@@ -84,8 +89,8 @@ class Engine:
         # can take the images from there: the direct-launch step of a whole-network plan with
         # the prediction text in its epilogue (GpuReplica ptr_input_)
         d["ingest_parse"] = bool(
-            not b64 and cfg.ingest_parse and cfg.gpu_ingest and cfg.use_graph and cfg.graph_step
-            and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"
+            (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
+            and cfg.use_graph and cfg.graph_step and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"
             and reps and all(getattr(r.executor, "step_out_ok", False) for r in reps))
         if (len(devs) > 1 or cfg.locality_split > 1) and cfg.numa_pin:
             # single-process multi-GPU: each GPU's replica workers and sources run on the CPUs
@@ -107,7 +112,7 @@ class Engine:
                                          cfg.step_launch == "direct")
             self.model_replicas.append(rep)
             self.devices.append(dev)
-        if cfg.gpu_ingest and not b64:
+        if ingest:
             # fetch buffers of each device's sources are mirrored on that device once and
             # parsed in place
             # one lane (stream + staging) per thread that runs the ingest: the decode workers,

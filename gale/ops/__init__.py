@@ -253,6 +253,54 @@ def b64_decode_instances(staged: torch.Tensor, table: torch.Tensor, shape, out: 
     return out
 
 
+def ingest_crc_b64(staged: torch.Tensor, shape, arena: Optional[torch.Tensor] = None,
+                   table: Optional[torch.Tensor] = None, wg_bad: Optional[torch.Tensor] = None,
+                   windows: Optional[torch.Tensor] = None, tables: Optional[torch.Tensor] = None,
+                   crc_out: Optional[torch.Tensor] = None, prep=None) -> None:
+    """The device ingest of a fetch of base64 image records in ONE launch: the raw CRC32C of
+    ``windows`` into ``crc_out`` and every string of ``table`` decoded into ``arena``.
+
+    ``staged``: uint8 bytes (the fetch's device mirror), with 16 readable bytes past the last
+    string. ``table``: int32 [n, 4] descriptors as for ``b64_decode_instances`` (the record index
+    is not read); ``arena``: fp32, whole [H, W, C] slots; ``wg_bad``: int32, one word per decode
+    workgroup (n * ceil(L / B64_CHUNK_CHARS)), every one of them written: 2 = a bad character
+    or bad padding in that chunk, else 0. ``windows``: int32 [m, 4] CRC windows (int64 end, int32
+    length, pad), ``tables``: the device CRC tables, ``crc_out``: uint32-as-int32 [m]. Either
+    half may be left out."""
+    H, W, C = (int(v) for v in shape)
+    _check(staged, torch.uint8, "staged")
+    n = m = 0
+    if table is not None:
+        _check(table, torch.int32, "table")
+        _check(arena, torch.float32, "arena")
+        _check(wg_bad, torch.int32, "wg_bad")
+        if table.dim() != 2 or table.shape[1] != native().B64_IMAGE_BYTES // 4:
+            raise ValueError("gale op: table must be int32 [images, 4]")
+        n = table.shape[0]
+        per = H * W * C
+        if arena.numel() % per != 0:
+            raise ValueError("gale op: arena must hold whole [H, W, C] images")
+        chars = 4 * ((per + 2) // 3)
+        cpi = -(-chars // native().B64_CHUNK_CHARS)
+        if wg_bad.numel() < n * cpi:
+            raise ValueError("gale op: wg_bad needs one word per decode workgroup")
+    if windows is not None:
+        _check(windows, torch.int32, "windows")
+        _check(tables, torch.int32, "tables")
+        _check(crc_out, torch.int32, "crc_out")
+        if windows.dim() != 2 or windows.shape[1] != 4:
+            raise ValueError("gale op: windows must be int32 [windows, 4]")
+        m = windows.shape[0]
+        if crc_out.numel() < m:
+            raise ValueError("gale op: crc_out shorter than the windows")
+    kw = prep.kernel_kwargs() if prep is not None else {}
+    native().ingest_crc_b64(staged.data_ptr(), windows.data_ptr() if m else 0, m,
+                            tables.data_ptr() if m else 0, crc_out.data_ptr() if m else 0, n,
+                            table.data_ptr() if n else 0, H, W, C,
+                            arena.data_ptr() if n else 0, wg_bad.data_ptr() if n else 0,
+                            _stream(), **kw)
+
+
 # ---- fp8 (OCP e4m3fn) path: tensors of e4m3 codes are uint8 --------------------------------
 
 

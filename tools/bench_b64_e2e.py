@@ -1,6 +1,7 @@
-"""End-to-end throughput of the three input encodings through one engine on one GPU.
+"""End-to-end throughput of the input encodings through one engine on one GPU.
 
-Per format - ``b64`` (--input-format b64), ``byte-text`` (integer-pixel JSON through the default
+Per format - ``b64`` (--input-format b64, decoded in the batch step), ``b64-ingest`` (the same
+records with --b64-ingest: batch CRCs and the decode in the GPU ingest), ``byte-text`` (integer-pixel JSON through the default
 GPU ingest) and ``float-text`` (Java Float.toString JSON through the default GPU ingest, what
 bench.py streams) - an embedded broker is preloaded with N one-image records (a set of distinct
 records appended by reference) and one engine serves them to ``max_records``. The rate is
@@ -35,7 +36,7 @@ CIFAR = dict(input_mean="0.4914,0.4822,0.4465", input_std="0.2470,0.2435,0.2616"
 
 
 def records_for(fmt, pixels):
-    if fmt == "b64":
+    if fmt in ("b64", "b64-ingest"):
         return encode_records_b64(pixels, 1)
     if fmt == "byte-text":
         return encode_records_text(pixels, 1)
@@ -72,7 +73,8 @@ def run(fmt, a, pixels, rnd):
                          model=a.model, max_batch=a.batch, max_wait_us=2000,
                          queue_depth=4 * a.batch, source_parallelism=a.partitions,
                          sink_parallelism=2, replicas=a.replicas, decode_threads=a.decode_threads,
-                         input_format="b64" if fmt == "b64" else "json", stub=a.stub,
+                         input_format="b64" if fmt in ("b64", "b64-ingest") else "json",
+                         b64_ingest=fmt == "b64-ingest", stub=a.stub,
                          **prep).validate()
         eng = Engine(cfg, devices=None if a.stub else [0], max_records=total)
         eng.start()
@@ -92,7 +94,9 @@ def run(fmt, a, pixels, rnd):
                 img_s=round((c1 - c0) / ((t1 - t0) * 1e-9)),
                 bytes_per_image=round(sum(len(r) for r in recs) / len(recs), 1),
                 errors=int(st["errors"]), b64_records=int(st["b64_records"]),
-                ingested_records=int(st["ingested_records"]), batch=a.batch,
+                ingested_records=int(st["ingested_records"]),
+                ingest_parsed_records=int(st.get("ingest_parsed_records", 0)),
+                table_batches=int(st.get("table_batches", 0)), batch=a.batch,
                 partitions=a.partitions, replicas=a.replicas, decode_threads=a.decode_threads)
 
 
@@ -104,7 +108,7 @@ def main():
     ap.add_argument("--distinct", type=int, default=1024)
     ap.add_argument("--records-per-batch", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--formats", default="b64,byte-text,float-text")
+    ap.add_argument("--formats", default="b64,b64-ingest,byte-text,float-text")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--partitions", type=int, default=11)
     ap.add_argument("--replicas", type=int, default=6)

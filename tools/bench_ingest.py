@@ -4,6 +4,11 @@ records, for CIFAR (32x32x3, ~35 KB per image) and ImageNet (224x224x3, ~1.7 MB)
 
 usage: python tools/bench_ingest.py [--iters 50]
 Prints one JSON line per (shape, kernel): us per launch and GB/s of JSON text.
+
+--encoding b64: the base64 ingest (ingest_crc_b64) over a fetch of one-image records, CRC windows
+over the whole body included, against the same work as two launches on the same buffer
+(crc32c_chunks + b64_decode_instances), alternating --rounds times in one process. One JSON line
+per (case, round, contender); --out appends them to a file.
 """
 
 import argparse
@@ -68,10 +73,82 @@ def timed(fn, iters):
     return a.elapsed_time(b) * 1e3 / iters
 
 
+IMG = np.dtype([("off", "<i8"), ("slot", "<i4"), ("rec", "<i4")])
+WIN = np.dtype([("end", "<i8"), ("len", "<i4"), ("pad", "<i4")])
+
+
+def main_b64(a):
+    from gale import ops
+    from gale.data import encode_records_b64, synthetic_pixels
+    from gale.models.preprocess import InputPrep
+
+    s = torch.cuda.current_stream().cuda_stream
+    tables = torch.tensor(np.array(K.crc32c_device_tables(), dtype=np.uint32).view(np.int32),
+                          device="cuda")
+    prep = InputPrep.build(3, 1 / 255, "0.4914,0.4822,0.4465", "0.2470,0.2435,0.2616")
+    for name, shape, nimg in (("cifar_1024", (32, 32, 3), 1024),
+                              ("imagenet_64", (224, 224, 3), 64)):
+        H, W, Cc = shape
+        recs = encode_records_b64(synthetic_pixels(nimg, shape, 0), 1)
+        buf = bytearray()
+        offs = []
+        for r in recs:  # record values back to back behind a few framing bytes, as in a fetch
+            buf += bytes(7)
+            st, arr_off, arr_len, n = C.scan_instances_b64(r, H, W, Cc)
+            assert st == 0 and n == 1
+            offs.append(len(buf) + arr_off + C.b64_image_offsets(r[arr_off:arr_off + arr_len],
+                                                                 H, W, Cc)[0])
+            buf += r
+        n = len(buf)
+        nw = -(-n // 4096)
+        ch = np.zeros(nw, dtype=WIN)
+        for k in range(nw):
+            ch[k] = (n - 4096 * (nw - 1 - k), n - 4096 * (nw - 1) if k == 0 else 4096, 0)
+        tab = np.zeros(nimg, dtype=IMG)
+        tab["off"], tab["slot"], tab["rec"] = offs, np.arange(nimg), np.arange(nimg)
+        d = torch.frombuffer(bytearray(bytes(buf) + bytes(64)), dtype=torch.uint8).cuda()
+        dch = torch.from_numpy(ch.view(np.int32).reshape(-1, 4).copy()).cuda()
+        dtab = torch.from_numpy(tab.view(np.int32).reshape(-1, 4).copy()).cuda()
+        cpi = -(-(4 * ((H * W * Cc + 2) // 3)) // C.B64_CHUNK_CHARS)
+        crc = [torch.zeros(nw, dtype=torch.int32, device="cuda") for _ in range(2)]
+        out = [torch.empty((nimg, H, W, Cc), device="cuda") for _ in range(2)]
+        bad = torch.full((nimg * cpi,), 7, dtype=torch.int32, device="cuda")
+        status = torch.zeros(nimg, dtype=torch.int32, device="cuda")
+
+        def fused():
+            ops.ingest_crc_b64(d, shape, arena=out[0], table=dtab, wg_bad=bad, windows=dch,
+                               tables=tables, crc_out=crc[0], prep=prep)
+
+        def pair():
+            C.crc32c_chunks(d.data_ptr(), dch.data_ptr(), nw, tables.data_ptr(),
+                            crc[1].data_ptr(), s)
+            ops.b64_decode_instances(d, dtab, shape, out[1], status, prep=prep)
+
+        for rnd in range(a.rounds):
+            for kname, fn in (("fused", fused), ("crc;decode", pair)):
+                us = timed(fn, a.iters)
+                line = json.dumps(dict(tool="bench_ingest", encoding="b64", case=name, round=rnd,
+                                       kernel=kname, images=nimg, windows=nw,
+                                       text_mb=round(n / 1e6, 2), us=round(us, 1),
+                                       gb_s=round(n / us / 1e3, 1)))
+                print(line, flush=True)
+                if a.out:
+                    with open(a.out, "a") as f:
+                        f.write(line + "\n")
+        # both forms computed the same thing
+        assert torch.equal(crc[0], crc[1]) and torch.equal(out[0], out[1])
+        assert (bad == 0).all() and (status == 0).all()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--encoding", default="json", choices=("json", "b64"))
+    ap.add_argument("--rounds", type=int, default=5, help="--encoding b64: alternating rounds")
+    ap.add_argument("--out", default="", help="--encoding b64: append the JSON lines to a file")
     a = ap.parse_args()
+    if a.encoding == "b64":
+        return main_b64(a)
     s = torch.cuda.current_stream().cuda_stream
     tables = torch.tensor(np.array(K.crc32c_device_tables(), dtype=np.uint32).view(np.int32),
                           device="cuda")
