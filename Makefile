@@ -76,13 +76,24 @@ build/asan/b64_scan_check: csrc/tests/b64_scan_check.cpp csrc/codec/json_codec.c
 
 # the b64 ingest's host plan behind the scanner, on mutated records and mutated scan results
 # (csrc/tests/b64_plan_check.cpp): codec + plan, no engine, no HIP call
-build/asan/b64_plan_check: csrc/tests/b64_plan_check.cpp csrc/runtime/b64_ingest_plan.cpp \
+build/asan/b64_plan_check: csrc/tests/b64_plan_check.cpp csrc/runtime/ingest_plan.cpp \
                            csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp $(HDRS)
 	@mkdir -p $(dir $@)
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Icsrc/include \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    csrc/tests/b64_plan_check.cpp csrc/runtime/b64_ingest_plan.cpp \
+	    csrc/tests/b64_plan_check.cpp csrc/runtime/ingest_plan.cpp \
+	    csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# the JSON ingest's host plan (layout + fill) behind the envelope scanner, on mutated records and
+# mutated scan results (csrc/tests/json_plan_check.cpp): codec + plan, no engine, no HIP call
+build/asan/json_plan_check: csrc/tests/json_plan_check.cpp csrc/runtime/ingest_plan.cpp \
+                            csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Icsrc/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/json_plan_check.cpp csrc/runtime/ingest_plan.cpp \
 	    csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
 tsan: build/tsan/engine_stress

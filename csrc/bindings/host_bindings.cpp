@@ -18,7 +18,7 @@
 #include "../kafka/client.h"
 #include "../kafka/compress.h"
 #include "../kafka/fetch_framing.h"
-#include "../runtime/b64_ingest_plan.h"
+#include "../runtime/ingest_plan.h"
 #include "../runtime/pack_tap.h"
 #include "../kafka/protocol.h"
 #include "../kafka/wire.h"
@@ -506,7 +506,72 @@ void bind_host(py::module_& m) {
         py::arg("batches"), py::arg("recs"), py::arg("offs"), py::arg("H"), py::arg("W"),
         py::arg("C"), py::arg("arena_bytes"), py::arg("fetch_size"),
         py::arg("check_crcs") = true,
-        "The host plan of a b64 fetch's device ingest (csrc/runtime/b64_ingest_plan.h)");
+        "The host plan of a b64 fetch's device ingest (csrc/runtime/ingest_plan.h)");
+  m.def("plan_json_ingest",
+        [](std::vector<std::pair<int64_t, int64_t>> batches,
+           std::vector<std::tuple<int, int64_t, int64_t, int64_t, int64_t>> recs, int H, int W,
+           int C, size_t arena_bytes, size_t fetch_size, size_t dev_cap, int64_t tap_result,
+           bool plan_separate, bool check_crcs) {
+          // batches: (offset, length); recs: (status, value_off, value_len, arr_off, arr_len)
+          std::vector<JsonPlanRecord> rs(recs.size());
+          for (size_t i = 0; i < recs.size(); ++i) {
+            rs[i].status = std::get<0>(recs[i]);
+            rs[i].value_off = std::get<1>(recs[i]);
+            rs[i].value_len = std::get<2>(recs[i]);
+            rs[i].arr_off = std::get<3>(recs[i]);
+            rs[i].arr_len = std::get<4>(recs[i]);
+          }
+          JsonIngestPlan p;
+          plan_json_ingest(batches, kafka::kBatchAttrOffset, check_crcs, rs, H, W, C, arena_bytes,
+                           fetch_size, dev_cap, tap_result, plan_separate, p);
+          // the plan sections as fill writes them (the pack table and the padding stay zero)
+          std::string plan(p.o_gsum, '\0');
+          if (!p.empty()) fill_json_ingest(p, rs, reinterpret_cast<uint8_t*>(&plan[0]));
+          py::list windows;
+          for (const CrcChunk& c : p.chunks) windows.append(py::make_tuple(c.end, c.len));
+          py::dict out;
+          out["windows"] = windows;
+          out["batch_windows"] = py::cast(p.batch_chunks);
+          out["rec_of"] = py::cast(p.rec_of);
+          out["pjs"] = py::cast(p.pjs);
+          out["nc"] = p.nc();
+          out["nr"] = p.nr();
+          out["np"] = p.np();
+          out["ntiles"] = p.ntiles;
+          out["ngroups"] = p.ngroups;
+          out["ptiles"] = p.ptiles;
+          out["ng"] = p.ng;
+          out["packed"] = p.packed;
+          out["lo"] = p.lo;
+          out["span"] = p.span;
+          out["link"] = p.link;
+          out["c_lo"] = p.c_lo;
+          out["c_len"] = p.c_len;
+          out["tab_off"] = p.tab_off;
+          out["used"] = p.used;
+          out["cnt_base"] = p.cnt_base;
+          out["o_chunks"] = p.o_chunks;
+          out["o_groups"] = p.o_groups;
+          out["o_recs"] = p.o_recs;
+          out["o_precs"] = p.o_precs;
+          out["o_ptr"] = p.o_ptr;
+          out["o_gsum"] = p.o_gsum;
+          out["prefix"] = p.o_gsum;  // what the DMA carries
+          out["o_crc"] = p.o_crc;
+          out["o_gbad"] = p.o_gbad;
+          out["o_pbad"] = p.o_pbad;
+          out["io_bytes"] = p.io_bytes;
+          out["plan_off"] = p.plan_off;
+          out["plan_in_chunk"] = p.plan_in_chunk;
+          out["plan"] = py::bytes(plan);
+          return out;
+        },
+        py::arg("batches"), py::arg("recs"), py::arg("H"), py::arg("W"), py::arg("C"),
+        py::arg("arena_bytes"), py::arg("fetch_size"), py::arg("dev_cap"),
+        py::arg("tap_result") = (int64_t)-1, py::arg("plan_separate") = false,
+        py::arg("check_crcs") = true,
+        "The host plan of a JSON fetch's device ingest, laid out and filled "
+        "(csrc/runtime/ingest_plan.h)");
   m.attr("BATCH_ATTR_OFFSET") = (int)kafka::kBatchAttrOffset;
   m.def("split_instances_b64", [](py::bytes arr, int H, int W, int C) -> py::object {
     const std::string_view s = view(arr);

@@ -243,7 +243,12 @@ struct JsonRecord {
   int64_t grp0;
 };
 static_assert(sizeof(JsonRecord) == 48, "JsonRecord layout (host <-> device tables)");
-int json_tile_count(int64_t off, int32_t len);
+// tiles of the record text [off, off + len): counted from its 16-byte-aligned start
+inline int json_tile_count(int64_t off, int32_t len) {
+  if (len <= 0) return 0;
+  const int64_t abeg = off & ~(int64_t)15;
+  return (int)((off + len - abeg + kJsonTileBytes - 1) / kJsonTileBytes);
+}
 // Input preprocessing applied at the parse's store: the model input for the record value x at
 // channel c is fmaf(x, a[c], b[c]) (binary32, one rounding; a = scale / std, b = -mean / std,
 // gale/models/preprocess.py). The coefficients travel by value in the kernel arguments (C <= 4

@@ -1007,12 +1007,6 @@ void json_parse_prep_kernel(JsonRecord* recs, const int* tile_rec, int ntiles,
 
 
 
-int json_tile_count(int64_t off, int32_t len) {
-  if (len <= 0) return 0;
-  const int64_t abeg = off & ~(int64_t)15;
-  return (int)((off + len - abeg + kJsonTileBytes - 1) / kJsonTileBytes);
-}
-
 hipError_t ingest_crc_count(const uint8_t* bytes, const CrcChunk* chunks, int nchunks,
                             const uint32_t* tables, uint32_t* crc_out, int nrec, int ngroups,
                             JsonRecord* recs, const int2* groups, int* counts, int* gsum,

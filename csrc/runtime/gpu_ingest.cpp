@@ -10,8 +10,8 @@
 #include <thread>
 
 #include "../codec/json_codec.h"
-#include "../codec/text_pack.h"
 #include "gale/executor.h"
+#include "replica.h"
 
 namespace gale {
 
@@ -55,7 +55,10 @@ GpuIngest::~GpuIngest() {
   if (d_tables_) hipFree(d_tables_);
 }
 
+// Before a run's first write into the lane's buffers: the device of the calling thread, and
+// room for the plan + results and for the scratch counts.
 void GpuIngest::grow(Lane& L, size_t io_bytes, size_t tiles) {
+  check_hip(hipSetDevice(device_), "ingest: hipSetDevice");
   auto up = [](size_t want, size_t have) {
     return (std::max(want, have * 2) + 4095) & ~(size_t)4095;
   };
@@ -91,9 +94,61 @@ void GpuIngest::wait(Lane& L) {
   }
 }
 
-namespace {
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-}  // namespace
+void GpuIngest::mark(Lane& L, const Stamps& ts, int k) {
+  if (ts.timed) check_hip(hipEventRecord(L.tev[k], L.stream), "ingest: timing event");
+}
+
+// The copies of a run: the text (with the plan behind it, in ONE DMA, when the plan rides in the
+// fetch's chunk), else the text and then the plan from the lane's buffer. A run without plan
+// sections copies the text alone.
+void GpuIngest::begin(Lane& L, Stamps& ts, const kafka::Fetched& f, uint8_t* dev,
+                      const Transfer& t) {
+  hipStream_t st = L.stream;
+  ts.plan = mono_ns();  // plan built; the HIP calls follow
+  ts.timed = dev_every_ > 0 && L.nrun++ % dev_every_ == 0;
+  mark(L, ts, 0);
+  if (t.tab_bytes) memcpy(t.hpl, t.tab, t.tab_bytes);
+  const bool has_plan = t.plan_bytes > 0;
+  if (t.in_chunk && has_plan) {
+    check_hip(hipMemcpyAsync(dev + t.lo, f.buf.get() + t.lo, t.plan_off + t.plan_bytes - t.lo,
+                             hipMemcpyHostToDevice, st),
+              "ingest: H2D text + plan");
+  } else {
+    check_hip(hipMemcpyAsync(dev + t.lo, f.buf.get() + t.lo, t.len, hipMemcpyHostToDevice, st),
+              "ingest: H2D text");
+    if (has_plan)
+      check_hip(hipMemcpyAsync(L.d_io, L.h_io, t.plan_bytes, hipMemcpyHostToDevice, st),
+                "ingest: H2D plan");
+  }
+  plan_in_chunk_ += t.in_chunk && has_plan;
+  mark(L, ts, 1);
+  text_bytes_ += (int64_t)t.text_bytes;
+  link_bytes_ += (int64_t)t.link_bytes;
+}
+
+// Returns the time the device was done (the host's verdict work is timed from it).
+int64_t GpuIngest::end(Lane& L, const Stamps& ts, bool parsed) {
+  mark(L, ts, 3);
+  check_hip(hipEventRecord(L.done, L.stream), "ingest: event");
+  const int64_t t_wait = mono_ns();
+  wait(L);
+  const int64_t t_post = mono_ns();
+  ++runs_;
+  prep_ns_ += t_wait - ts.start;
+  plan_ns_ += ts.plan - ts.start;
+  wait_ns_ += t_post - t_wait;
+  if (ts.timed) {
+    float ms[3] = {0.f, 0.f, 0.f};  // copies, count (or b64) launch, parse launch
+    for (int k = 0; k < (parsed ? 3 : 2); ++k)
+      check_hip(hipEventElapsedTime(&ms[k], L.tev[k], L.tev[k + 1]), "ingest: event time");
+    ++dev_runs_;
+    dev_copy_ns_ += (int64_t)(ms[0] * 1e6);
+    dev_count_ns_ += (int64_t)(ms[1] * 1e6);
+    dev_parse_ns_ += (int64_t)(ms[2] * 1e6);
+    dev_wait_ns_ += t_post - t_wait;
+  }
+  return t_post;
+}
 
 // Joins the window CRCs of each batch and compares with the batch header's (io.batch_ok).
 void GpuIngest::join_batch_crcs(const kafka::Fetched& f,
@@ -122,11 +177,13 @@ void GpuIngest::run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t 
                         size_t arena_bytes) {
   Lane& L = *lanes_[(size_t)lane % lanes_.size()];
   std::lock_guard<std::mutex> lk(L.mu);
-  const int64_t t_start = mono_ns();
+  Stamps ts;
+  ts.start = mono_ns();
   const size_t nrec_all = f.records.size();
   io.cnt_off.assign(nrec_all, -1);
   io.batch_ok.assign(f.batches.size(), 1);
   io.img.assign(nrec_all, nullptr);
+  // ---- plan
   std::vector<std::pair<int64_t, int64_t>> batches;
   for (const kafka::BatchSpan& b : f.batches) batches.emplace_back((int64_t)b.off, (int64_t)b.len);
   std::vector<B64PlanRecord> recs(nrec_all);
@@ -144,70 +201,35 @@ void GpuIngest::run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t 
                   arena ? arena_bytes : 0, f.size, plan);
   const size_t nc = plan.chunks.size(), ni = plan.imgs.size();
   if (nc == 0 && plan.ok_records == 0) return;
-  // the span holding batches and records, raw (base64 text does not nibble-pack)
-  const size_t lo = plan.lo & ~(size_t)15;
-  const size_t span = plan.hi - lo;
-  check_hip(hipSetDevice(device_), "ingest: hipSetDevice");
   grow(L, plan.plan_bytes + plan.result_bytes + 16, 1);
-  // the plan: behind the fetch's bytes in its own pinned chunk when it fits (the chunk is pinned
-  // and mirrored at the same offsets), so ONE DMA carries text and plan; else the lane's buffer
-  // and a second copy. There is no packed body in this mode, so the plan cannot land on a pack
-  // table behind the body (the overlap run()'s `used` guards against does not exist here).
-  const size_t plan_off = ((size_t)f.size + 255) & ~(size_t)255;
-  const bool plan_in_chunk = !plan_separate_ && plan_off + plan.plan_bytes <= dev_cap;
-  uint8_t* hpl = plan_in_chunk ? f.buf.get() + plan_off : L.h_io;
-  uint8_t* dpl = plan_in_chunk ? dev + plan_off : L.d_io;
-  if (nc) memcpy(hpl + plan.o_chunks, plan.chunks.data(), nc * sizeof(CrcChunk));
-  if (ni) memcpy(hpl + plan.o_imgs, plan.imgs.data(), ni * sizeof(B64Image));
+  // ---- fill. The plan: behind the fetch's bytes in its own pinned chunk when it fits (the chunk
+  // is pinned and mirrored at the same offsets), so ONE DMA carries text and plan; else the
+  // lane's buffer and a second copy. There is no packed body in this mode, so the plan cannot
+  // land on a pack table behind the body (the overlap the JSON plan's `used` guards against does
+  // not exist here). The span holding batches and records crosses raw (base64 text does not
+  // nibble-pack).
+  Transfer t;
+  t.lo = plan.c_lo;
+  t.len = t.text_bytes = t.link_bytes = plan.c_len;
+  t.plan_off = plan.plan_off;
+  t.plan_bytes = plan.plan_bytes;
+  t.in_chunk = !plan_separate_ && t.plan_off + plan.plan_bytes <= dev_cap;
+  t.hpl = t.in_chunk ? f.buf.get() + t.plan_off : L.h_io;
+  const uint8_t* dpl = t.in_chunk ? dev + t.plan_off : L.d_io;
+  if (nc) memcpy(t.hpl + plan.o_chunks, plan.chunks.data(), nc * sizeof(CrcChunk));
+  if (ni) memcpy(t.hpl + plan.o_imgs, plan.imgs.data(), ni * sizeof(B64Image));
   // the results behind the lane's plan area, host-mapped: the kernel stores them over the link
   uint8_t* res = L.h_io + plan.plan_bytes;
-  hipStream_t st = L.stream;
-  const int64_t t_plan = mono_ns();
-  const bool timed = dev_every_ > 0 && L.nrun++ % dev_every_ == 0;
-  if (timed) check_hip(hipEventRecord(L.tev[0], st), "ingest: timing event");
-  const bool has_plan = plan.plan_bytes > 0;
-  if (plan_in_chunk && has_plan) {
-    check_hip(hipMemcpyAsync(dev + lo, f.buf.get() + lo, plan_off + plan.plan_bytes - lo,
-                             hipMemcpyHostToDevice, st),
-              "ingest: H2D text + plan");
-  } else {
-    check_hip(hipMemcpyAsync(dev + lo, f.buf.get() + lo, span, hipMemcpyHostToDevice, st),
-              "ingest: H2D text");
-    if (has_plan)
-      check_hip(hipMemcpyAsync(L.d_io, L.h_io, plan.plan_bytes, hipMemcpyHostToDevice, st),
-                "ingest: H2D plan");
-  }
-  plan_in_chunk_ += plan_in_chunk && has_plan;
-  if (timed) check_hip(hipEventRecord(L.tev[1], st), "ingest: timing event");
-  text_bytes_ += (int64_t)span;
-  link_bytes_ += (int64_t)span;
   int* wg_bad = reinterpret_cast<int*>(res + plan.o_bad);
+  // ---- device
+  begin(L, ts, f, dev, t);
   check_hip(ingest_crc_b64(dev, reinterpret_cast<const CrcChunk*>(dpl + plan.o_chunks), (int)nc,
                            d_tables_, reinterpret_cast<uint32_t*>(res + plan.o_crc), (int)ni,
                            reinterpret_cast<const B64Image*>(dpl + plan.o_imgs), H, W, C, arena,
-                           wg_bad, st, &input_prep_),
+                           wg_bad, L.stream, &input_prep_),
             "ingest: crc32c + b64 decode");
-  if (timed) {
-    check_hip(hipEventRecord(L.tev[2], st), "ingest: timing event");
-    check_hip(hipEventRecord(L.tev[3], st), "ingest: timing event");  // (no parse launch)
-  }
-  check_hip(hipEventRecord(L.done, st), "ingest: event");
-  const int64_t t_wait = mono_ns();
-  wait(L);
-  const int64_t t_post = mono_ns();
-  ++runs_;
-  prep_ns_ += t_wait - t_start;
-  plan_ns_ += t_plan - t_start;
-  wait_ns_ += t_post - t_wait;
-  if (timed) {
-    float ms[2] = {0.f, 0.f};
-    for (int k = 0; k < 2; ++k)
-      check_hip(hipEventElapsedTime(&ms[k], L.tev[k], L.tev[k + 1]), "ingest: event time");
-    ++dev_runs_;
-    dev_copy_ns_ += (int64_t)(ms[0] * 1e6);
-    dev_count_ns_ += (int64_t)(ms[1] * 1e6);
-    dev_wait_ns_ += t_post - t_wait;
-  }
+  mark(L, ts, 2);
+  const int64_t t_post = end(L, ts, /*parsed=*/false);  // (no parse launch)
   // ---- host: batch CRCs; a record's verdict is the worst of its images' workgroup words
   join_batch_crcs(f, plan.batch_chunks, reinterpret_cast<const uint32_t*>(res + plan.o_crc), io);
   const int64_t per = (int64_t)H * W * C;
@@ -223,153 +245,52 @@ void GpuIngest::run_b64(int lane, const kafka::Fetched& f, uint8_t* dev, size_t 
   post_ns_ += mono_ns() - t_post;
 }
 
+// The ingest of a fetch of JSON number records: one or two DMAs (text, plan) and two launches,
+// ingest_crc_count and - for the records whose arena slots fit - json_parse_instances.
 void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_cap,
                     bool check_crcs, int H, int W, int C, IngestIO& io, float* arena,
                     size_t arena_bytes) {
   Lane& L = *lanes_[(size_t)lane % lanes_.size()];
   std::lock_guard<std::mutex> lk(L.mu);
-  const int64_t t_start = mono_ns();
+  Stamps ts;
+  ts.start = mono_ns();
   const size_t nrec_all = f.records.size();
   io.images.assign(nrec_all, 0);
   io.cnt_off.assign(nrec_all, -1);
   io.batch_ok.assign(f.batches.size(), 1);
   io.img.assign(nrec_all, nullptr);
-  // ---- plan: CRC windows (aligned to each batch's end) and the records to count
-  std::vector<CrcChunk> chunks;
-  std::vector<std::pair<size_t, size_t>> batch_chunks;  // (first chunk, count) per batch
-  size_t lo = f.size, hi = 0;
-  for (const kafka::BatchSpan& b : f.batches) {
-    lo = std::min(lo, b.off);
-    hi = std::max(hi, b.off + b.len);
-    if (!check_crcs) continue;
-    const size_t first = chunks.size();
-    const size_t n = append_crc_windows((int64_t)b.off + kafka::kBatchAttrOffset,
-                                        (int64_t)(b.off + b.len), chunks);
-    batch_chunks.emplace_back(first, n);
-  }
-  std::vector<int> rec_of;  // JsonRecord j -> record index
-  int ntiles = 0, ngroups = 0;
+  // ---- plan: CRC windows, the records to count and to parse, the span that crosses the link,
+  // the count block and every section offset (ingest_plan.h)
+  L.batches.clear();
+  for (const kafka::BatchSpan& b : f.batches)
+    L.batches.emplace_back((int64_t)b.off, (int64_t)b.len);
+  L.recs.resize(nrec_all);
   for (size_t i = 0; i < nrec_all; ++i) {
-    if (io.status[i] != codec::OK) continue;
     const kafka::RecordRef& rr = f.records[i];
-    rec_of.push_back((int)i);
-    const int nt = json_tile_count(rr.value_off + io.arr_off[i], (int32_t)io.arr_len[i]);
-    ntiles += nt;
-    ngroups += (nt + kGroupTiles - 1) / kGroupTiles;
-    lo = std::min(lo, (size_t)rr.value_off);
-    hi = std::max(hi, (size_t)(rr.value_off + rr.value_len));
+    JsonPlanRecord& r = L.recs[i];
+    r.status = io.status[i];
+    r.value_off = rr.value_off;
+    r.value_len = rr.value_len;
+    r.arr_off = io.arr_off[i];
+    r.arr_len = io.arr_len[i];
   }
-  const size_t nc = chunks.size(), nr = rec_of.size();
-  if (nc == 0 && nr == 0) return;
-  // packed body (the source's PackTap, text_pack.h): the whole body crosses the link packed and
-  // is expanded in its device mirror; otherwise the span holding batches and records, raw
-  const bool packed = f.tap_result >= 0;
-  if (packed) {
-    lo = 0;
-    hi = f.size;
-  }
-  lo &= ~(size_t)15;
-  const size_t span = hi - lo;
-  const size_t ng = packed ? codec::pack_groups(span) : 0;
-  const size_t link = packed ? (size_t)f.tap_result : span;
-  // the per-tile token counts stay with the fetch buffer: at the end of its device mirror when
-  // they fit behind the text (and the packed stream), so the parse - here or in the replica that
-  // later takes these records - reuses them instead of counting again
-  const size_t ncnt = (size_t)ntiles + (size_t)ngroups;  // per record: tile counts, group sums
-  int64_t cnt_base = -1;
-  if (ntiles > 0) {
-    const size_t used = packed ? codec::pack_offset(span) + link : hi;
-    const size_t cb = (ncnt * sizeof(int) + 255) & ~(size_t)255;
-    if (dev_cap > cb + 256 && ((dev_cap - cb) & ~(size_t)255) >= ((used + 64 + 255) & ~(size_t)255))
-      cnt_base = (int64_t)((dev_cap - cb) & ~(size_t)255);
-  }
-  // parse at ingest: every counted record whose arena slots fit, images taken from its counts on
-  // the device (JsonRecord::images = -1), verdicts per tile into host memory
-  const int64_t per = (int64_t)H * W * C;
-  const int64_t S = 2 * per;
-  const bool parse = arena && cnt_base >= 0 && per > 0;
-  std::vector<int> pjs;  // parse record p -> counting record j
-  int ptiles = 0;
-  if (parse) {
-    for (size_t j = 0; j < nr; ++j) {
-      const size_t i = (size_t)rec_of[j];
-      const int64_t off = f.records[i].value_off + io.arr_off[i];
-      const int64_t slot = (off + S - 1) / S, cap = io.arr_len[i] / S;
-      if (cap <= 0 || (slot + cap) * per * (int64_t)sizeof(float) > (int64_t)arena_bytes) continue;
-      pjs.push_back((int)j);
-      ptiles += json_tile_count(off, (int32_t)io.arr_len[i]);
-    }
-  }
-  const size_t np = pjs.size();
-  const size_t o_chunks = align16(ng * 2 * sizeof(uint32_t));  // (the pack group table first)
-  const size_t o_groups = o_chunks + align16(nc * sizeof(CrcChunk));
-  const size_t o_recs = o_groups + align16((size_t)ngroups * sizeof(int2));
-  const size_t o_precs = o_recs + nr * sizeof(JsonRecord);  // (JsonRecord is 48 bytes)
-  const size_t o_ptr = o_precs + np * sizeof(JsonRecord);
-  const size_t o_gsum = o_ptr + align16((size_t)ptiles * sizeof(int));
-  const size_t o_crc = o_gsum + align16((size_t)ngroups * 4);
-  const size_t o_gbad = o_crc + align16(nc * 4);
-  const size_t o_pbad = o_gbad + align16((size_t)ngroups * 4);
-  const size_t io_bytes = o_pbad + align16((size_t)ptiles * 4);
-  check_hip(hipSetDevice(device_), "ingest: hipSetDevice");
-  grow(L, io_bytes + 16, ncnt + 1);
-  // the plan part [0, o_gsum): written into the fetch's own pinned chunk, behind the bytes the
-  // copy moves anyway, when it fits before the counts (the chunk is pinned and mirrored at the
-  // same offsets), so ONE DMA carries text and plan; else into the lane's buffer, its own DMA.
+  const JsonIngestPlan& p = L.plan;
+  plan_json_ingest(L.batches, kafka::kBatchAttrOffset, check_crcs, L.recs, H, W, C,
+                   arena ? arena_bytes : 0, f.size, dev_cap, f.tap_result, plan_separate_, L.plan);
+  if (p.empty()) return;
+  const size_t nc = p.nc(), nr = p.nr(), np = p.np();
+  grow(L, p.io_bytes + 16, (size_t)p.ntiles + (size_t)p.ngroups + 1);
+  // ---- fill. The plan part [0, o_gsum): written into the fetch's own pinned chunk, behind the
+  // bytes the copy moves anyway, when it fits before the counts (the chunk is pinned and
+  // mirrored at the same offsets), so ONE DMA carries text and plan; else into the lane's
+  // buffer, its own DMA.
   // (Sampled device timing, GALE_INGEST_DEV_TIMING: the copies were the largest device span of
   // a fetch, 40-60 us, mostly per-DMA latency - profiles/r6_ingest_device_split.jsonl)
-  // (past every byte of the fetch: host code may still read records this plan skips)
-  const size_t used = std::max((size_t)f.size, packed ? codec::pack_offset(span) + link : hi);
-  const size_t plan_off = (used + 255) & ~(size_t)255;
-  const size_t plan_lim = cnt_base >= 0 ? (size_t)cnt_base : dev_cap;
-  const bool plan_in_chunk = !plan_separate_ && plan_off + o_gsum <= plan_lim;
-  uint8_t* hpl = plan_in_chunk ? f.buf.get() + plan_off : L.h_io;  // host view of the plan
-  uint8_t* dpl = plan_in_chunk ? dev + plan_off : L.d_io;          // device view
-  CrcChunk* hc = reinterpret_cast<CrcChunk*>(hpl + o_chunks);
-  int2* hg = reinterpret_cast<int2*>(hpl + o_groups);
-  JsonRecord* hr = reinterpret_cast<JsonRecord*>(hpl + o_recs);
-  if (nc) memcpy(hc, chunks.data(), nc * sizeof(CrcChunk));
-  int tile = 0, grp = 0;
-  for (size_t j = 0; j < nr; ++j) {
-    const size_t i = (size_t)rec_of[j];
-    JsonRecord& jr = hr[j];
-    jr.off = f.records[i].value_off + io.arr_off[i];
-    jr.len = (int32_t)io.arr_len[i];
-    jr.slot = 0;
-    jr.images = 0;
-    jr.status = 0;
-    jr.tile0 = tile;
-    jr.has_cnt = 0;
-    jr.cnt_off = 0;
-    jr.grp0 = grp;
-    const int nt = json_tile_count(jr.off, jr.len);
-    for (int t0 = 0; t0 < nt; t0 += kGroupTiles) {
-      hg[grp].x = (int)j;
-      hg[grp].y = t0;
-      ++grp;
-    }
-    tile += nt;
-  }
-  JsonRecord* hp = reinterpret_cast<JsonRecord*>(hpl + o_precs);
-  int* hpt = reinterpret_cast<int*>(hpl + o_ptr);
-  {
-    int pt = 0;
-    for (size_t k = 0; k < np; ++k) {
-      const JsonRecord& jr = hr[pjs[k]];
-      JsonRecord& pr = hp[k];
-      pr = jr;
-      pr.slot = (int32_t)((jr.off + S - 1) / S);
-      pr.images = -1;  // from the counts, on the device
-      pr.status = 0;
-      pr.tile0 = pt;
-      pr.has_cnt = 1;
-      pr.cnt_off = cnt_base + (int64_t)(jr.tile0 + jr.grp0) * (int64_t)sizeof(int);
-      pr.grp0 = 0;
-      const int nt = json_tile_count(pr.off, pr.len);
-      for (int t = 0; t < nt; ++t) hpt[pt + t] = (int)k;
-      pt += nt;
-    }
-  }
+  uint8_t* hpl = p.plan_in_chunk ? f.buf.get() + p.plan_off : L.h_io;  // host view of the plan
+  uint8_t* dpl = p.plan_in_chunk ? dev + p.plan_off : L.d_io;          // device view
+  fill_json_ingest(p, L.recs, hpl);
+  const JsonRecord* hr = reinterpret_cast<const JsonRecord*>(hpl + p.o_recs);
+  const JsonRecord* hp = reinterpret_cast<const JsonRecord*>(hpl + p.o_precs);
   // ---- device: text span -> mirror (packed: ONE H2D of the packed stream, expanded in place),
   // plan H2D, CRC windows, token counts [, parse]; the kernels store their results (window CRCs,
   // group sums and verdicts, parse tile verdicts) straight into the lane's host-mapped buffer,
@@ -379,111 +300,81 @@ void GpuIngest::run(int lane, const kafka::Fetched& f, uint8_t* dev, size_t dev_
   // chunk made text_unpack 15x slower (device time per batch 0.34 -> 2.9 ms), and reading only
   // the plan and the step's metadata that way still stretched every kernel by 25-40 %
   // (profiles/r5_step_ab.txt).
-  hipStream_t st = L.stream;
-  const int64_t t_plan = mono_ns();  // plan built; the HIP calls follow
-  const bool timed = dev_every_ > 0 && L.nrun++ % dev_every_ == 0;
-  if (timed) check_hip(hipEventRecord(L.tev[0], st), "ingest: timing event");
-  if (packed) memcpy(hpl, f.buf.get() + codec::tab_offset(span), ng * 2 * sizeof(uint32_t));
-  const size_t c_lo = packed ? codec::pack_offset(span) : lo;
-  const size_t c_len = packed ? link : span;
-  if (plan_in_chunk) {
-    check_hip(hipMemcpyAsync(dev + c_lo, f.buf.get() + c_lo, plan_off + o_gsum - c_lo,
-                             hipMemcpyHostToDevice, st),
-              "ingest: H2D text + plan");
-  } else {
-    check_hip(hipMemcpyAsync(dev + c_lo, f.buf.get() + c_lo, c_len, hipMemcpyHostToDevice, st),
-              "ingest: H2D text");
-    check_hip(hipMemcpyAsync(L.d_io, L.h_io, o_gsum, hipMemcpyHostToDevice, st),
-              "ingest: H2D plan");
+  Transfer t;
+  t.lo = p.c_lo;
+  t.len = p.c_len;
+  t.plan_off = p.plan_off;
+  t.plan_bytes = p.o_gsum;
+  t.in_chunk = p.plan_in_chunk;
+  t.hpl = hpl;
+  if (p.packed) {
+    t.tab = f.buf.get() + p.tab_off;
+    t.tab_bytes = p.ng * 2 * sizeof(uint32_t);
   }
-  plan_in_chunk_ += plan_in_chunk;
-  if (timed) check_hip(hipEventRecord(L.tev[1], st), "ingest: timing event");
-  text_bytes_ += (int64_t)span;
-  link_bytes_ += (int64_t)link;
-  uint32_t* d_crc = reinterpret_cast<uint32_t*>(L.h_io + o_crc);   // (host-mapped results)
-  int* d_gsum = reinterpret_cast<int*>(L.h_io + o_gsum);
-  int* d_gbad = reinterpret_cast<int*>(L.h_io + o_gbad);
-  int* d_pbad = reinterpret_cast<int*>(L.h_io + o_pbad);
-  JsonRecord* d_rec = reinterpret_cast<JsonRecord*>(dpl + o_recs);
-  int* d_cnt = cnt_base >= 0 ? reinterpret_cast<int*>(dev + cnt_base) : L.d_counts;
+  t.text_bytes = p.span;
+  t.link_bytes = p.link;
+  begin(L, ts, f, dev, t);
+  uint32_t* d_crc = reinterpret_cast<uint32_t*>(L.h_io + p.o_crc);   // (host-mapped results)
+  int* d_gsum = reinterpret_cast<int*>(L.h_io + p.o_gsum);
+  int* d_gbad = reinterpret_cast<int*>(L.h_io + p.o_gbad);
+  int* d_pbad = reinterpret_cast<int*>(L.h_io + p.o_pbad);
+  int* d_cnt = p.cnt_base >= 0 ? reinterpret_cast<int*>(dev + p.cnt_base) : L.d_counts;
   // CRC windows and token counts: one launch, one pass of workgroups over the buffer. Packed,
   // the same launch expands the text: CRC and counting waves read the packed stream, and the
   // counting waves store each record's text into the mirror for the parse (r4 ran a separate
   // text_unpack pass over the whole body first: a third of the ingest launches, 16 % of the
   // GPU's busy time under the serving load, profiles/r5_step_ab.txt)
-  check_hip(ingest_crc_count(dev, reinterpret_cast<const CrcChunk*>(dpl + o_chunks), (int)nc,
-                             d_tables_, d_crc, (int)nr, ngroups, d_rec,
-                             reinterpret_cast<const int2*>(dpl + o_groups), d_cnt, d_gsum,
-                             d_gbad, st, packed ? dev + codec::pack_offset(span) : nullptr,
-                             packed ? reinterpret_cast<const uint32_t*>(dpl) : nullptr,
-                             packed ? dev : nullptr),
+  check_hip(ingest_crc_count(dev, reinterpret_cast<const CrcChunk*>(dpl + p.o_chunks), (int)nc,
+                             d_tables_, d_crc, (int)nr, p.ngroups,
+                             reinterpret_cast<JsonRecord*>(dpl + p.o_recs),
+                             reinterpret_cast<const int2*>(dpl + p.o_groups), d_cnt, d_gsum,
+                             d_gbad, L.stream, p.packed ? dev + p.c_lo : nullptr,
+                             p.packed ? reinterpret_cast<const uint32_t*>(dpl) : nullptr,
+                             p.packed ? dev : nullptr),
             "ingest: crc32c + count");
-  if (timed) check_hip(hipEventRecord(L.tev[2], st), "ingest: timing event");
+  mark(L, ts, 2);
   // the parse right behind it, same stream (the counts are in place when it starts): the text
   // -> fp32 images in the fetch's arena, so the batch step later runs only the forward
   if (np > 0)
-    check_hip(json_parse_instances((int)np, ptiles, reinterpret_cast<JsonRecord*>(dpl + o_precs),
-                                   reinterpret_cast<const int*>(dpl + o_ptr), dev, H, W, C,
-                                   L.d_counts, arena, st, /*count_pass=*/false, nullptr, nullptr,
-                                   d_pbad, &input_prep_),
+    check_hip(json_parse_instances((int)np, p.ptiles,
+                                   reinterpret_cast<JsonRecord*>(dpl + p.o_precs),
+                                   reinterpret_cast<const int*>(dpl + p.o_ptr), dev, H, W, C,
+                                   L.d_counts, arena, L.stream, /*count_pass=*/false, nullptr,
+                                   nullptr, d_pbad, &input_prep_),
               "ingest: parse");
-  if (timed) check_hip(hipEventRecord(L.tev[3], st), "ingest: timing event");
-  check_hip(hipEventRecord(L.done, st), "ingest: event");
-  const int64_t t_wait = mono_ns();
-  wait(L);
-  const int64_t t_post = mono_ns();
-  ++runs_;
-  prep_ns_ += t_wait - t_start;
-  plan_ns_ += t_plan - t_start;
-  wait_ns_ += t_post - t_wait;
-  if (timed) {
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k)
-      check_hip(hipEventElapsedTime(&ms[k], L.tev[k], L.tev[k + 1]), "ingest: event time");
-    ++dev_runs_;
-    dev_copy_ns_ += (int64_t)(ms[0] * 1e6);
-    dev_count_ns_ += (int64_t)(ms[1] * 1e6);
-    dev_parse_ns_ += (int64_t)(ms[2] * 1e6);
-    dev_wait_ns_ += t_post - t_wait;
-  }
+  const int64_t t_post = end(L, ts, /*parsed=*/true);
   // ---- host: join the windows of each batch and compare; images from the element counts
-  join_batch_crcs(f, batch_chunks, reinterpret_cast<const uint32_t*>(L.h_io + o_crc), io);
+  join_batch_crcs(f, p.batch_chunks, d_crc, io);
   // a record's tokens: the sums of its tile groups (and its verdict: the worst group's)
-  const int* gsum = reinterpret_cast<const int*>(L.h_io + o_gsum);
-  const int* gbad = reinterpret_cast<const int*>(L.h_io + o_gbad);
-  const int* pbad = reinterpret_cast<const int*>(L.h_io + o_pbad);
-  std::vector<int> parsed_as(nr, -1);
-  for (size_t k = 0; k < np; ++k) parsed_as[(size_t)pjs[k]] = (int)k;
+  size_t k = 0;  // the next parse record (pjs ascends)
   for (size_t j = 0; j < nr; ++j) {
-    const size_t i = (size_t)rec_of[j];
-    const int64_t g1 = j + 1 < nr ? hr[j + 1].grp0 : ngroups;
+    const size_t i = (size_t)p.rec_of[j];
+    const bool parsed = k < np && (size_t)p.pjs[k] == j;
+    const JsonRecord* pr = parsed ? &hp[k++] : nullptr;
+    const int64_t g1 = j + 1 < nr ? hr[j + 1].grp0 : p.ngroups;
     int64_t tok = 0;
     int bad = 0;
     for (int64_t g = hr[j].grp0; g < g1; ++g) {
-      tok += gsum[g];
-      bad |= gbad[g];
+      tok += d_gsum[g];
+      bad |= d_gbad[g];
     }
     if (bad != 0) {
       io.status[i] = codec::BAD_NUMBER;
     } else if (tok == 0) {
       io.status[i] = codec::EMPTY;
-    } else if (tok % per != 0) {
+    } else if (tok % p.per != 0) {
       io.status[i] = codec::BAD_SHAPE;
     } else {
-      io.images[i] = (int32_t)(tok / per);
-      if (cnt_base >= 0)
-        io.cnt_off[i] = cnt_base + (hr[j].tile0 + hr[j].grp0) * (int64_t)sizeof(int);
-      const int k = parsed_as[j];
-      if (k >= 0) {
-        // the parse's verdict (structure, element count, numbers): the worst of its tiles, in
-        // the replica's mapping (GpuReplica::wait)
-        const JsonRecord& pr = hp[k];
-        const int nt = json_tile_count(pr.off, pr.len);
+      io.images[i] = (int32_t)(tok / p.per);
+      if (p.cnt_base >= 0) io.cnt_off[i] = p.cnt_off(hr[j]);
+      if (pr) {
+        // the parse's verdict (structure, element count, numbers): the worst of its tiles
+        const int nt = json_tile_count(pr->off, pr->len);
         int v = 0;
-        for (int t = 0; t < nt; ++t) v = std::max(v, pbad[pr.tile0 + t]);
-        if (v == 1 || v == 3) io.status[i] = codec::BAD_SHAPE;
-        else if (v == 2) io.status[i] = codec::BAD_NUMBER;
-        else io.img[i] = arena + (int64_t)pr.slot * per;
+        for (int t0 = 0; t0 < nt; ++t0) v = std::max(v, d_pbad[pr->tile0 + t0]);
+        const int32_t verdict = device_verdict_status(v);
+        if (verdict != codec::OK) io.status[i] = verdict;
+        else io.img[i] = arena + (int64_t)pr->slot * p.per;
       }
     }
   }

@@ -10,8 +10,8 @@
 #include <vector>
 
 #include "gale/kernels.h"
-#include "b64_ingest_plan.h"
 #include "ingest.h"
+#include "ingest_plan.h"
 
 namespace gale {
 
@@ -55,15 +55,15 @@ class GpuIngest : public Ingest {
     std::mutex mu;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    // one host-mapped pinned buffer and a device image of its plan part:
-    //   [pack tab u32 x 2 per 2 KiB group][CrcChunk x nc][int2 group x ng][JsonRecord x nr]
-    //   [parse JsonRecord x np][parse tile -> record i32 x npt]
-    //   [group sum i32 x ng][crc u32 x nc][group verdict i32 x ng][parse tile verdict i32 x npt]
-    // the host writes the plan, ONE H2D copies it (up to the group sums) into d_io, and
-    // ingest_crc_count stores the results (group sums and verdicts, window CRCs) straight into
-    // the host buffer: no D2H copy
-    // run_b64: [CrcChunk x nc][B64Image x ni] (the plan, when it does not ride in the fetch's
-    // chunk) [crc u32 x nc][workgroup verdict i32 x ni * chunks per image]
+    // one host-mapped pinned buffer and a device image of its plan part, laid out by the
+    // fetch's plan (ingest_plan.h):
+    //   run (JsonIngestPlan): the plan sections [0, o_gsum) - pack tab, o_chunks, o_groups,
+    //   o_recs, o_precs, o_ptr - then the result sections o_gsum, o_crc, o_gbad, o_pbad
+    //   run_b64 (B64IngestPlan): the plan sections [0, plan_bytes) - o_chunks, o_imgs - then,
+    //   from plan_bytes on, the result sections o_crc, o_bad
+    // The host writes the plan sections - here, or behind the fetch in its own pinned chunk, when
+    // they fit there - ONE H2D copies them into d_io (or carries them with the text), and the
+    // kernels store the result sections straight into the host buffer: no D2H copy
     uint8_t* h_io = nullptr;
     uint8_t* d_io = nullptr;
     size_t io_cap = 0;
@@ -71,9 +71,37 @@ class GpuIngest : public Ingest {
     size_t counts_cap = 0;
     hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};  // sampled device timing
     int64_t nrun = 0;
+    // run()'s plan and its inputs, kept for their capacity: a fetch allocates nothing
+    std::vector<std::pair<int64_t, int64_t>> batches;
+    std::vector<JsonPlanRecord> recs;
+    JsonIngestPlan plan;
+  };
+  // What begin() moves to the device: the fetch's bytes [lo, lo + len) into its mirror and the
+  // plan sections, `plan_bytes` at hpl - in the fetch's chunk at plan_off (in_chunk: one DMA
+  // carries both) or in the lane's buffer (its own DMA into d_io).
+  struct Transfer {
+    size_t lo = 0, len = 0;
+    size_t plan_off = 0, plan_bytes = 0;
+    bool in_chunk = false;
+    uint8_t* hpl = nullptr;
+    // packed body: its pack group table, copied in front of the plan sections
+    const uint8_t* tab = nullptr;
+    size_t tab_bytes = 0;
+    size_t text_bytes = 0, link_bytes = 0;  // for the link counters
+  };
+  struct Stamps {  // of one lane transaction (mono_ns)
+    int64_t start = 0, plan = 0;
+    bool timed = false;  // this run is in the device timing sample
   };
   void grow(Lane& L, size_t io_bytes, size_t tiles);
   void wait(Lane& L);
+  // One lane transaction around a run's launches (the caller holds the lane and has grown it):
+  // begin() issues the copies, mark() records timing event k between launches, end() records the
+  // rest, waits for the device and does the accounting; a run with one launch (parsed false)
+  // leaves the parse span out.
+  void begin(Lane& L, Stamps& ts, const kafka::Fetched& f, uint8_t* dev, const Transfer& t);
+  void mark(Lane& L, const Stamps& ts, int k);
+  int64_t end(Lane& L, const Stamps& ts, bool parsed);
   void join_batch_crcs(const kafka::Fetched& f,
                        const std::vector<std::pair<size_t, size_t>>& batch_chunks,
                        const uint32_t* crc, IngestIO& io);

@@ -252,6 +252,28 @@ void GpuReplica::submit(Batch& b) {
   const float* in = static_cast<const float*>(exec_->input(slot));
   s.parse_idx.assign(b.recs.size(), -1);
   if (ptr_input_) ensure_tiles(s, 1, 0);  // (the pointer table lives in the metadata)
+  // where a record's instances array stands in the slot's device bytes: resident in a mirror,
+  // inside a pinned span, or staged here behind the spans
+  auto dev_offset = [&](const InRecord& r) -> int64_t {
+    const uint8_t* base = r.buf.get();
+    const size_t lo = (size_t)(r.value + r.arr_off - base);
+    if (resident(r)) {
+      // offsets are relative to the slot's buffer; a mirror elsewhere in device memory is a
+      // (signed) distance in the flat address space, 16-byte phase preserved (both bases are
+      // 256-byte aligned allocations)
+      return (int64_t)((r.dev_value + r.arr_off) - s.d_bytes);
+    }
+    if (r.pinned) {
+      size_t k = 0;
+      while (spans[k].base != base) ++k;
+      return (int64_t)(span_dev[k] + (lo - spans[k].lo));
+    }
+    hoff += (lo - hoff) & 15;  // keep the record's alignment modulo 16
+    memcpy(s.h_bytes + hoff, r.value + r.arr_off, (size_t)r.arr_len);
+    const int64_t off = (int64_t)(staged_dev + hoff);
+    hoff = (hoff + (size_t)r.arr_len + 15) & ~(size_t)15;
+    return off;
+  };
   for (size_t ri = 0; ri < b.recs.size(); ++ri) {
     const InRecord& r = b.recs[ri];
     if (img + r.images > exec_->max_batch())
@@ -267,21 +289,7 @@ void GpuReplica::submit(Batch& b) {
     s.parse_idx[ri] = nrec;
     if (b64_) {
       // one descriptor per image: where its string starts in the staged bytes
-      const uint8_t* base = r.buf.get();
-      const size_t lo = (size_t)(r.value + r.arr_off - base);
-      int64_t off;
-      if (resident(r)) {
-        off = (int64_t)((r.dev_value + r.arr_off) - s.d_bytes);
-      } else if (r.pinned) {
-        size_t k = 0;
-        while (spans[k].base != base) ++k;
-        off = (int64_t)(span_dev[k] + (lo - spans[k].lo));
-      } else {
-        hoff += (lo - hoff) & 15;  // keep the record's alignment modulo 16
-        memcpy(s.h_bytes + hoff, r.value + r.arr_off, (size_t)r.arr_len);
-        off = (int64_t)(staged_dev + hoff);
-        hoff = (hoff + (size_t)r.arr_len + 15) & ~(size_t)15;
-      }
+      const int64_t off = dev_offset(r);
       if (!codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, H_, W_, C_,
                                     s.b64_offs) ||
           (int)s.b64_offs.size() != r.images)
@@ -296,23 +304,7 @@ void GpuReplica::submit(Batch& b) {
       continue;
     }
     JsonRecord& jr = s.h_recs[nrec++];
-    const uint8_t* base = r.buf.get();
-    const size_t lo = (size_t)(r.value + r.arr_off - base);
-    if (resident(r)) {
-      // offsets are relative to the slot's buffer; a mirror elsewhere in device memory is a
-      // (signed) distance in the flat address space, 16-byte phase preserved (both bases are
-      // 256-byte aligned allocations)
-      jr.off = (int64_t)((r.dev_value + r.arr_off) - s.d_bytes);
-    } else if (r.pinned) {
-      size_t k = 0;
-      while (spans[k].base != base) ++k;
-      jr.off = (int64_t)(span_dev[k] + (lo - spans[k].lo));
-    } else {
-      hoff += (lo - hoff) & 15;  // keep the record's alignment modulo 16
-      memcpy(s.h_bytes + hoff, r.value + r.arr_off, (size_t)r.arr_len);
-      jr.off = (int64_t)(staged_dev + hoff);
-      hoff = (hoff + (size_t)r.arr_len + 15) & ~(size_t)15;
-    }
+    jr.off = dev_offset(r);
     jr.len = (int32_t)r.arr_len;
     jr.slot = img;
     jr.images = r.images;
@@ -592,8 +584,7 @@ void GpuReplica::wait(Batch& b) {
     const int st = copy_free ? s.h_status[k]
                    : b64_    ? b64_status(s.h_recs)[k]
                              : s.h_recs[k].status;
-    if (st == 1 || st == 3) b.dev_status[i] = codec::BAD_SHAPE;
-    else if (st == 2) b.dev_status[i] = codec::BAD_NUMBER;
+    b.dev_status[i] = device_verdict_status(st);
   }
   b.probs = gpu_encode_ ? nullptr : s.h_out;
   b.pred_text = gpu_encode_ ? s.h_text : nullptr;

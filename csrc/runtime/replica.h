@@ -15,10 +15,18 @@
 #include <string>
 #include <vector>
 
+#include "../codec/json_codec.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
 
 namespace gale {
+
+// The device parsers' verdict word (json_parse_instances' record status or the worst of a
+// record's tile verdicts: 0 ok, 1 number-count mismatch, 2 malformed number, 3 bad structure) as
+// the codec::Status the engine reports - one mapping for the replica's parse and the ingest's.
+inline int32_t device_verdict_status(int v) {
+  return v == 1 || v == 3 ? codec::BAD_SHAPE : v == 2 ? codec::BAD_NUMBER : codec::OK;
+}
 
 struct InRecord;
 // A record with more images than one micro-batch holds (InstObj N > max_batch): it is served as

@@ -1,4 +1,4 @@
-// Sanitizer run of the base64 ingest's host plan (csrc/runtime/b64_ingest_plan.h) behind the real
+// Sanitizer run of the base64 ingest's host plan (csrc/runtime/ingest_plan.h) behind the real
 // scanner: a fixed seed, fetch-like buffers of valid records of several shapes, then mutated and
 // truncated copies of their text AND of the scan results handed to the plan (counts, offsets,
 // extents). Every buffer is a heap block of exactly its size. The plan either throws
@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../codec/json_codec.h"
-#include "../runtime/b64_ingest_plan.h"
+#include "../runtime/ingest_plan.h"
 
 using namespace gale;
 
