@@ -96,6 +96,15 @@ build/asan/json_plan_check: csrc/tests/json_plan_check.cpp csrc/runtime/ingest_p
 	    csrc/tests/json_plan_check.cpp csrc/runtime/ingest_plan.cpp \
 	    csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
+# the GPU replica's host batch plan (layout + fill) on random and mutated batches
+# (csrc/tests/batch_plan_check.cpp): the plan alone, no codec, no engine, no HIP call
+build/asan/batch_plan_check: csrc/tests/batch_plan_check.cpp csrc/runtime/batch_plan.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 \
+	    -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Icsrc/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/batch_plan_check.cpp csrc/runtime/batch_plan.cpp -o $@
+
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500
 

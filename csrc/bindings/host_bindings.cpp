@@ -18,6 +18,7 @@
 #include "../kafka/client.h"
 #include "../kafka/compress.h"
 #include "../kafka/fetch_framing.h"
+#include "../runtime/batch_plan.h"
 #include "../runtime/ingest_plan.h"
 #include "../runtime/pack_tap.h"
 #include "../kafka/protocol.h"
@@ -572,6 +573,85 @@ void bind_host(py::module_& m) {
         py::arg("check_crcs") = true,
         "The host plan of a JSON fetch's device ingest, laid out and filled "
         "(csrc/runtime/ingest_plan.h)");
+  m.def("plan_batch",
+        [](std::vector<py::dict> recs, int max_batch, int tiles_cap, int64_t per,
+           const std::string& form, bool ptr_input, bool b64, uint64_t d_bytes,
+           uint64_t input_base) {
+          // recs: dicts of BatchPlanRecord's fields (absent = default), "b64_offs" a record's
+          // string offsets
+          std::vector<BatchPlanRecord> rs(recs.size());
+          std::vector<uint32_t> offs;
+          for (size_t i = 0; i < recs.size(); ++i) {
+            const py::dict& d = recs[i];
+            BatchPlanRecord& r = rs[i];
+            auto get = [&d](const char* k, auto& v) {
+              if (d.contains(k)) v = d[k].cast<std::decay_t<decltype(v)>>();
+            };
+            get("buf", r.buf);
+            get("arr_off", r.arr_off);
+            get("arr_len", r.arr_len);
+            get("images", r.images);
+            get("pinned", r.pinned);
+            get("resident", r.resident);
+            get("preparsed", r.preparsed);
+            get("dev_text", r.dev_text);
+            get("dev_counts", r.dev_counts);
+            get("dev_image", r.dev_image);
+            if (d.contains("b64_offs")) {
+              const auto o = d["b64_offs"].cast<std::vector<uint32_t>>();
+              r.b64_first = (int32_t)offs.size();
+              r.b64_n = (int32_t)o.size();
+              offs.insert(offs.end(), o.begin(), o.end());
+            }
+          }
+          const StepForm f = form == "op-by-op"   ? StepForm::OpByOp
+                             : form == "captured" ? StepForm::Captured
+                             : form == "kernels"  ? StepForm::Kernels
+                                                  : throw std::invalid_argument("plan_batch: form");
+          BatchPlan p;
+          plan_batch(rs, max_batch, per, f, ptr_input, b64, p);
+          const MetaLayout L(max_batch, std::max(tiles_cap, p.ntiles));
+          const MetaRange used = L.used(p);
+          // the whole allocation, 0xEE where fill_batch wrote nothing
+          std::string meta(L.total, '\xee');
+          fill_batch(p, rs, offs, L, d_bytes, input_base, reinterpret_cast<uint8_t*>(&meta[0]));
+          py::list spans, staged;
+          for (const BatchPlan::Span& x : p.spans)
+            spans.append(py::make_tuple(x.buf, x.lo, x.len, x.dev));
+          for (const BatchPlan::Staged& g : p.staged)
+            staged.append(py::make_tuple(g.rec, g.host, g.len));
+          py::dict out;
+          out["spans"] = spans;
+          out["staged"] = staged;
+          out["parse_idx"] = py::cast(p.parse_idx);
+          out["staged_bytes"] = p.staged_bytes;
+          out["staged_dev"] = p.staged_dev;
+          out["dev_total"] = p.dev_total;
+          out["nrec"] = p.nrec;
+          out["ntiles"] = p.ntiles;
+          out["img"] = p.img;
+          out["b64n"] = p.b64n;
+          out["npre"] = p.npre;
+          out["resident"] = p.resident;
+          out["count_pass"] = p.count_pass;
+          py::dict lay;
+          lay["hdr"] = L.hdr;
+          lay["recs"] = L.recs;
+          lay["xs"] = L.xs;
+          lay["tiles"] = L.tiles;
+          lay["b64_table"] = L.b64_table;
+          lay["b64_status"] = L.b64_status;
+          lay["total"] = L.total;
+          out["layout"] = lay;
+          out["used"] = py::make_tuple(used.off, used.bytes);
+          out["meta"] = py::bytes(meta);
+          return out;
+        },
+        py::arg("recs"), py::arg("max_batch"), py::arg("tiles_cap"), py::arg("per"),
+        py::arg("form"), py::arg("ptr_input") = false, py::arg("b64") = false,
+        py::arg("d_bytes") = (uint64_t)0, py::arg("input_base") = (uint64_t)0,
+        "The host plan of a GPU replica's batch, laid out and filled "
+        "(csrc/runtime/batch_plan.h)");
   m.attr("BATCH_ATTR_OFFSET") = (int)kafka::kBatchAttrOffset;
   m.def("split_instances_b64", [](py::bytes arr, int H, int W, int C) -> py::object {
     const std::string_view s = view(arr);

@@ -16,6 +16,32 @@
 
 namespace gale {
 
+namespace {
+
+// a section of a slot's metadata (host copy or device mirror) at its MetaLayout offset
+template <typename T>
+T* meta_at(uint8_t* base, size_t off) {
+  return reinterpret_cast<T*>(base + off);
+}
+
+}  // namespace
+
+// How a site emits the step's sequence (emit_step)
+struct GpuReplica::StepDesc {
+  bool device_counts;  // the kernels read the batch's counts from the metadata header, their
+                       // launches sized for the largest batch; else the host passes them
+  bool meta_h2d;       // the metadata's copy is part of the sequence (else: ahead of it)
+  // the prediction text / the text and the verdicts, from the forward's epilogue or the
+  // formatting kernel / the probabilities copied back
+  enum { Text, TextVerdicts, Probs } out;
+  bool verdict_d2h;  // the verdicts are copied back from the metadata
+};
+
+struct GpuReplica::StepError {
+  hipError_t code;
+  const char* what;
+};
+
 // ---------------------------------------------------------------------------------------------
 // GpuReplica
 // ---------------------------------------------------------------------------------------------
@@ -28,6 +54,8 @@ GpuReplica::GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int 
       step_direct_(step_direct) {
   step_graph_ = step_graph && use_graph && exec_->device_batch_ok();
   ptr_input_ = step_graph_ && gpu_encode_ && step_direct_ && exec_->step_out_ok();
+  my_loc_ = this->locality();
+  form_ = !step_graph_ ? StepForm::OpByOp : gpu_encode_ ? StepForm::Kernels : StepForm::Captured;
   if (exec_->input_bytes_per_image() != (long long)H * W * C * 4)
     throw std::invalid_argument("GpuReplica: executor input is not fp32 [H, W, C]");
   if (exec_->output_bytes_per_image() != (long long)classes * 4)
@@ -70,7 +98,7 @@ GpuReplica::GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int 
               "hipEventCreate");
     // initial text capacity: ~12 bytes per number (Java Float.toString + ",") x a full batch
     ensure_device(s, (size_t)mb * H * W * C * 12 + 4096);
-    ensure_tiles(s, (int)(((size_t)mb * H * W * C * 12) / kJsonTileBytes) + 2 * mb, 0);
+    ensure_tiles(s, (int)(((size_t)mb * H * W * C * 12) / kJsonTileBytes) + 2 * mb);
   }
 }
 
@@ -81,8 +109,8 @@ GpuReplica::~GpuReplica() {
     drop_steps(s);
     if (s.h_bytes) hipHostFree(s.h_bytes);
     if (s.d_bytes) hipFree(s.d_bytes);
-    if (s.h_hdr) hipHostFree(s.h_hdr);
-    if (s.d_hdr) hipFree(s.d_hdr);
+    if (s.h_meta) hipHostFree(s.h_meta);
+    if (s.d_meta) hipFree(s.d_meta);
     if (s.d_tiles) hipFree(s.d_tiles);
     if (s.h_out) hipHostFree(s.h_out);
     if (s.h_text) hipHostFree(s.h_text);
@@ -128,45 +156,29 @@ void GpuReplica::drop_steps(Slot& s) {
   }
 }
 
-size_t GpuReplica::meta_rec_bytes() const {
-  return (sizeof(JsonRecord) + sizeof(float*)) * (size_t)exec_->max_batch();
-}
-
-// Per-slot parser metadata: [header][JsonRecord x max_batch][input pointer x max_batch]
-// [tile -> record index x tiles_cap], pinned on the host and mirrored on the device (one H2D per
-// batch), plus the per-tile token counts. Growing keeps the first `keep` records and the input
-// pointer table already written into the host copy.
-void GpuReplica::ensure_tiles(Slot& s, int ntiles, int keep) {
-  if (ntiles <= s.tiles_cap) return;
-  const int cap = std::max(ntiles, s.tiles_cap * 2);
-  const size_t rec_bytes = meta_rec_bytes();
-  const size_t xs_off = sizeof(JsonRecord) * (size_t)exec_->max_batch();
-  const size_t bytes = kMetaHdr + rec_bytes + sizeof(int) * (size_t)cap;
-  if (s.h_hdr) check_hip(hipEventSynchronize(s.done), "hipEventSynchronize");
-  // host-mapped: the copy-free step graph's kernels read the metadata from here
-  uint8_t* h = static_cast<uint8_t*>(mapped_alloc(bytes, "meta"));
-  memset(h, 0, kMetaHdr);
-  if (s.h_hdr) {
-    memcpy(h + kMetaHdr, s.h_recs, sizeof(JsonRecord) * (size_t)keep);
-    memcpy(h + kMetaHdr + xs_off, s.h_xs, sizeof(float*) * (size_t)exec_->max_batch());
+// Per-slot parser metadata (MetaLayout, batch_plan.h), pinned on the host and mirrored on the
+// device (one H2D per batch), plus the per-tile token counts. Grown before the batch's metadata
+// is written (the plan knows the tile count first), so nothing is carried over.
+void GpuReplica::ensure_tiles(Slot& s, int ntiles) {
+  if (ntiles <= s.meta.tiles_cap) return;
+  const MetaLayout m(exec_->max_batch(), std::max(ntiles, s.meta.tiles_cap * 2));
+  if (s.h_meta) {
+    check_hip(hipEventSynchronize(s.done), "hipEventSynchronize");
     drop_steps(s);
-    hipHostFree(s.h_hdr);
-    hipFree(s.d_hdr);
+    hipHostFree(s.h_meta);
+    hipFree(s.d_meta);
     hipFree(s.d_tiles);
+    s.h_meta = s.d_meta = nullptr;
+    s.d_tiles = nullptr;
+    s.meta = MetaLayout();
   }
-  uint8_t* d = nullptr;
-  check_hip(hipMalloc(reinterpret_cast<void**>(&d), bytes), "hipMalloc(meta)");
-  s.h_hdr = reinterpret_cast<int32_t*>(h);
-  s.d_hdr = reinterpret_cast<int32_t*>(d);
-  s.h_recs = reinterpret_cast<JsonRecord*>(h + kMetaHdr);
-  s.d_recs = reinterpret_cast<JsonRecord*>(d + kMetaHdr);
-  s.h_xs = reinterpret_cast<const float**>(h + kMetaHdr + xs_off);
-  s.d_xs = reinterpret_cast<const float**>(d + kMetaHdr + xs_off);
-  check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_tiles), sizeof(int) * cap),
+  // host-mapped: the copy-free step graph's kernels read the metadata from here
+  s.h_meta = static_cast<uint8_t*>(mapped_alloc(m.total, "meta"));
+  memset(s.h_meta, 0, MetaLayout::kHeaderBytes);
+  check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_meta), m.total), "hipMalloc(meta)");
+  check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_tiles), sizeof(int) * (size_t)m.tiles_cap),
             "hipMalloc(tiles)");
-  s.h_tile_rec = reinterpret_cast<int*>(reinterpret_cast<char*>(s.h_recs) + rec_bytes);
-  s.d_tile_rec = reinterpret_cast<int*>(reinterpret_cast<char*>(s.d_recs) + rec_bytes);
-  s.tiles_cap = cap;
+  s.meta = m;
 }
 
 void GpuReplica::ensure_device(Slot& s, size_t bytes) {
@@ -181,241 +193,117 @@ void GpuReplica::ensure_device(Slot& s, size_t bytes) {
   s.d_cap = cap;
 }
 
-// Stage the batch's JSON text on the device. Records that arrived in pinned fetch buffers are
-// DMA'd straight from them: one hipMemcpyAsync per fetch buffer covering the records' span
-// (the few Kafka record-header bytes between values ride along); records in pageable memory are
-// first gathered into the slot's pinned staging buffer. Offsets keep their position modulo 16,
-// so the parser's aligned 16-byte loads see the same layout as on the host.
+// The batch as the plan sees it (BatchPlanRecord): where each record's instances array lies,
+// whether this replica's device memory holds its text (GPU ingest, its own locality slot) and
+// its parsed images, and for b64 records where their strings start.
+void GpuReplica::describe(const Batch& b, Slot& s) {
+  s.recs.assign(b.recs.size(), BatchPlanRecord());
+  s.b64_offs.clear();
+  for (size_t i = 0; i < b.recs.size(); ++i) {
+    const InRecord& r = b.recs[i];
+    BatchPlanRecord& p = s.recs[i];
+    p.arr_len = r.arr_len;
+    p.images = r.images;
+    p.pinned = r.pinned;
+    p.resident = resident(r);
+    p.preparsed = preparsed(r);
+    if (p.resident) {
+      p.dev_text = reinterpret_cast<uint64_t>(r.dev_value + r.arr_off);
+      p.dev_counts = reinterpret_cast<uint64_t>(r.dev_counts);
+      p.dev_image = reinterpret_cast<uint64_t>(r.dev_image);
+    } else {
+      p.buf = reinterpret_cast<uint64_t>(r.buf.get());
+      p.arr_off = (r.value + r.arr_off) - r.buf.get();
+    }
+    if (b64_ && !p.preparsed) {
+      p.b64_first = (int32_t)s.b64_offs.size();
+      p.b64_n = codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, H_, W_, C_,
+                                         s.b64_scan)
+                    ? (int32_t)s.b64_scan.size()
+                    : -1;
+      s.b64_offs.insert(s.b64_offs.end(), s.b64_scan.begin(), s.b64_scan.end());
+    }
+  }
+}
+
+// One batch: its step is the forward alone when the ingest parsed every record (table_step);
+// otherwise the plan (batch_plan.h) says where every record's text goes on the device and what
+// the parser's metadata holds, the slot's buffers grow to fit, the text and the metadata are
+// written, and the step is launched in the replica's form.
 void GpuReplica::submit(Batch& b) {
   const int slot = next_slot_;
   next_slot_ = (next_slot_ + 1) % (int)slots_.size();
   b.slot = slot;
   Slot& s = slots_[(size_t)slot];
-  struct Span {
-    const uint8_t* base;
-    size_t lo, hi;
-  };
-  std::vector<Span> spans;
-  size_t staged = 0;
-  const int my_loc = locality();
-  auto resident = [my_loc](const InRecord& r) {
-    return r.dev_value != nullptr && r.dev_locality == my_loc;
-  };
-  // images the GPU ingest already parsed (its arena is in this replica's device memory)
-  auto preparsed = [&](const InRecord& r) { return ptr_input_ && resident(r) && r.dev_image; };
-  if (ptr_input_ && try_table_step(b, s, slot, preparsed)) return;
-  for (const InRecord& r : b.recs) {
-    if (resident(r)) continue;  // already in device memory (GPU ingest): nothing to copy
-    const uint8_t* base = r.buf.get();
-    const size_t lo = (size_t)(r.value + r.arr_off - base), hi = lo + (size_t)r.arr_len;
-    if (!r.pinned) {
-      staged += ((size_t)r.arr_len + 31) & ~(size_t)15;
-      continue;
-    }
-    Span* sp = nullptr;
-    for (Span& x : spans)
-      if (x.base == base) sp = &x;
-    if (!sp) {
-      spans.push_back({base, lo, hi});
-    } else {
-      sp->lo = std::min(sp->lo, lo);
-      sp->hi = std::max(sp->hi, hi);
-    }
+  if (!(ptr_input_ && table_step(b, s, slot))) {
+    BatchPlan& p = s.plan;
+    describe(b, s);
+    plan_batch(s.recs, exec_->max_batch(), (int64_t)H_ * W_ * C_, form_, ptr_input_, b64_, p);
+    resident_ += p.resident;
+    host_ += (int64_t)b.recs.size() - p.resident;
+    preparsed_ += p.npre;
+    b.images = p.img;
+    ensure_device(s, p.dev_total + 16);
+    if (p.staged_bytes) ensure_host(s, p.staged_bytes + 16);
+    ensure_tiles(s, p.ntiles);
+    stage_text(b, s);
+    fill_batch(p, s.recs, s.b64_offs, s.meta, reinterpret_cast<uint64_t>(s.d_bytes),
+               reinterpret_cast<uint64_t>(exec_->input(slot)), s.h_meta);
+    launch_step(b, s, slot);
   }
-  size_t dev_total = 16 + staged;
-  for (Span& x : spans) {
-    x.lo &= ~(size_t)15;
-    dev_total += ((x.hi - x.lo) + 15) & ~(size_t)15;
-  }
-  ensure_device(s, dev_total + 16);
-  if (staged) ensure_host(s, staged + 16);
-  // device layout: [span 0][span 1]...[staged records]
-  std::vector<size_t> span_dev(spans.size());
-  size_t doff = 0;
-  for (size_t i = 0; i < spans.size(); ++i) {
-    span_dev[i] = doff;
-    check_hip(hipMemcpyAsync(s.d_bytes + doff, spans[i].base + spans[i].lo,
-                             spans[i].hi - spans[i].lo, hipMemcpyHostToDevice, stream_),
-              "H2D span");
-    doff += ((spans[i].hi - spans[i].lo) + 15) & ~(size_t)15;
-  }
-  const size_t staged_dev = doff;
-  size_t hoff = 0;
-  int nrec = 0, img = 0, ntiles = 0, npre = 0;
-  // b64: descriptors written so far. The table is dense over the images decoded in this step:
-  // a batch can mix them with images the ingest already decoded (a split record's fragments
-  // next to preparsed records), which have no descriptor - the decode launch takes this count,
-  // not the batch's image count
-  int b64n = 0;
-  bool count_pass = false;
-  const int64_t per = (int64_t)H_ * W_ * C_;
-  const float* in = static_cast<const float*>(exec_->input(slot));
-  s.parse_idx.assign(b.recs.size(), -1);
-  if (ptr_input_) ensure_tiles(s, 1, 0);  // (the pointer table lives in the metadata)
-  // where a record's instances array stands in the slot's device bytes: resident in a mirror,
-  // inside a pinned span, or staged here behind the spans
-  auto dev_offset = [&](const InRecord& r) -> int64_t {
-    const uint8_t* base = r.buf.get();
-    const size_t lo = (size_t)(r.value + r.arr_off - base);
-    if (resident(r)) {
-      // offsets are relative to the slot's buffer; a mirror elsewhere in device memory is a
-      // (signed) distance in the flat address space, 16-byte phase preserved (both bases are
-      // 256-byte aligned allocations)
-      return (int64_t)((r.dev_value + r.arr_off) - s.d_bytes);
-    }
-    if (r.pinned) {
-      size_t k = 0;
-      while (spans[k].base != base) ++k;
-      return (int64_t)(span_dev[k] + (lo - spans[k].lo));
-    }
-    hoff += (lo - hoff) & 15;  // keep the record's alignment modulo 16
-    memcpy(s.h_bytes + hoff, r.value + r.arr_off, (size_t)r.arr_len);
-    const int64_t off = (int64_t)(staged_dev + hoff);
-    hoff = (hoff + (size_t)r.arr_len + 15) & ~(size_t)15;
-    return off;
-  };
-  for (size_t ri = 0; ri < b.recs.size(); ++ri) {
-    const InRecord& r = b.recs[ri];
-    if (img + r.images > exec_->max_batch())
-      throw std::logic_error("GpuReplica: batch exceeds max_batch");
-    if (preparsed(r)) {  // the forward reads its images where the ingest parsed them
-      for (int k = 0; k < r.images; ++k) s.h_xs[img + k] = r.dev_image + k * per;
-      img += r.images;
-      ++npre;
-      continue;
-    }
-    if (ptr_input_)
-      for (int k = 0; k < r.images; ++k) s.h_xs[img + k] = in + (int64_t)(img + k) * per;
-    s.parse_idx[ri] = nrec;
-    if (b64_) {
-      // one descriptor per image: where its string starts in the staged bytes
-      const int64_t off = dev_offset(r);
-      if (!codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, H_, W_, C_,
-                                    s.b64_offs) ||
-          (int)s.b64_offs.size() != r.images)
-        throw std::logic_error("GpuReplica: b64 record does not match its scan");
-      B64Image* tab = b64_table(s.h_recs);
-      for (int k = 0; k < r.images; ++k)
-        tab[b64n + k] = B64Image{off + (int64_t)s.b64_offs[(size_t)k], img + k, nrec};
-      b64n += r.images;
-      b64_status(s.h_recs)[nrec] = 0;
-      ++nrec;
-      img += r.images;
-      continue;
-    }
-    JsonRecord& jr = s.h_recs[nrec++];
-    jr.off = dev_offset(r);
-    jr.len = (int32_t)r.arr_len;
-    jr.slot = img;
-    jr.images = r.images;
-    jr.status = 0;
-    jr.tile0 = ntiles;
-    jr.has_cnt = 0;
-    jr.cnt_off = 0;
-    jr.grp0 = 0;
-    if (resident(r) && r.dev_counts) {  // counted by the ingest pass: no counting pass here
-      jr.has_cnt = 1;
-      jr.cnt_off = (int64_t)(r.dev_counts - s.d_bytes);
-    } else {
-      count_pass = true;
-    }
-    ntiles += json_tile_count(jr.off, jr.len);
-    img += r.images;
-  }
-  if (img > exec_->max_batch()) throw std::logic_error("GpuReplica: batch exceeds max_batch");
-  {
-    int64_t res = 0;
-    for (const InRecord& r : b.recs) res += resident(r) ? 1 : 0;
-    resident_ += res;
-    host_ += (int64_t)b.recs.size() - res;
-    preparsed_ += npre;
-  }
-  b.images = img;
-  ensure_tiles(s, ntiles, nrec);
-  for (int i = 0; i < nrec; ++i) {
-    const JsonRecord& jr = s.h_recs[i];
-    const int nt = json_tile_count(jr.off, jr.len);
-    for (int t = 0; t < nt; ++t) s.h_tile_rec[jr.tile0 + t] = i;
-  }
-  if (hoff)
-    check_hip(hipMemcpyAsync(s.d_bytes + staged_dev, s.h_bytes, hoff, hipMemcpyHostToDevice,
-                             stream_),
-              "H2D staged");
-  if (step_graph_) {
-    // ONE launch for the whole step: the captured graph copies the metadata (header included)
-    // and its kernels take the record / tile / image counts from the header
-    s.h_hdr[0] = nrec;
-    s.h_hdr[1] = ntiles;
-    s.h_hdr[2] = img;
-    s.h_hdr[3] = b64n;
-    hipGraphExec_t g = (gpu_encode_ && step_direct_) ? nullptr : step_for(s, slot, count_pass);
-    if (gpu_encode_) {
-      // the metadata this batch uses (header, its records, the input pointer table, its tile
-      // map) as one DMA
-      const size_t rec_bytes = meta_rec_bytes();
-      const size_t used = ntiles > 0 ? kMetaHdr + rec_bytes + sizeof(int) * (size_t)ntiles
-                          : ptr_input_ ? kMetaHdr + rec_bytes
-                          : b64_       ? kMetaHdr + sizeof(B64Image) * (size_t)b64n
-                                       : kMetaHdr + sizeof(JsonRecord) * (size_t)nrec;
-      check_hip(hipMemcpyAsync(s.d_hdr, s.h_hdr, used, hipMemcpyHostToDevice, stream_),
-                "H2D step metadata");
-    }
-    if (g)
-      check_hip(hipGraphLaunch(g, stream_), "hipGraphLaunch(step)");
-    else  // (the same kernels launched directly: no graph-launch bookkeeping in the runtime)
-      check_hip(enqueue_step(s, slot, count_pass, stream_, nrec > 0, ptr_input_), "step launch");
-    b.step_graph = true;
-    ++step_batches_;
-    check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
-    s.t_submit_ns = mono_ns();
-    return;
-  }
-  // (b64: the descriptor table and the status words behind it)
-  const size_t meta = b64_ ? (sizeof(B64Image) + sizeof(int)) * (size_t)exec_->max_batch()
-                           : (size_t)(reinterpret_cast<char*>(s.h_tile_rec + ntiles) -
-                                      reinterpret_cast<char*>(s.h_recs));
-  check_hip(hipMemcpyAsync(s.d_recs, s.h_recs, meta, hipMemcpyHostToDevice, stream_),
-            "H2D recs");
-  if (b64_)
-    check_hip(launch_b64(s, slot, b64n, stream_, nullptr, nullptr), "b64_decode_instances");
-  else
-    check_hip(json_parse_instances(nrec, ntiles, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
-                                   s.d_tiles,
-                                   static_cast<float*>(exec_->input(slot)), stream_, count_pass,
-                                   nullptr, nullptr, nullptr, &prep_),
-              "json_parse_instances");
-  exec_->run(slot, img, stream_, use_graph_);
-  if (use_graph_ && exec_->graph_pays()) ++fwd_graph_batches_;
-  if (gpu_encode_) {
-    // the prediction text (Java Float.toString per value) is formatted on the stream and comes
-    // back instead of the probabilities, so the emitting thread only concatenates slots
-    // (format.hip: ~6 us per 256-image batch). The kernel stores the 16-byte slots straight
-    // into the pinned (device-mapped, coherent) host buffer: no separate D2H copy.
-    check_hip(format_floats_java(img * classes_, static_cast<const float*>(exec_->output(slot)),
-                                 s.h_text, stream_),
-              "format_floats_java");
-  } else {
-    check_hip(hipMemcpyAsync(s.h_out, exec_->output(slot), sizeof(float) * img * classes_,
-                             hipMemcpyDeviceToHost, stream_),
-              "D2H probs");
-  }
-  if (b64_)
-    check_hip(hipMemcpyAsync(b64_status(s.h_recs), b64_status(s.d_recs), sizeof(int) * nrec,
-                             hipMemcpyDeviceToHost, stream_),
-              "D2H status");
-  else
-    check_hip(hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * nrec,
-                             hipMemcpyDeviceToHost, stream_),
-              "D2H status");
   check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
   s.t_submit_ns = mono_ns();
 }
 
-hipError_t GpuReplica::launch_b64(Slot& s, int slot, int images, hipStream_t st,
-                                  const int* d_images, int* status) {
-  return b64_decode_instances(images, b64_table(s.d_recs), s.d_bytes, H_, W_, C_,
-                              static_cast<float*>(exec_->input(slot)),
-                              status ? status : b64_status(s.d_recs), st, d_images, &prep_);
+// The batch's text on the device. Records that arrived in pinned fetch buffers are DMA'd straight
+// from them: one hipMemcpyAsync per fetch buffer covering the records' span (the few Kafka
+// record-header bytes between values ride along); records in pageable memory are first gathered
+// into the slot's pinned staging buffer.
+void GpuReplica::stage_text(const Batch& b, Slot& s) {
+  const BatchPlan& p = s.plan;
+  for (const BatchPlan::Span& x : p.spans)
+    check_hip(hipMemcpyAsync(s.d_bytes + x.dev, reinterpret_cast<const uint8_t*>(x.buf) + x.lo,
+                             x.len, hipMemcpyHostToDevice, stream_),
+              "H2D span");
+  if (!p.staged_bytes) return;
+  for (const BatchPlan::Staged& g : p.staged) {
+    const InRecord& r = b.recs[(size_t)g.rec];
+    memcpy(s.h_bytes + g.host, r.value + r.arr_off, g.len);
+  }
+  check_hip(hipMemcpyAsync(s.d_bytes + p.staged_dev, s.h_bytes, p.staged_bytes,
+                           hipMemcpyHostToDevice, stream_),
+            "H2D staged");
+}
+
+// The planned batch's step: ONE replay of the slot's captured graph, or its sequence enqueued
+// here (step_direct: the same kernels launched directly, no graph-launch bookkeeping in the
+// runtime; without a step graph: op by op).
+void GpuReplica::launch_step(Batch& b, Slot& s, int slot) {
+  const BatchPlan& p = s.plan;
+  const bool captured =
+      form_ == StepForm::Captured || (form_ == StepForm::Kernels && !step_direct_);
+  hipGraphExec_t g = captured ? step_for(s, slot, p.count_pass) : nullptr;
+  if (form_ == StepForm::Kernels) {
+    // the metadata this batch uses (header, its records, the input pointer table, its tile
+    // map) as one DMA ahead of the kernels
+    const MetaRange m = s.meta.used(p);
+    check_hip(hipMemcpyAsync(s.d_meta + m.off, s.h_meta + m.off, m.bytes, hipMemcpyHostToDevice,
+                             stream_),
+              "H2D step metadata");
+  }
+  if (g) {
+    check_hip(hipGraphLaunch(g, stream_), "hipGraphLaunch(step)");
+  } else {
+    const StepError e = emit_step(s, slot, stream_, step_desc(), p.count_pass,
+                                  form_ == StepForm::OpByOp || p.nrec > 0);
+    check_hip(e.code, e.what);
+  }
+  if (form_ == StepForm::OpByOp) {
+    if (use_graph_ && exec_->graph_pays()) ++fwd_graph_batches_;
+  } else {
+    b.step_graph = true;
+    ++step_batches_;
+  }
 }
 
 // Every record of the batch parsed by the ingest pass (into at most kInputTableBases arenas):
@@ -423,8 +311,7 @@ hipError_t GpuReplica::launch_b64(Slot& s, int slot, int images, hipStream_t st,
 // arguments - with no metadata copy (the H2D of a step's metadata ran as a CU blit kernel, ~12 us
 // of device time per batch, profiles/r6_e2e_kernel_stats.txt) and no verdict hand-off (the
 // ingest judged the records).
-template <typename Pre>
-bool GpuReplica::try_table_step(Batch& b, Slot& s, int slot, const Pre& preparsed) {
+bool GpuReplica::table_step(Batch& b, Slot& s, int slot) {
   InputTable tab;
   memset(&tab, 0, sizeof(tab));
   const int64_t per = (int64_t)H_ * W_ * C_;
@@ -443,7 +330,7 @@ bool GpuReplica::try_table_step(Batch& b, Slot& s, int slot, const Pre& preparse
     img += r.images;
   }
   if (img <= 0 || img > exec_->max_batch()) return false;
-  s.parse_idx.assign(b.recs.size(), -1);
+  s.plan.all_preparsed(b.recs.size());
   StepOut so;
   so.text = s.h_text;  // (no status hand-off: status_out null)
   exec_->launch_table(slot, img, tab, stream_, &so);
@@ -453,94 +340,124 @@ bool GpuReplica::try_table_step(Batch& b, Slot& s, int slot, const Pre& preparse
   ++table_batches_;
   preparsed_ += (int64_t)b.recs.size();
   resident_ += (int64_t)b.recs.size();
-  check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
-  s.t_submit_ns = mono_ns();
   return true;
 }
 
-// The kernels-only step (gpu_encode): [count] -> parse -> forward (+ prediction text and
-// verdicts in its epilogue; other plans end with the formatting kernel). The batch's metadata
-// is DMA'd just before (submit(): an SDMA copy of the used part only), and the kernels read the
-// record / tile / image counts from its header. The r4 step captured a metadata H2D and a status
-// D2H as graph nodes, which this runtime runs as CU blit kernels (two per batch, 68 us average
-// under the serving load); reading the metadata from host memory instead stretched every kernel
-// by 25-40 % under the link's DMA load (profiles/r5_step_ab.txt). Captured once per slot into
-// the step graph, or enqueued directly (step_direct).
-hipError_t GpuReplica::enqueue_step(Slot& s, int slot, bool count_pass, hipStream_t st,
-                                     bool parse, bool xs) {
-  const int mb = exec_->max_batch();
-  hipError_t c = hipSuccess;
-  if (parse && b64_)
-    c = launch_b64(s, slot, mb, st, s.d_hdr + 3, s.d_status);
-  else if (parse)  // (a batch of records the ingest already parsed: the forward alone)
-    c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
-                             s.d_tiles, static_cast<float*>(exec_->input(slot)), st, count_pass,
-                             s.d_hdr + 1, s.d_status, nullptr, &prep_);
-  const bool fused = exec_->step_out_ok();
-  StepOut so;
-  so.text = s.h_text;
-  so.status = s.d_status;
-  so.status_out = s.h_status;
-  so.nrec = s.d_hdr;
-  if (c == hipSuccess) {
-    try {
-      exec_->launch_device_batch(slot, s.d_hdr + 2, st, fused ? &so : nullptr,
-                                 xs ? s.d_xs : nullptr);
-    } catch (const std::exception&) {
-      c = hipErrorLaunchFailure;
-    }
-  }
-  if (c == hipSuccess && !fused)
-    c = format_floats_java_step(std::max(mb * classes_, mb), s.d_hdr + 2, classes_,
-                                static_cast<const float*>(exec_->output(slot)), s.h_text,
-                                s.d_hdr, s.d_status, s.h_status, st);
-  return c;
+// The step's sequence, enqueued on `st`: [metadata H2D] -> [count] -> parse -> forward -> output
+// -> [verdicts D2H]; parse false: a batch of records the ingest already parsed, the forward
+// alone. Three sites emit it, each in the replica's form (step_desc):
+//   op by op (no step graph): the counts come from the host (the slot's plan), the forward is
+//     the executor's own run, the text or the probabilities and the verdicts come back by copy;
+//   the captured step without gpu_encode: the same with every launch sized for the largest batch
+//     and the counts read from the metadata header, so one graph per slot serves every batch
+//     (the parse covers tiles_cap tiles and the forward max_batch images, their waves past the
+//     header's counts exit at once; the status copy-back is max_batch records);
+//   the kernels-only step (gpu_encode), captured or launched directly: the batch's metadata is
+//     DMA'd just before (submit(): an SDMA copy of the used part only), the prediction text and
+//     the verdicts leave in the forward's epilogue (other plans end with the formatting kernel).
+//     The r4 step captured a metadata H2D and a status D2H as graph nodes, which this runtime
+//     runs as CU blit kernels (two per batch, 68 us average under the serving load); reading the
+//     metadata from host memory instead stretched every kernel by 25-40 % under the link's DMA
+//     load (profiles/r5_step_ab.txt).
+GpuReplica::StepDesc GpuReplica::step_desc() const {
+  const bool kernels = form_ == StepForm::Kernels;
+  return {form_ != StepForm::OpByOp, !kernels,
+          kernels       ? StepDesc::TextVerdicts
+          : gpu_encode_ ? StepDesc::Text
+                        : StepDesc::Probs,
+          !kernels};
 }
 
-// The slot's step graph, captured on first use (and after its buffers moved). Sized for the
-// largest batch: the parse covers tiles_cap tiles and the forward max_batch images, their waves
-// past the header's counts exit at once; the status copy-back is max_batch records.
+GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, const StepDesc& d,
+                                            bool count_pass, bool parse) {
+  const MetaLayout& L = s.meta;
+  const BatchPlan& p = s.plan;
+  const int mb = exec_->max_batch();
+  const bool dev = d.device_counts;
+  const int32_t* hdr = meta_at<int32_t>(s.d_meta, L.hdr);
+  float* in = static_cast<float*>(exec_->input(slot));
+  const float* out = static_cast<const float*>(exec_->output(slot));
+  int* status = d.out == StepDesc::TextVerdicts ? s.d_status : nullptr;  // (null: in the table)
+  hipError_t c = hipSuccess;
+  if (d.meta_h2d) {
+    const MetaRange m = L.used(p);
+    c = hipMemcpyAsync(s.d_meta + m.off, s.h_meta + m.off, m.bytes, hipMemcpyHostToDevice, st);
+    if (c != hipSuccess) return {c, "H2D step metadata"};
+  }
+  if (parse && b64_) {
+    c = b64_decode_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
+                             s.d_bytes, H_, W_, C_, in,
+                             status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
+                             dev ? hdr + kHdrB64 : nullptr, &prep_);
+    if (c != hipSuccess) return {c, "b64_decode_instances"};
+  } else if (parse) {
+    c = json_parse_instances(dev ? mb : p.nrec, dev ? L.tiles_cap : p.ntiles,
+                             meta_at<JsonRecord>(s.d_meta, L.recs), meta_at<int>(s.d_meta, L.tiles),
+                             s.d_bytes, H_, W_, C_, s.d_tiles, in, st, count_pass,
+                             dev ? hdr + kHdrTiles : nullptr, status, nullptr, &prep_);
+    if (c != hipSuccess) return {c, "json_parse_instances"};
+  }
+  // the forward: the executor's run with the host's count for plans that are not one device
+  // batch, else sized for max_batch with the count read from the header
+  const bool epilogue = d.out == StepDesc::TextVerdicts && exec_->step_out_ok();
+  if (!dev) {
+    exec_->run(slot, p.img, st, use_graph_);
+  } else {
+    StepOut so;
+    so.text = s.h_text;
+    so.status = s.d_status;
+    so.status_out = s.h_status;
+    so.nrec = hdr + kHdrRecords;
+    try {
+      exec_->launch_device_batch(slot, hdr + kHdrImages, st, epilogue ? &so : nullptr,
+                                 ptr_input_ ? meta_at<const float*>(s.d_meta, L.xs) : nullptr);
+    } catch (const std::exception&) {
+      return {hipErrorLaunchFailure, "step forward"};
+    }
+  }
+  const int rows = dev ? mb : p.img;
+  switch (d.out) {
+    case StepDesc::Text:
+      // the prediction text (Java Float.toString per value) is formatted on the stream and
+      // comes back instead of the probabilities, so the emitting thread only concatenates slots
+      // (format.hip: ~6 us per 256-image batch). The kernel stores the 16-byte slots straight
+      // into the pinned (device-mapped, coherent) host buffer: no separate D2H copy.
+      c = format_floats_java(rows * classes_, out, s.h_text, st);
+      if (c != hipSuccess) return {c, "format_floats_java"};
+      break;
+    case StepDesc::TextVerdicts:
+      if (!epilogue)
+        c = format_floats_java_step(std::max(mb * classes_, mb), hdr + kHdrImages, classes_, out,
+                                    s.h_text, hdr + kHdrRecords, s.d_status, s.h_status, st);
+      if (c != hipSuccess) return {c, "format_floats_java_step"};
+      break;
+    case StepDesc::Probs:
+      c = hipMemcpyAsync(s.h_out, out, sizeof(float) * rows * classes_, hipMemcpyDeviceToHost, st);
+      if (c != hipSuccess) return {c, "D2H probs"};
+      break;
+  }
+  if (d.verdict_d2h) {
+    const size_t n = (size_t)(dev ? mb : p.nrec);
+    c = b64_ ? hipMemcpyAsync(s.h_meta + L.b64_status, s.d_meta + L.b64_status, sizeof(int) * n,
+                              hipMemcpyDeviceToHost, st)
+             : hipMemcpyAsync(s.h_meta + L.recs, s.d_meta + L.recs, sizeof(JsonRecord) * n,
+                              hipMemcpyDeviceToHost, st);
+    if (c != hipSuccess) return {c, "D2H status"};
+  }
+  return {hipSuccess, ""};
+}
+
+// The slot's step graph, captured on first use (and after its buffers moved), on a private
+// stream (as Executor::run does) and replayed on the replica's stream.
 hipGraphExec_t GpuReplica::step_for(Slot& s, int slot, bool count_pass) {
   hipGraphExec_t& g = s.step[count_pass ? 1 : 0];
   if (g) return g;
-  const int mb = exec_->max_batch();
-  const size_t meta = kMetaHdr + meta_rec_bytes() + sizeof(int) * s.tiles_cap;
-  // capture on a private stream (as Executor::run does), replayed on the replica's stream
   hipStream_t cs = nullptr;
   check_hip(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking), "capture stream");
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-  if (e == hipSuccess && gpu_encode_) {
-    const hipError_t c = enqueue_step(s, slot, count_pass, cs);
-    e = hipStreamEndCapture(cs, &graph);
-    if (e == hipSuccess) e = c;
-  } else if (e == hipSuccess) {
-    hipError_t c = hipMemcpyAsync(s.d_hdr, s.h_hdr, meta, hipMemcpyHostToDevice, cs);
-    if (c == hipSuccess && b64_)
-      c = launch_b64(s, slot, mb, cs, s.d_hdr + 3, nullptr);
-    else if (c == hipSuccess)
-      c = json_parse_instances(mb, s.tiles_cap, s.d_recs, s.d_tile_rec, s.d_bytes, H_, W_, C_,
-                               s.d_tiles, static_cast<float*>(exec_->input(slot)), cs,
-                               count_pass, s.d_hdr + 1, nullptr, nullptr, &prep_);
-    if (c == hipSuccess) {
-      try {
-        exec_->launch_device_batch(slot, s.d_hdr + 2, cs);
-      } catch (const std::exception&) {
-        c = hipErrorLaunchFailure;
-      }
-    }
-    if (c == hipSuccess)
-      c = gpu_encode_
-              ? format_floats_java_dev(mb * classes_, s.d_hdr + 2, classes_,
-                                       static_cast<const float*>(exec_->output(slot)), s.h_text,
-                                       cs)
-              : hipMemcpyAsync(s.h_out, exec_->output(slot), sizeof(float) * mb * classes_,
-                               hipMemcpyDeviceToHost, cs);
-    if (c == hipSuccess)
-      c = b64_ ? hipMemcpyAsync(b64_status(s.h_recs), b64_status(s.d_recs), sizeof(int) * mb,
-                                hipMemcpyDeviceToHost, cs)
-               : hipMemcpyAsync(s.h_recs, s.d_recs, sizeof(JsonRecord) * mb,
-                                hipMemcpyDeviceToHost, cs);
+  if (e == hipSuccess) {
+    const hipError_t c = emit_step(s, slot, cs, step_desc(), count_pass, true).code;
     e = hipStreamEndCapture(cs, &graph);
     if (e == hipSuccess) e = c;
   }
@@ -577,14 +494,15 @@ void GpuReplica::wait(Batch& b) {
     check_hip(hipEventSynchronize(s.done), "hipEventSynchronize(batch)");
   }
   b.dev_status.assign(b.recs.size(), codec::OK);
-  const bool copy_free = b.step_graph && gpu_encode_;
+  // the verdicts are where the form the batch was submitted in leaves them
+  const int* words = s.plan.form == StepForm::Kernels ? s.h_status
+                     : b64_ ? meta_at<int>(s.h_meta, s.meta.b64_status)
+                            : nullptr;
+  const JsonRecord* recs = meta_at<JsonRecord>(s.h_meta, s.meta.recs);
   for (size_t i = 0; i < b.recs.size(); ++i) {
-    const int k = i < s.parse_idx.size() ? s.parse_idx[i] : (int)i;
+    const int k = i < s.plan.parse_idx.size() ? s.plan.parse_idx[i] : (int)i;
     if (k < 0) continue;  // parsed (and judged) by the ingest pass
-    const int st = copy_free ? s.h_status[k]
-                   : b64_    ? b64_status(s.h_recs)[k]
-                             : s.h_recs[k].status;
-    b.dev_status[i] = device_verdict_status(st);
+    b.dev_status[i] = device_verdict_status(words ? words[k] : recs[k].status);
   }
   b.probs = gpu_encode_ ? nullptr : s.h_out;
   b.pred_text = gpu_encode_ ? s.h_text : nullptr;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../codec/json_codec.h"
+#include "batch_plan.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
 
@@ -152,10 +153,8 @@ class GpuReplica : public Replica {
   // DMA'd from the host-pinned fetch buffer, as it would be across GPUs (--locality-split
   // exercises the multi-GPU dispatch on one device)
   // step_graph: with use_graph and a whole-network plan (Executor::device_batch_ok), each batch
-  // is ONE hipGraphLaunch of the slot's captured step: JSON parse -> forward -> prediction text +
-  // parse verdicts, the kernels reading the batch's record / tile / image counts and records from
-  // the host-mapped metadata (no copy nodes; without gpu_encode: metadata H2D -> parse -> forward
-  // -> probabilities D2H -> status D2H), so one graph per slot serves every batch size
+  // is ONE hipGraphLaunch of the slot's captured step (the sequence and its forms: emit_step in
+  // gpu_replica.cpp), so one graph per slot serves every batch size
   // high_priority: the replica's stream at the device's highest stream priority, so its step
   // kernels are dispatched ahead of the GPU ingest's when both wait for CUs
   GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int classes, bool use_graph,
@@ -188,57 +187,52 @@ class GpuReplica : public Replica {
   void set_input_b64(bool on) { b64_ = on; }
 
  private:
-  // [nrec, ntiles, images, b64 descriptors, ...] ahead of the records
-  static constexpr size_t kMetaHdr = 64;
   struct Slot {
     uint8_t* h_bytes = nullptr;  // pinned staging for records that arrived in pageable memory
     uint8_t* d_bytes = nullptr;  // device copy of the batch's JSON text
     size_t h_cap = 0, d_cap = 0;
-    int32_t* h_hdr = nullptr;      // metadata header (pinned) and its device mirror:
-    int32_t* d_hdr = nullptr;      // [kMetaHdr][records][tile map], one allocation each
-    JsonRecord* h_recs = nullptr;  // [max_batch records][tile -> record map] (pinned)
-    JsonRecord* d_recs = nullptr;  // device mirror
+    // parser metadata: header, records, input pointer table (per batch image its fp32 input on
+    // the device, ptr_input_), tile map, laid out by `meta` (batch_plan.h). Pinned and
+    // host-mapped, and its device mirror
+    uint8_t* h_meta = nullptr;
+    uint8_t* d_meta = nullptr;
+    MetaLayout meta;
     hipGraphExec_t step[2] = {nullptr, nullptr};  // captured steps (without / with count pass)
-    int* h_tile_rec = nullptr;
-    int* d_tile_rec = nullptr;
     int* d_tiles = nullptr;      // per-tile token counts (parser scratch)
-    int tiles_cap = 0;
     float* h_out = nullptr;      // pinned softmax rows
     uint8_t* h_text = nullptr;   // pinned, device-mapped prediction text slots (gpu_encode)
-    // copy-free step graph (gpu_encode): the kernels read the metadata from h_hdr (host-mapped)
-    // and raise verdicts in d_status; the format node hands them to h_status (host-mapped)
+    // the kernels-only step (gpu_encode) raises verdicts in d_status; its last kernel hands
+    // them to h_status (host-mapped)
     int* d_status = nullptr;
     int* h_status = nullptr;
-    // input pointer table (ptr_input_): per batch image, its fp32 input on the device (the
-    // ingest arena, or the slot's input buffer for records parsed in the step), in the metadata
-    // allocation behind the records
-    const float** h_xs = nullptr;
-    const float** d_xs = nullptr;
-    // per batch record: its index among the records the step parses (-1: parsed at ingest)
-    std::vector<int> parse_idx;
-    std::vector<uint32_t> b64_offs;  // (b64 mode) scratch: a record's string offsets
+    // the batch in flight: its records as the plan sees them, their b64 string offsets, and
+    // the plan (its form says where wait() finds the verdicts)
+    std::vector<BatchPlanRecord> recs;
+    std::vector<uint32_t> b64_offs, b64_scan;  // (b64_scan: one record's, scratch)
+    BatchPlan plan;
     hipEvent_t done = nullptr;
     int64_t t_submit_ns = 0;
   };
+  struct StepDesc;   // how the step's sequence is emitted (gpu_replica.cpp)
+  struct StepError;  // what failed in it
   void ensure_host(Slot& s, size_t bytes);
   void ensure_device(Slot& s, size_t bytes);
-  void ensure_tiles(Slot& s, int ntiles, int keep);
+  void ensure_tiles(Slot& s, int ntiles);
   void drop_steps(Slot& s);  // (buffers moved: the captured steps point at the old ones)
-  hipGraphExec_t step_for(Slot& s, int slot, bool count_pass);
-  hipError_t enqueue_step(Slot& s, int slot, bool count_pass, hipStream_t st, bool parse = true,
-                          bool xs = false);
-  template <typename Pre>
-  bool try_table_step(Batch& b, Slot& s, int slot, const Pre& preparsed);
-  size_t meta_rec_bytes() const;  // records + input pointer table of the metadata allocation
-  // b64 mode: the views of the record table's place (see set_input_b64)
-  B64Image* b64_table(JsonRecord* recs) const { return reinterpret_cast<B64Image*>(recs); }
-  int* b64_status(JsonRecord* recs) const {
-    return reinterpret_cast<int*>(b64_table(recs) + exec_->max_batch());
+  // the record's text is in this replica's device memory (GPU ingest, its own locality slot) /
+  // so are its images, already parsed there (the ingest's arena)
+  bool resident(const InRecord& r) const {
+    return r.dev_value != nullptr && r.dev_locality == my_loc_;
   }
-  // the decode launch of a b64 step: `images` images, or with d_images the count read on the
-  // device; status null: the status words behind the descriptor table
-  hipError_t launch_b64(Slot& s, int slot, int images, hipStream_t st, const int* d_images,
-                        int* status);
+  bool preparsed(const InRecord& r) const { return ptr_input_ && resident(r) && r.dev_image; }
+  void describe(const Batch& b, Slot& s);
+  bool table_step(Batch& b, Slot& s, int slot);
+  void stage_text(const Batch& b, Slot& s);
+  void launch_step(Batch& b, Slot& s, int slot);
+  hipGraphExec_t step_for(Slot& s, int slot, bool count_pass);
+  StepDesc step_desc() const;
+  StepError emit_step(Slot& s, int slot, hipStream_t st, const StepDesc& d, bool count_pass,
+                      bool parse);
   static void* mapped_alloc(size_t bytes, const char* what);
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
@@ -256,10 +250,12 @@ class GpuReplica : public Replica {
   std::vector<Slot> slots_;
   int next_slot_ = 0;
   int locality_ = -1;
+  int my_loc_ = -1;  // locality(), fixed at construction
   std::atomic<int64_t> resident_{0}, host_{0};
   std::atomic<int64_t> step_batches_{0}, fwd_graph_batches_{0};
   bool step_graph_ = false;
   bool step_direct_ = false;  // the kernels-only step launched directly, not as a graph replay
+  StepForm form_ = StepForm::OpByOp;  // the form every batch is submitted in (batch_plan.h)
   // batches whose records the GPU ingest already parsed (InRecord::dev_image) run the forward
   // only, reading each image through the slot's input pointer table (direct-launch step of a
   // whole-network plan with the epilogue outputs); records without parse as before
