@@ -226,11 +226,16 @@ PYBIND11_MODULE(_C, m) {
                            relu, P(y), S(stream)),
               "bn_act");
         });
+  // The serving forms (kernels.h) by keyword: d_ntiles non-zero: the tile count is read there on
+  // the device (ntiles = the launch size); status non-zero: the verdicts go to status[record] and
+  // recs / tile_rec are only read; tile_bad non-zero (count_pass false): one plain-stored verdict
+  // per tile. recs[].images < 0 (with has_cnt): the image count comes from the record's group sums
   m.def("json_parse_instances",
         [](int nrec, int ntiles, uintptr_t recs, uintptr_t tile_rec, uintptr_t bytes, int H,
            int W, int C, uintptr_t tile_counts, uintptr_t out, uintptr_t stream,
            bool count_pass, std::optional<std::vector<float>> a,
-           std::optional<std::vector<float>> b, bool nchw) {
+           std::optional<std::vector<float>> b, bool nchw, uintptr_t d_ntiles, uintptr_t status,
+           uintptr_t tile_bad) {
           // a / b (four coefficients each) or nchw: an InputPrep is passed (identity ones too)
           gale::InputPrep prep;
           const bool with_prep = a || b || nchw;
@@ -246,13 +251,17 @@ PYBIND11_MODULE(_C, m) {
                                          static_cast<const uint8_t*>(P(bytes)), H, W, C,
                                          static_cast<int*>(P(tile_counts)),
                                          static_cast<float*>(P(out)), S(stream), count_pass,
-                                         nullptr, nullptr, nullptr, with_prep ? &prep : nullptr),
+                                         static_cast<const int*>(P(d_ntiles)),
+                                         static_cast<int*>(P(status)),
+                                         static_cast<int*>(P(tile_bad)),
+                                         with_prep ? &prep : nullptr),
               "json_parse_instances");
         },
         py::arg("nrec"), py::arg("ntiles"), py::arg("recs"), py::arg("tile_rec"),
         py::arg("bytes"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("tile_counts"),
         py::arg("out"), py::arg("stream"), py::arg("count_pass") = true,
-        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
+        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false,
+        py::arg("d_ntiles") = 0, py::arg("status") = 0, py::arg("tile_bad") = 0);
   m.def("json_tile_count", &gale::json_tile_count);
   m.def("b64_decode_instances",
         [](int images, uintptr_t imgs, uintptr_t bytes, int H, int W, int C, uintptr_t out,
@@ -392,6 +401,32 @@ PYBIND11_MODULE(_C, m) {
                                              reinterpret_cast<hipStream_t>(stream)),
                     "format_floats_java");
   });
+  // the step's forms of the formatter: the value count is (*d_count) * per on the device
+  // (max_n = the launch size); _step also hands the parse verdicts over (kernels.h)
+  m.def("format_floats_java_dev",
+        [](int max_n, uintptr_t d_count, int per, uintptr_t x, uintptr_t out16,
+           uintptr_t stream) {
+          chk(gale::format_floats_java_dev(max_n, static_cast<const int*>(P(d_count)), per,
+                                           static_cast<const float*>(P(x)), P(out16), S(stream)),
+              "format_floats_java_dev");
+        },
+        py::arg("max_n"), py::arg("d_count"), py::arg("per"), py::arg("x"), py::arg("out16"),
+        py::arg("stream"));
+  m.def("format_floats_java_step",
+        [](int max_n, uintptr_t d_count, int per, uintptr_t x, uintptr_t out16, uintptr_t d_nrec,
+           uintptr_t status, uintptr_t status_out, uintptr_t stream) {
+          chk(gale::format_floats_java_step(max_n, static_cast<const int*>(P(d_count)), per,
+                                            static_cast<const float*>(P(x)), P(out16),
+                                            static_cast<const int*>(P(d_nrec)),
+                                            static_cast<int*>(P(status)),
+                                            static_cast<int*>(P(status_out)), S(stream)),
+              "format_floats_java_step");
+        },
+        py::arg("max_n"), py::arg("d_count"), py::arg("per"), py::arg("x"), py::arg("out16"),
+        py::arg("d_nrec"), py::arg("status"), py::arg("status_out"), py::arg("stream"));
+  m.attr("FLOAT_TEXT_SLOT") = gale::kFloatTextSlot;
+  m.attr("INPUT_TABLE_IMAGES") = gale::kInputTableImages;
+  m.attr("INPUT_TABLE_BASES") = gale::kInputTableBases;
   m.def("set_conv_path", &gale::set_conv_path);
   m.def("set_conv_patch", &gale::set_conv_patch);
   m.def("conv_patch_supported", [](py::dict desc, int batch, bool has_res) {
@@ -446,6 +481,43 @@ PYBIND11_MODULE(_C, m) {
              py::gil_scoped_release nogil;
              e.capture_all(S(stream));
            })
+      // the serving forms of the whole-network plans (tests): raw addresses as everywhere else.
+      // A StepOut is passed only when text or status_out is non-zero
+      .def("launch_device_batch",
+           [](gale::Executor& e, int slot, uintptr_t d_batch, uintptr_t stream, uintptr_t text,
+              uintptr_t status, uintptr_t status_out, uintptr_t nrec, uintptr_t xs) {
+             if (status_out && (!status || !nrec))
+               throw py::value_error("launch_device_batch: status_out needs status and nrec");
+             gale::StepOut so;
+             so.text = P(text);
+             so.status = static_cast<int*>(P(status));
+             so.status_out = static_cast<int*>(P(status_out));
+             so.nrec = static_cast<const int*>(P(nrec));
+             py::gil_scoped_release nogil;
+             e.launch_device_batch(slot, static_cast<const int*>(P(d_batch)), S(stream),
+                                   text || status_out ? &so : nullptr,
+                                   static_cast<const float* const*>(P(xs)));
+           },
+           py::arg("slot"), py::arg("d_batch"), py::arg("stream"), py::arg("text") = 0,
+           py::arg("status") = 0, py::arg("status_out") = 0, py::arg("nrec") = 0,
+           py::arg("xs") = 0)
+      .def("launch_table",
+           [](gale::Executor& e, int slot, int batch, std::vector<uintptr_t> bases,
+              std::vector<uint32_t> codes, uintptr_t stream, uintptr_t text) {
+             if (bases.size() > (size_t)gale::kInputTableBases ||
+                 codes.size() > (size_t)gale::kInputTableImages)
+               throw py::value_error("launch_table: too many bases / codes for an InputTable");
+             gale::InputTable tab{};
+             for (size_t i = 0; i < bases.size(); ++i)
+               tab.base[i] = static_cast<const float*>(P(bases[i]));
+             for (size_t i = 0; i < codes.size(); ++i) tab.code[i] = codes[i];
+             gale::StepOut so;
+             so.text = P(text);
+             py::gil_scoped_release nogil;
+             e.launch_table(slot, batch, tab, S(stream), text ? &so : nullptr);
+           },
+           py::arg("slot"), py::arg("batch"), py::arg("bases"), py::arg("codes"),
+           py::arg("stream"), py::arg("text") = 0)
       .def("input_ptr", [](gale::Executor& e, int slot) { return (uintptr_t)e.input(slot); })
       .def("output_ptr", [](gale::Executor& e, int slot) { return (uintptr_t)e.output(slot); })
       .def("bucket_for", &gale::Executor::bucket_for)
