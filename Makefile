@@ -105,6 +105,15 @@ build/asan/batch_plan_check: csrc/tests/batch_plan_check.cpp csrc/runtime/batch_
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/batch_plan_check.cpp csrc/runtime/batch_plan.cpp -o $@
 
+# the two top-k encoders (host selection by the score order rule, slot concatenation) over
+# generated rows (csrc/tests/topk_encode_check.cpp): codec only, no engine
+build/asan/topk_encode_check: csrc/tests/topk_encode_check.cpp csrc/codec/json_codec.cpp \
+                              csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/topk_encode_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500
 

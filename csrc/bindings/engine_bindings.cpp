@@ -44,6 +44,7 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "text_pack_bounce", c.text_pack_bounce);
   opt(d, "text_pack_window_kb", c.text_pack_window_kb);
   opt(d, "float_format", c.float_format);
+  opt(d, "top_k", c.top_k);
   opt(d, "recv_lowat", c.recv_lowat);
   opt(d, "commit_interval_ms", c.commit_interval_ms);
   opt(d, "group_membership", c.group_membership);
@@ -129,7 +130,7 @@ void bind_engine(py::module_& m) {
              auto rep = std::make_shared<GpuReplica>(std::move(exec), c.H, c.W, c.C, c.classes,
                                                      use_graph, wait_poll_us, gpu_encode,
                                                      locality, step_graph, high_priority,
-                                                     step_direct);
+                                                     step_direct, c.top_k);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
              e.add_replica(std::move(rep));

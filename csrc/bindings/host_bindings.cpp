@@ -766,6 +766,34 @@ void bind_host(py::module_& m) {
                                    json_string, out);
     return py::bytes(out);
   }, py::arg("text16"), py::arg("n"), py::arg("classes"), py::arg("json_string") = false);
+  // the top-k output (--top-k, json_codec.h): selected on the host / from a device selection
+  m.def("encode_predictions_topk",
+        [](py::array_t<float, py::array::c_style | py::array::forcecast> p, int k,
+           bool json_string, bool java8) {
+          if (p.ndim() != 2) throw std::invalid_argument("predictions must be [N, classes]");
+          if (k < 1 || k > p.shape(1)) throw std::invalid_argument("need 1 <= k <= classes");
+          std::string out;
+          codec::encode_predictions_topk(p.data(), (int)p.shape(0), (int)p.shape(1), k,
+                                         json_string, out, java8);
+          return py::bytes(out);
+        },
+        py::arg("probs"), py::arg("k"), py::arg("json_string") = false,
+        py::arg("java8") = false);
+  m.def("encode_predictions_topk_text",
+        [](py::bytes text16, py::array_t<int32_t, py::array::c_style | py::array::forcecast> idx,
+           int n, int k, bool json_string) {
+          const std::string t = text16;
+          if (n < 0 || k <= 0 || t.size() != (size_t)n * k * 16 || idx.size() != (ssize_t)n * k)
+            throw std::invalid_argument("need n * k 16-byte slots and n * k indices");
+          for (size_t i = 15; i < t.size(); i += 16)
+            if ((unsigned char)t[i] > 15) throw std::invalid_argument("slot length > 15");
+          std::string out;
+          codec::encode_predictions_topk_text(reinterpret_cast<const uint8_t*>(t.data()),
+                                              idx.data(), n, k, json_string, out);
+          return py::bytes(out);
+        },
+        py::arg("text16"), py::arg("idx"), py::arg("n"), py::arg("k"),
+        py::arg("json_string") = false);
   m.def("encode_instances", [](py::array_t<float, py::array::c_style | py::array::forcecast> x) {
     if (x.ndim() != 4) throw std::invalid_argument("instances must be [N, H, W, C]");
     std::string out;

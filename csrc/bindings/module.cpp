@@ -424,6 +424,41 @@ PYBIND11_MODULE(_C, m) {
         },
         py::arg("max_n"), py::arg("d_count"), py::arg("per"), py::arg("x"), py::arg("out16"),
         py::arg("d_nrec"), py::arg("status"), py::arg("status_out"), py::arg("stream"));
+  // the top-k selection + text kernel (topk.hip) in its three forms, as the formatter's
+  m.def("topk_java",
+        [](int rows, int classes, int k, uintptr_t x, uintptr_t text16, uintptr_t idx,
+           uintptr_t stream) {
+          chk(gale::topk_java(rows, classes, k, static_cast<const float*>(P(x)), P(text16),
+                              static_cast<int32_t*>(P(idx)), S(stream)),
+              "topk_java");
+        },
+        py::arg("rows"), py::arg("classes"), py::arg("k"), py::arg("x"), py::arg("text16"),
+        py::arg("idx"), py::arg("stream"));
+  m.def("topk_java_dev",
+        [](int max_rows, uintptr_t d_rows, int classes, int k, uintptr_t x, uintptr_t text16,
+           uintptr_t idx, uintptr_t stream) {
+          chk(gale::topk_java_dev(max_rows, static_cast<const int*>(P(d_rows)), classes, k,
+                                  static_cast<const float*>(P(x)), P(text16),
+                                  static_cast<int32_t*>(P(idx)), S(stream)),
+              "topk_java_dev");
+        },
+        py::arg("max_rows"), py::arg("d_rows"), py::arg("classes"), py::arg("k"), py::arg("x"),
+        py::arg("text16"), py::arg("idx"), py::arg("stream"));
+  m.def("topk_java_step",
+        [](int max_rows, uintptr_t d_rows, int classes, int k, uintptr_t x, uintptr_t text16,
+           uintptr_t idx, uintptr_t d_nrec, uintptr_t status, uintptr_t status_out,
+           uintptr_t stream) {
+          chk(gale::topk_java_step(max_rows, static_cast<const int*>(P(d_rows)), classes, k,
+                                   static_cast<const float*>(P(x)), P(text16),
+                                   static_cast<int32_t*>(P(idx)),
+                                   static_cast<const int*>(P(d_nrec)),
+                                   static_cast<int*>(P(status)),
+                                   static_cast<int*>(P(status_out)), S(stream)),
+              "topk_java_step");
+        },
+        py::arg("max_rows"), py::arg("d_rows"), py::arg("classes"), py::arg("k"), py::arg("x"),
+        py::arg("text16"), py::arg("idx"), py::arg("d_nrec"), py::arg("status"),
+        py::arg("status_out"), py::arg("stream"));
   m.attr("FLOAT_TEXT_SLOT") = gale::kFloatTextSlot;
   m.attr("INPUT_TABLE_IMAGES") = gale::kInputTableImages;
   m.attr("INPUT_TABLE_BASES") = gale::kInputTableBases;

@@ -622,6 +622,79 @@ void encode_predictions_text(const uint8_t* text16, int n, int classes, bool jso
   if (json_string) out.push_back('"');
 }
 
+namespace {
+
+// the top-k document around per-image (classes, scores) lists; cls(i, j) appends entry j's class
+// of image i, score(i, j) its score text
+template <typename Cls, typename Score>
+void encode_topk(int n, int k, bool json_string, std::string& out, Cls cls, Score score) {
+  out.clear();
+  out.reserve((size_t)n * ((size_t)k * 18 + 32) + 32);
+  const char* q = json_string ? "\\\"" : "\"";
+  if (json_string) out.push_back('"');
+  out.push_back('{');
+  out.append(q).append("predictions").append(q).append(":[");
+  for (int i = 0; i < n; ++i) {
+    if (i) out.push_back(',');
+    out.push_back('{');
+    out.append(q).append("classes").append(q).append(":[");
+    for (int j = 0; j < k; ++j) {
+      if (j) out.push_back(',');
+      cls(i, j);
+    }
+    out.append("],").append(q).append("scores").append(q).append(":[");
+    for (int j = 0; j < k; ++j) {
+      if (j) out.push_back(',');
+      score(i, j);
+    }
+    out.append("]}");
+  }
+  out.append("]}");
+  if (json_string) out.push_back('"');
+}
+
+void append_int(std::string& out, int32_t v) {
+  char buf[16];
+  out.append(buf, std::to_chars(buf, buf + sizeof(buf), v).ptr);
+}
+
+}  // namespace
+
+void encode_predictions_topk(const float* probs, int n, int classes, int k, bool json_string,
+                             std::string& out, bool java8) {
+  k = std::max(0, std::min(k, classes));
+  // per image: (key, index) of every class, the k best in front
+  std::vector<std::pair<uint32_t, int32_t>> sel((size_t)std::max(classes, 0));
+  std::vector<int32_t> best((size_t)std::max(n, 0) * (size_t)k);
+  for (int i = 0; i < n; ++i) {
+    const float* row = probs + (size_t)i * classes;
+    for (int c = 0; c < classes; ++c) sel[(size_t)c] = {score_key(row[c]), c};
+    std::partial_sort(sel.begin(), sel.begin() + k, sel.end(),
+                      [](const std::pair<uint32_t, int32_t>& a,
+                         const std::pair<uint32_t, int32_t>& b) {
+                        return a.first != b.first ? a.first > b.first : a.second < b.second;
+                      });
+    for (int j = 0; j < k; ++j) best[(size_t)i * k + j] = sel[(size_t)j].second;
+  }
+  char buf[32];
+  encode_topk(
+      n, k, json_string, out, [&](int i, int j) { append_int(out, best[(size_t)i * k + j]); },
+      [&](int i, int j) {
+        const float v = probs[(size_t)i * classes + best[(size_t)i * k + j]];
+        out.append(buf, java8 ? format_float_java8(v, buf) : format_float_java(v, buf));
+      });
+}
+
+void encode_predictions_topk_text(const uint8_t* text16, const int32_t* idx, int n, int k,
+                                  bool json_string, std::string& out) {
+  encode_topk(
+      n, k, json_string, out, [&](int i, int j) { append_int(out, idx[(size_t)i * k + j]); },
+      [&](int i, int j) {
+        const uint8_t* t = text16 + ((size_t)i * k + j) * 16;
+        out.append(reinterpret_cast<const char*>(t), t[15] & 15);
+      });
+}
+
 void encode_instances(const float* x, int n, int H, int W, int C, std::string& out) {
   out.clear();
   out.reserve((size_t)n * H * W * C * 12 + 32);

@@ -134,6 +134,29 @@ void encode_predictions(const float* probs, int n, int classes, bool json_string
 void encode_predictions_text(const uint8_t* text16, int n, int classes, bool json_string,
                              std::string& out);
 
+// ---- top-k output (--top-k K) -------------------------------------------------------------------
+//     {"predictions":[{"classes":[3,5,1],"scores":[0.9123,0.05,0.0101]},{...}]}
+// One element per image, in image order: the K best classes (0-based) and their scores (the same
+// Float.toString text as the full rows), in score order.
+//
+// Score order. It is defined on the bits, so host and device cannot differ:
+//     key(v) = bits(v) ^ (bits(v) >> 31 ? 0xffffffff : 0x80000000), compared as unsigned;
+// entry j of an image is its j-th largest (key, -index): descending by score, ties to the lower
+// class index. So -0 sorts below +0 and a positive NaN above +Infinity. The device selection
+// (csrc/kernels/topk.hip) implements this rule and refers here.
+inline uint32_t score_key(float v) {
+  uint32_t b;
+  __builtin_memcpy(&b, &v, 4);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+// Selects on the host (std::partial_sort on (key, index)) and formats; 1 <= k <= classes.
+void encode_predictions_topk(const float* probs, int n, int classes, int k, bool json_string,
+                             std::string& out, bool java8 = false);
+// Same output from a device selection: text16 holds n * k score slots (format as
+// encode_predictions_text's), idx the n * k class indices, entry (i, j) at i * k + j.
+void encode_predictions_topk_text(const uint8_t* text16, const int32_t* idx, int n, int k,
+                                  bool json_string, std::string& out);
+
 // {"instances":[[[[x,...]]]]} with Java Float.toString numbers: the load generator's encoder
 // (the reference's producers are external; this is the shape README.md:22-27 documents).
 void encode_instances(const float* x, int n, int H, int W, int C, std::string& out);

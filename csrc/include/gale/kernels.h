@@ -393,4 +393,23 @@ hipError_t format_floats_java_step(int max_n, const int* d_count, int per, const
                                    void* out16, const int* d_nrec, int* status, int* status_out,
                                    hipStream_t stream);
 
+// ---- top-k prediction output (topk.hip) -----------------------------------------------------
+// Of each row of x (fp32 [rows][classes], device memory) the k best classes in score order
+// (codec/json_codec.h "Score order": descending by the order-preserving key of the bits, ties to
+// the lower class): entry (r, j) goes to slot r * k + j of text16 (kFloatTextSlot bytes, the
+// value's text as format_floats_java writes it) and of idx (the 0-based class). text16 and idx
+// may be host-mapped pinned memory. hipErrorInvalidValue, before any launch, for k < 1, k > 64,
+// k > classes or classes > 4096. One wave per row, so the launch has 64 threads per row.
+hipError_t topk_java(int rows, int classes, int k, const float* x, void* text16, int32_t* idx,
+                     hipStream_t stream);
+// rows = min(*d_rows, max_rows) read on the device (max_rows: the launch size); waves of later
+// rows exit before touching memory: the step graph's form
+hipError_t topk_java_dev(int max_rows, const int* d_rows, int classes, int k, const float* x,
+                         void* text16, int32_t* idx, hipStream_t stream);
+// topk_java_dev with format_floats_java_step's verdict hand-off by the launch's first threads
+// (status_out[i] = status[i], status[i] = 0 for i < *d_nrec); *d_nrec <= 64 * max_rows
+hipError_t topk_java_step(int max_rows, const int* d_rows, int classes, int k, const float* x,
+                          void* text16, int32_t* idx, const int* d_nrec, int* status,
+                          int* status_out, hipStream_t stream);
+
 }  // namespace gale

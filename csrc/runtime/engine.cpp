@@ -183,6 +183,9 @@ Engine::Engine(EngineConfig cfg) : cfg_(std::move(cfg)), rng_(cfg_.seed) {
                                 "(sink_mode async or sync)");
   if (cfg_.max_batch <= 0 || cfg_.source_parallelism <= 0 || cfg_.sink_parallelism <= 0)
     throw std::invalid_argument("engine: max_batch / parallelism must be positive");
+  if (cfg_.top_k < 0 || cfg_.top_k > std::min(cfg_.classes, 64))
+    throw std::invalid_argument("engine: top_k must be 0 (off) or 1 .. min(classes, 64) = " +
+                                std::to_string(std::min(cfg_.classes, 64)));
   // fault injection spec: comma separated kind@value
   std::stringstream ss(cfg_.fault);
   std::string item;
@@ -1376,8 +1379,16 @@ void Engine::finish_batch(ReplicaSlot* rs, Batch& b) {
   kafka::Producer* prod = producer_for(rs->index);
   const bool js = cfg_.value_format == "json-string";
   const bool java8 = cfg_.float_format == "java8";
+  const int topk = cfg_.top_k;
   auto encode_ok = [&](const InRecord& r, int img, std::string& out, bool jstr) {
-    if (b.pred_text)
+    if (topk > 0 && b.pred_text && b.pred_idx)  // selected and formatted on the device
+      codec::encode_predictions_topk_text(b.pred_text + (size_t)img * topk * 16,
+                                          b.pred_idx + (size_t)img * topk, r.images, topk, jstr,
+                                          out);
+    else if (topk > 0)  // (a replica that returns the rows: the host selects, same order rule)
+      codec::encode_predictions_topk(b.probs + (size_t)img * cfg_.classes, r.images,
+                                     cfg_.classes, topk, jstr, out, java8);
+    else if (b.pred_text)
       codec::encode_predictions_text(b.pred_text + (size_t)img * cfg_.classes * 16, r.images,
                                      cfg_.classes, jstr, out);
     else
@@ -1393,7 +1404,10 @@ void Engine::finish_batch(ReplicaSlot* rs, Batch& b) {
   kafka::RecordGroup g;
   g.off.reserve(b.recs.size() + 1);
   g.off.push_back(0);
-  g.values.reserve(b.recs.size() * (size_t)(cfg_.classes * 13 + 24));
+  // (per record: ~13 bytes per full-row value; a top-k image is k (score, class) pairs of up
+  // to 18 bytes and its two keys)
+  g.values.reserve(topk > 0 ? b.recs.size() * 24 + (size_t)b.images * ((size_t)topk * 18 + 32)
+                            : b.recs.size() * (size_t)(cfg_.classes * 13 + 24));
   const bool keyed = cfg_.output_key == "input";
   if (keyed) g.koff.push_back(0);
   if (cfg_.type_id_header) g.headers.push_back({"__TypeId__", "java.lang.String", false});
@@ -1405,8 +1419,12 @@ void Engine::finish_batch(ReplicaSlot* rs, Batch& b) {
     if (r.split) {  // a fragment of an oversized record: its rows join the others'
       std::string rows;
       if (r.status == codec::OK) {
-        encode_ok(r, img, out, false);
-        rows.assign(out, 16, out.size() - 18);  // {"predictions":[ rows ]}
+        // the fragment in the record's value format, so that what its rows hold (the top-k
+        // elements' quotes) is escaped as the joined record needs it; the envelope is cut off:
+        // {"predictions":[ rows ]}, or "{\"predictions\":[ rows ]}" as a JSON string
+        encode_ok(r, img, out, js);
+        const size_t head = js ? 19 : 16, tail = js ? 3 : 2;
+        rows.assign(out, head, out.size() - head - tail);
       }
       fragment_done(r, std::move(rows), r.status, prod);
       img += r.images;

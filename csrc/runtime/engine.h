@@ -121,6 +121,9 @@ struct EngineConfig {
   // prediction digits: "jdk19" (shortest, also on the GPU) | "java8" (the reference runtime's
   // Float.toString, host-formatted; codec::format_float_java8)
   std::string float_format = "jdk19";
+  // > 0: each image's output is its top_k best classes and their scores in score order
+  // (codec/json_codec.h) instead of the whole softmax row; 1 <= top_k <= min(classes, 64)
+  int top_k = 0;
   bool type_id_header = false;     // __TypeId__: java.lang.String header (E8)
   std::string on_error = "null";   // null | error-json | drop
   // output record key: "none" = unkeyed (the reference, E9: FieldNameBasedTupleToKafkaMapper

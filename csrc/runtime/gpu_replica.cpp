@@ -48,10 +48,14 @@ struct GpuReplica::StepError {
 
 GpuReplica::GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int classes,
                        bool use_graph, int wait_poll_us, bool gpu_encode, int locality,
-                       bool step_graph, bool high_priority, bool step_direct)
+                       bool step_graph, bool high_priority, bool step_direct, int top_k)
     : exec_(std::move(exec)), H_(H), W_(W), C_(C), classes_(classes), use_graph_(use_graph),
-      wait_poll_us_(wait_poll_us), gpu_encode_(gpu_encode), locality_(locality),
-      step_direct_(step_direct) {
+      wait_poll_us_(wait_poll_us), gpu_encode_(gpu_encode), top_k_(gpu_encode ? top_k : 0),
+      locality_(locality), step_direct_(step_direct) {
+  // (the selection kernel's limits, topk.hip; the engine's configuration is checked before)
+  if (top_k_ < 0 || top_k_ > std::min(classes, 64) || (top_k_ > 0 && classes > 4096))
+    throw std::invalid_argument("GpuReplica: top_k must be 1 .. min(classes, 64), classes <= "
+                                "4096");
   step_graph_ = step_graph && use_graph && exec_->device_batch_ok();
   ptr_input_ = step_graph_ && gpu_encode_ && step_direct_ && exec_->step_out_ok();
   my_loc_ = this->locality();
@@ -85,9 +89,13 @@ GpuReplica::GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int 
     check_hip(hipHostMalloc(reinterpret_cast<void**>(&s.h_out), sizeof(float) * mb * classes),
               "hipHostMalloc(out)");
     if (gpu_encode_) {
-      const size_t tb = (size_t)kFloatTextSlot * mb * classes;
-      check_hip(hipHostMalloc(reinterpret_cast<void**>(&s.h_text), tb, hipHostMallocMapped),
+      // top_k: k slots per image and, behind them in the same allocation, k class indices
+      const size_t per = top_k_ > 0 ? (size_t)top_k_ : (size_t)classes;
+      const size_t tb = (size_t)kFloatTextSlot * mb * per;
+      const size_t ib = top_k_ > 0 ? sizeof(int32_t) * mb * per : 0;
+      check_hip(hipHostMalloc(reinterpret_cast<void**>(&s.h_text), tb + ib, hipHostMallocMapped),
                 "hipHostMalloc(text)");
+      if (top_k_ > 0) s.h_idx = reinterpret_cast<int32_t*>(s.h_text + tb);
       check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_status), sizeof(int) * mb),
                 "hipMalloc(status)");
       check_hip(hipMemset(s.d_status, 0, sizeof(int) * mb), "hipMemset(status)");
@@ -310,7 +318,8 @@ void GpuReplica::launch_step(Batch& b, Slot& s, int slot) {
 // the step is ONE launch - the forward, each image addressed through an InputTable in its kernel
 // arguments - with no metadata copy (the H2D of a step's metadata ran as a CU blit kernel, ~12 us
 // of device time per batch, profiles/r6_e2e_kernel_stats.txt) and no verdict hand-off (the
-// ingest judged the records).
+// ingest judged the records). With top_k the forward writes no text and the selection kernel
+// follows it: two launches.
 bool GpuReplica::table_step(Batch& b, Slot& s, int slot) {
   InputTable tab;
   memset(&tab, 0, sizeof(tab));
@@ -332,8 +341,12 @@ bool GpuReplica::table_step(Batch& b, Slot& s, int slot) {
   if (img <= 0 || img > exec_->max_batch()) return false;
   s.plan.all_preparsed(b.recs.size());
   StepOut so;
-  so.text = s.h_text;  // (no status hand-off: status_out null)
+  so.text = top_k_ > 0 ? nullptr : s.h_text;  // (no status hand-off: status_out null)
   exec_->launch_table(slot, img, tab, stream_, &so);
+  if (top_k_ > 0)  // a second launch: the selection reads the rows the forward left on the device
+    check_hip(topk_java(img, classes_, top_k_, static_cast<const float*>(exec_->output(slot)),
+                        s.h_text, s.h_idx, stream_),
+              "topk_java");
   b.images = img;
   b.step_graph = true;
   ++step_batches_;
@@ -404,7 +417,7 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
     exec_->run(slot, p.img, st, use_graph_);
   } else {
     StepOut so;
-    so.text = s.h_text;
+    so.text = top_k_ > 0 ? nullptr : s.h_text;  // (top_k: the selection launch below writes it)
     so.status = s.d_status;
     so.status_out = s.h_status;
     so.nrec = hdr + kHdrRecords;
@@ -422,10 +435,24 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
       // comes back instead of the probabilities, so the emitting thread only concatenates slots
       // (format.hip: ~6 us per 256-image batch). The kernel stores the 16-byte slots straight
       // into the pinned (device-mapped, coherent) host buffer: no separate D2H copy.
-      c = format_floats_java(rows * classes_, out, s.h_text, st);
-      if (c != hipSuccess) return {c, "format_floats_java"};
+      // With top_k the selection kernel (topk.hip) stands in its place: k slots and k class
+      // indices per row.
+      c = top_k_ > 0 ? topk_java(rows, classes_, top_k_, out, s.h_text, s.h_idx, st)
+                     : format_floats_java(rows * classes_, out, s.h_text, st);
+      if (c != hipSuccess) return {c, top_k_ > 0 ? "topk_java" : "format_floats_java"};
       break;
     case StepDesc::TextVerdicts:
+      if (top_k_ > 0) {
+        // the epilogue handed the verdicts over and wrote no text: the selection follows it with
+        // the header's image count; other plans end with the selection's step form (its launch
+        // has 64 threads per row of max_batch, enough for max_batch verdicts)
+        c = epilogue ? topk_java_dev(mb, hdr + kHdrImages, classes_, top_k_, out, s.h_text,
+                                     s.h_idx, st)
+                     : topk_java_step(mb, hdr + kHdrImages, classes_, top_k_, out, s.h_text,
+                                      s.h_idx, hdr + kHdrRecords, s.d_status, s.h_status, st);
+        if (c != hipSuccess) return {c, epilogue ? "topk_java_dev" : "topk_java_step"};
+        break;
+      }
       if (!epilogue)
         c = format_floats_java_step(std::max(mb * classes_, mb), hdr + kHdrImages, classes_, out,
                                     s.h_text, hdr + kHdrRecords, s.d_status, s.h_status, st);
@@ -506,6 +533,7 @@ void GpuReplica::wait(Batch& b) {
   }
   b.probs = gpu_encode_ ? nullptr : s.h_out;
   b.pred_text = gpu_encode_ ? s.h_text : nullptr;
+  b.pred_idx = gpu_encode_ && top_k_ > 0 ? s.h_idx : nullptr;
 }
 
 void GpuReplica::recover() {

@@ -75,6 +75,9 @@ struct Batch {
   // [images, classes] Java Float.toString slots (kFloatTextSlot bytes each) when the replica
   // formats on the device (GpuReplica gpu_encode), else null: the engine formats `probs`
   const uint8_t* pred_text = nullptr;
+  // top-k output selected on the device (GpuReplica gpu_encode with top_k): pred_text then holds
+  // [images, k] score slots and pred_idx the [images, k] class indices; else null
+  const int32_t* pred_idx = nullptr;
   std::vector<int32_t> dev_status;  // per-record codec::Status found by the replica's parser
   int64_t t_take_ns = 0, t_submit_ns = 0, t_done_ns = 0;
   bool step_graph = false;  // (GpuReplica) submitted as one replay of the slot's step graph
@@ -157,9 +160,15 @@ class GpuReplica : public Replica {
   // gpu_replica.cpp), so one graph per slot serves every batch size
   // high_priority: the replica's stream at the device's highest stream priority, so its step
   // kernels are dispatched ahead of the GPU ingest's when both wait for CUs
+  // top_k > 0 (EngineConfig::top_k) with gpu_encode: the step ends with the selection kernel
+  // (topk.hip) where it formatted the whole rows: k score slots and k class indices per image
+  // come back instead of `classes` slots (whole-network plans keep the verdict hand-off in the
+  // forward's epilogue and leave its text out). Without gpu_encode the probabilities come back
+  // as ever and the engine selects
   GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int classes, bool use_graph,
              int wait_poll_us = 0, bool gpu_encode = false, int locality = -1,
-             bool step_graph = true, bool high_priority = false, bool step_direct = false);
+             bool step_graph = true, bool high_priority = false, bool step_direct = false,
+             int top_k = 0);
   ~GpuReplica() override;
   std::string name() const override;
   int max_images() const override { return exec_->max_batch(); }
@@ -201,6 +210,7 @@ class GpuReplica : public Replica {
     int* d_tiles = nullptr;      // per-tile token counts (parser scratch)
     float* h_out = nullptr;      // pinned softmax rows
     uint8_t* h_text = nullptr;   // pinned, device-mapped prediction text slots (gpu_encode)
+    int32_t* h_idx = nullptr;    // top_k: the class indices, behind the k slots per image in h_text
     // the kernels-only step (gpu_encode) raises verdicts in d_status; its last kernel hands
     // them to h_status (host-mapped)
     int* d_status = nullptr;
@@ -241,6 +251,7 @@ class GpuReplica : public Replica {
   bool use_graph_;
   int wait_poll_us_ = 0;
   bool gpu_encode_ = false;
+  int top_k_ = 0;  // > 0 with gpu_encode_: the device selects (else 0, whatever the engine's is)
   // H2D of the batch's metadata (and of any text not already resident) + parse + forward + D2H,
   // in order on ONE stream: with GPU ingest the text is resident, so a separate copy stream
   // bought no overlap, and its cross-stream wait (hipStreamWaitEvent) was where rocprofv3's

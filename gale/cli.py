@@ -36,7 +36,7 @@ import time
 from dataclasses import fields
 from typing import List, Optional
 
-from gale.config import CHOICES, GaleConfig, from_sources
+from gale.config import CHOICES, HELP, GaleConfig, from_sources
 
 SUBCOMMANDS = ("kill", "list", "broker", "produce", "consume")
 
@@ -62,6 +62,10 @@ def _topology_parser() -> argparse.ArgumentParser:
             kw = dict(default=None, type={"int": int, "float": float}.get(t, str))
             if f.name in CHOICES:
                 kw["choices"] = CHOICES[f.name]
+            if f.name in HELP:
+                kw["help"] = HELP[f.name]
+            if f.name == "top_k":
+                kw["metavar"] = "K"
             ap.add_argument(flag, **kw)
     return ap
 

@@ -42,6 +42,15 @@ CHOICES = {
     "input_format": ("json", "b64"),
 }
 
+TOP_K_MAX = 64  # --top-k: one winner per lane of the selection kernel's wave
+
+# --help text of options that need more than their name
+HELP = {
+    "top_k": "K > 0: each image's output is {\"classes\": [...], \"scores\": [...]} of its K best "
+             "classes, descending by score (ties to the lower class), instead of the whole "
+             "softmax row; 1 <= K <= min(classes, 64); 0 = off (default)",
+}
+
 
 @dataclass
 class GaleConfig:
@@ -133,6 +142,10 @@ class GaleConfig:
     float_format: str = "jdk19"        # prediction digits: jdk19 = shortest round-trip (GPU
                                        # formatted); java8 = the reference runtime's
                                        # Float.toString (host formatted, csrc/codec/java8_float.cpp)
+    top_k: int = 0                     # > 0: each image's output is {"classes": [...], "scores":
+                                       # [...]} of its K best classes in score order instead of
+                                       # the whole softmax row; 1 <= K <= min(classes, 64)
+                                       # (selected on the GPU with gpu_encode: topk.hip)
     producer_buffer_mb: int = 32       # unsent output bytes per sink producer before the sink
                                        # blocks (Kafka buffer.memory, 32 MB default)
     producer_request_kb: int = 1024    # bytes per produce request (Kafka max.request.size)
@@ -249,6 +262,14 @@ class GaleConfig:
         if self.b64_ingest and self.input_format != "b64":
             raise ValueError("--b64-ingest needs --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
+        if self.top_k != 0:
+            from gale.models import get_model
+
+            classes = get_model(self.model).classes
+            if not 1 <= self.top_k <= min(classes, TOP_K_MAX):
+                raise ValueError(f"--top-k {self.top_k}: expected 0 (off) or 1 <= K <= "
+                                 f"{min(classes, TOP_K_MAX)} (the smaller of {self.model}'s "
+                                 f"{classes} classes and {TOP_K_MAX})")
         return self
 
     def input_prep(self, C: Optional[int] = None):
@@ -302,7 +323,7 @@ class GaleConfig:
             compression=self.compression,
             value_format=self.value_format, type_id_header=self.type_id_header,
             on_error=self.on_error, output_key=self.output_key, float_format=self.float_format,
-            output_partition=self.output_partition,
+            top_k=self.top_k, output_partition=self.output_partition,
             producer_buffer_bytes=self.producer_buffer_mb << 20,
             producer_request_bytes=self.producer_request_kb << 10, H=H, W=W, C=C, classes=classes,
             max_batch=self.max_batch,

@@ -157,6 +157,26 @@ def softmax(x: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
     return out
 
 
+def topk(x: torch.Tensor, k: int):
+    """The ``k`` best classes of each row of x (fp32 [rows, classes]) in score order (descending
+    by the bits' order-preserving key, ties to the lower class; csrc/codec/json_codec.h), selected
+    and formatted by the top-k kernel (csrc/kernels/topk.hip).
+
+    Returns ``(texts, indices)``: uint8 [rows, k, FLOAT_TEXT_SLOT] Java ``Float.toString`` slots
+    (characters from byte 0, length in byte 15) and int32 [rows, k] class indices."""
+    _check(x, torch.float32, "x")
+    if x.dim() != 2:
+        raise ValueError("gale op: x must be [rows, classes]")
+    rows, classes = x.shape
+    if not 1 <= k <= min(classes, 64) or classes > 4096:
+        raise ValueError("gale op: topk needs 1 <= k <= min(classes, 64) and classes <= 4096")
+    texts = torch.empty(rows, k, native().FLOAT_TEXT_SLOT, device=x.device, dtype=torch.uint8)
+    indices = torch.empty(rows, k, device=x.device, dtype=torch.int32)
+    native().topk_java(rows, classes, k, x.data_ptr(), texts.data_ptr(), indices.data_ptr(),
+                       _stream())
+    return texts, indices
+
+
 def batchnorm(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
               relu: bool = False, residual: Optional[torch.Tensor] = None,
               res_mode: str = "identity", out: Optional[torch.Tensor] = None) -> torch.Tensor:
