@@ -48,7 +48,7 @@ clean:
 # linked; GPU sanitizers are not available on this pool).
 SAN_SRC   := csrc/tests/engine_stress.cpp csrc/runtime/engine.cpp csrc/runtime/replica.cpp \
              csrc/runtime/pinned_pool.cpp csrc/runtime/trace.cpp csrc/codec/json_codec.cpp \
-             csrc/codec/text_pack.cpp csrc/codec/java8_float.cpp \
+             csrc/codec/text_pack.cpp csrc/codec/java8_float.cpp csrc/codec/resize.cpp \
              $(wildcard csrc/kafka/*.cpp)
 SAN_FLAGS := -O1 -g -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include \
              -Icsrc/include -mavx2 -mfma -msse4.2 -mpclmul -mbmi2 -pthread
@@ -113,6 +113,14 @@ build/asan/topk_encode_check: csrc/tests/topk_encode_check.cpp csrc/codec/json_c
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/topk_encode_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# the input resize's table builder and host twin (csrc/tests/resize_check.cpp): every
+# (source, resize, model) size of 1..24 per axis and the 4096 extremes; codec only, no HIP call
+build/asan/resize_check: csrc/tests/resize_check.cpp csrc/codec/resize.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/resize_check.cpp csrc/codec/resize.cpp -o $@
 
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500

@@ -73,6 +73,11 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "W", c.W);
   opt(d, "C", c.C);
   opt(d, "classes", c.classes);
+  // input resize (gale/models/preprocess.py InputResize.engine_entries; absent = off)
+  opt(d, "rec_H", c.rec_H);
+  opt(d, "rec_W", c.rec_W);
+  opt(d, "resize_H", c.resize_H);
+  opt(d, "resize_W", c.resize_W);
   // input preprocessing (gale/models/preprocess.py InputPrep.engine_entries)
   std::vector<float> pa, pb;
   bool nchw = false;
@@ -103,7 +108,19 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "trace", c.trace);
   opt(d, "max_records", c.max_records);
   opt(d, "seed", c.seed);
+  if (c.resize_active()) {
+    codec::ResizeTables t;  // (std::invalid_argument on dimensions no table is built for)
+    codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
+    // the ingest's image arena and the table step address model-size images
+    c.ingest_parse = false;
+  }
   return c;
+}
+
+codec::ResizeTables resize_tables(const EngineConfig& c) {
+  codec::ResizeTables t;
+  codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
+  return t;
 }
 
 }  // namespace
@@ -118,6 +135,7 @@ void bind_engine(py::module_& m) {
                                                       delay_us, compute, locality);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
+             if (c.resize_active()) rep->set_input_resize(resize_tables(c));
              e.add_replica(std::move(rep));
            },
            py::arg("max_images") = 256, py::arg("delay_us") = 0, py::arg("compute") = true,
@@ -133,6 +151,7 @@ void bind_engine(py::module_& m) {
                                                      step_direct, c.top_k);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
+             if (c.resize_active()) rep->set_input_resize(resize_tables(c));
              e.add_replica(std::move(rep));
            },
            py::arg("executor"), py::arg("use_graph") = true, py::arg("wait_poll_us") = 0,

@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "../codec/json_codec.h"
+#include "../codec/resize.h"
 #include "gale/llc_pair.h"
 #include "../codec/text_pack.h"
 #include "../kafka/broker.h"
@@ -676,6 +677,32 @@ void bind_host(py::module_& m) {
         },
         py::arg("x"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("nchw"), py::arg("a"),
         py::arg("b"));
+  // ---- input resize (codec/resize.h): the table builder and the host twin of resize_crop ----
+  m.def("build_resize_tables",
+        [](int HS, int WS, int HR, int WR, int H, int W) {
+          codec::ResizeTables t;
+          codec::build_resize_tables(HS, WS, HR, WR, H, W, t);
+          auto ia = [](const std::vector<int32_t>& v) {
+            return py::array_t<int32_t>((py::ssize_t)v.size(), v.data());
+          };
+          auto fa = [](const std::vector<float>& v) {
+            return py::array_t<float>((py::ssize_t)v.size(), v.data());
+          };
+          return py::make_tuple(ia(t.y0), ia(t.y1), fa(t.wy), ia(t.x0), ia(t.x1), fa(t.wx));
+        },
+        py::arg("HS"), py::arg("WS"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
+  m.def("resize_crop_host",
+        [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int HR, int WR, int H,
+           int W) {
+          if (x.ndim() != 4) throw std::invalid_argument("resize_crop_host: x must be [N, HS, WS, C]");
+          codec::ResizeTables t;
+          codec::build_resize_tables((int)x.shape(1), (int)x.shape(2), HR, WR, H, W, t);
+          const int C = (int)x.shape(3);
+          py::array_t<float> out({x.shape(0), (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
+          codec::resize_crop_host(x.data(), (int)x.shape(0), C, t, out.mutable_data());
+          return out;
+        },
+        py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
   // ---- nibble transport (text_pack.h) ----
   m.def("text_pack_fast", &codec::text_pack_fast);
   // L3-domain pairing (gale/llc_pair.h), for tests: each call acts on the calling thread

@@ -459,6 +459,44 @@ PYBIND11_MODULE(_C, m) {
         py::arg("max_rows"), py::arg("d_rows"), py::arg("classes"), py::arg("k"), py::arg("x"),
         py::arg("text16"), py::arg("idx"), py::arg("d_nrec"), py::arg("status"),
         py::arg("status_out"), py::arg("stream"));
+  // the input resize kernel (resize_crop.hip) in its two forms; tables: the six device pointers
+  // (y0, y1, wy, x0, x1, wx) of the plan
+  auto resize_plan = [](int HS, int WS, int H, int W, int C, const std::vector<uintptr_t>& t) {
+    if (t.size() != 6) throw std::invalid_argument("resize_crop: six table pointers");
+    gale::ResizePlan p;
+    p.HS = HS, p.WS = WS, p.H = H, p.W = W, p.C = C;
+    p.y0 = static_cast<const int32_t*>(P(t[0]));
+    p.y1 = static_cast<const int32_t*>(P(t[1]));
+    p.wy = static_cast<const float*>(P(t[2]));
+    p.x0 = static_cast<const int32_t*>(P(t[3]));
+    p.x1 = static_cast<const int32_t*>(P(t[4]));
+    p.wx = static_cast<const float*>(P(t[5]));
+    return p;
+  };
+  m.def("resize_crop",
+        [resize_plan](int images, int HS, int WS, int H, int W, int C,
+                      std::vector<uintptr_t> tables, uintptr_t src, uintptr_t dst,
+                      uintptr_t stream) {
+          chk(gale::resize_crop(images, resize_plan(HS, WS, H, W, C, tables),
+                                static_cast<const float*>(P(src)), static_cast<float*>(P(dst)),
+                                S(stream)),
+              "resize_crop");
+        },
+        py::arg("images"), py::arg("HS"), py::arg("WS"), py::arg("H"), py::arg("W"), py::arg("C"),
+        py::arg("tables"), py::arg("src"), py::arg("dst"), py::arg("stream"));
+  m.def("resize_crop_dev",
+        [resize_plan](int max_images, uintptr_t d_images, int HS, int WS, int H, int W, int C,
+                      std::vector<uintptr_t> tables, uintptr_t src, uintptr_t dst,
+                      uintptr_t stream) {
+          chk(gale::resize_crop_dev(max_images, static_cast<const int*>(P(d_images)),
+                                    resize_plan(HS, WS, H, W, C, tables),
+                                    static_cast<const float*>(P(src)), static_cast<float*>(P(dst)),
+                                    S(stream)),
+              "resize_crop_dev");
+        },
+        py::arg("max_images"), py::arg("d_images"), py::arg("HS"), py::arg("WS"), py::arg("H"),
+        py::arg("W"), py::arg("C"), py::arg("tables"), py::arg("src"), py::arg("dst"),
+        py::arg("stream"));
   m.attr("FLOAT_TEXT_SLOT") = gale::kFloatTextSlot;
   m.attr("INPUT_TABLE_IMAGES") = gale::kInputTableImages;
   m.attr("INPUT_TABLE_BASES") = gale::kInputTableBases;

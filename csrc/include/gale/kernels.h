@@ -316,6 +316,33 @@ hipError_t b64_decode_instances(int images, const B64Image* imgs, const uint8_t*
                                 int W, int C, float* out, int* status, hipStream_t stream,
                                 const int* d_images = nullptr, const InputPrep* prep = nullptr);
 
+// ---- input resize (resize_crop.hip) ---------------------------------------------------------
+// Bilinear resize (half-pixel centres, no antialiasing) + centre crop of fp32 NHWC images:
+// src [n][HS][WS][C] -> dst [n][H][W][C]. The six tables (device memory; per output row y0 / y1
+// / wy of H entries, per output column x0 / x1 / wx of W entries) are built on the host by
+// codec::build_resize_tables (csrc/codec/resize.h, where the numerics are defined) and uploaded
+// once; the plan travels by value in the kernel arguments. Bit-identical to
+// codec::resize_crop_host. src and dst must not overlap.
+struct ResizePlan {
+  int HS = 0, WS = 0, H = 0, W = 0, C = 0;
+  const int32_t* y0 = nullptr;
+  const int32_t* y1 = nullptr;
+  const float* wy = nullptr;
+  const int32_t* x0 = nullptr;
+  const int32_t* x1 = nullptr;
+  const float* wx = nullptr;
+};
+// hipErrorInvalidValue, before any launch, for a null pointer, HS / WS / H / W outside 1..4096,
+// C < 1, an image of 2^31 floats or more, images < 0 or images > 65535. images == 0 launches
+// nothing. 16-byte stores when H * W * C is a multiple of 4 floats and dst is 16-byte aligned,
+// one store per float otherwise.
+hipError_t resize_crop(int images, const ResizePlan& plan, const float* src, float* dst,
+                       hipStream_t stream);
+// images = min(*d_images, max_images) read on the device (max_images: the launch size);
+// workgroups of later images exit before touching memory: the step graph's form
+hipError_t resize_crop_dev(int max_images, const int* d_images, const ResizePlan& plan,
+                           const float* src, float* dst, hipStream_t stream);
+
 // Raw (zero initial state, no final inversion) CRC32C of byte windows [end - len, end) of a
 // device buffer, one wave per window (len <= kCrcChunkBytes): each lane folds 64 bytes with
 // slicing-by-4 tables in LDS, shifts its register over the bytes after its piece (one GF(2)

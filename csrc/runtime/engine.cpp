@@ -341,7 +341,7 @@ void Engine::start() {
       // bytes of fetch body, the most images a body of that size can hold. b64: an image takes
       // at least L + 10 bytes of body, L = 4 * ceil(H*W*C / 3) (its string and {"b64":""}), so
       // body / L + 2 slots always do: ~3x the body in fp32, against 2x for JSON text
-      const size_t per = (size_t)cfg_.H * cfg_.W * cfg_.C;
+      const size_t per = (size_t)cfg_.rec_h() * cfg_.rec_w() * cfg_.C;
       const size_t b64_L = 4 * ((per + 2) / 3);
       const size_t slots = !per ? 0 : cfg_.input_b64 ? body / b64_L + 2 : body / (2 * per) + 2;
       const size_t arena = cfg_.ingest_parse ? slots * per * 4 : 0;
@@ -953,10 +953,11 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
     if (b64) {
       // image count and string offsets from the host scan (~20 bytes touched per image)
       const uint8_t* v = f.buf.get() + rr.value_off;
-      codec::Scan s = codec::scan_instances_b64(v, (size_t)rr.value_len, cfg_.H, cfg_.W, cfg_.C);
+      codec::Scan s = codec::scan_instances_b64(v, (size_t)rr.value_len, cfg_.rec_h(),
+                                                cfg_.rec_w(), cfg_.C);
       if (s.status == codec::OK &&
-          (!codec::b64_image_offsets(v + s.arr_off, (size_t)s.arr_len, cfg_.H, cfg_.W, cfg_.C,
-                                     offs) ||
+          (!codec::b64_image_offsets(v + s.arr_off, (size_t)s.arr_len, cfg_.rec_h(), cfg_.rec_w(),
+                                     cfg_.C, offs) ||
            (int64_t)offs.size() != s.images))
         s.status = codec::BAD_SHAPE;
       io.status[i] = s.status;
@@ -984,10 +985,10 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   try {
     if (b64)
       ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
-                      cfg_.H, cfg_.W, cfg_.C, io, arena, arena_bytes);
+                      cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
     else
-      ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked, cfg_.H,
-                  cfg_.W, cfg_.C, io, arena, arena_bytes);
+      ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
+                  cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
   } catch (const std::exception& e) {
     if (!ingest_failed_.exchange(true))
       fprintf(stderr, "[gale decode] GPU ingest failed (%s): host decode from now on\n", e.what());
@@ -1063,11 +1064,12 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   std::vector<char> have_pre;
   // the nesting dims of a record: (H, W, C), or (C, H, W) for NCHW input
   const bool nchw = cfg_.prep.nchw != 0;
-  const int scan_h = nchw ? cfg_.C : cfg_.H, scan_w = nchw ? cfg_.H : cfg_.W,
-            scan_c = nchw ? cfg_.W : cfg_.C;
+  const int rec_h = cfg_.rec_h(), rec_w = cfg_.rec_w();  // (the size the images arrive in)
+  const int scan_h = nchw ? cfg_.C : rec_h, scan_w = nchw ? rec_h : rec_w,
+            scan_c = nchw ? rec_w : cfg_.C;
   const bool b64 = cfg_.input_b64;
   auto scan = [&](const uint8_t* p, size_t n) {
-    return b64 ? codec::scan_instances_b64(p, n, cfg_.H, cfg_.W, cfg_.C)
+    return b64 ? codec::scan_instances_b64(p, n, rec_h, rec_w, cfg_.C)
                : codec::scan_instances(p, n, scan_h, scan_w, scan_c);
   };
   if (cfg_.check_crcs && !f.crc_checked) {
@@ -1663,8 +1665,8 @@ void Engine::emit(InRecord& r, std::string value, bool null_value, kafka::Produc
 bool Engine::split_record(InRecord& r, std::vector<InRecord>& good) {
   std::vector<std::pair<uint32_t, uint32_t>> spans;
   const uint8_t* arr = r.value + r.arr_off;
-  const bool ok = cfg_.input_b64 ? codec::split_instances_b64(arr, (size_t)r.arr_len, cfg_.H,
-                                                              cfg_.W, cfg_.C, spans)
+  const bool ok = cfg_.input_b64 ? codec::split_instances_b64(arr, (size_t)r.arr_len, cfg_.rec_h(),
+                                                              cfg_.rec_w(), cfg_.C, spans)
                                  : codec::split_instances(arr, (size_t)r.arr_len, spans);
   if (!ok || (int)spans.size() != r.images) return false;
   const int mb = cfg_.max_batch;
@@ -1877,13 +1879,15 @@ std::map<std::string, double> Engine::stats() const {
   s["ingested_records"] = (double)ingested_records_;
   s["ingest_parsed_records"] = (double)ingest_parsed_;
   {
-    int64_t step = 0, fwd = 0, pre = 0, tab = 0;
+    int64_t step = 0, fwd = 0, pre = 0, tab = 0, rsz = 0;
     for (auto& r : replicas_) {
+      rsz += r->rep->resized_images();
       step += r->rep->graph_step_batches();
       fwd += r->rep->graph_forward_batches();
       pre += r->rep->preparsed_records();
       tab += r->rep->table_batches();
     }
+    s["resized_images"] = (double)rsz;  // images through the input resize (kernel or host twin)
     s["table_batches"] = (double)tab;  // steps = one forward launch, inputs in kernel arguments
     s["graph_step_batches"] = (double)step;
     s["graph_forward_batches"] = (double)fwd;

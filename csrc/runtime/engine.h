@@ -131,6 +131,18 @@ struct EngineConfig {
   std::string output_key = "none";
   // model I/O contract (InstObj [N][H][W][C] -> PredObj [N][classes])
   int H = 32, W = 32, C = 3, classes = 10;
+  // input resize (codec/resize.h): every image of a record arrives as rec_H x rec_W, is resized
+  // to resize_H x resize_W and centre-cropped to the model's H x W in the replica's step. 0 =
+  // the model's dimension. Every record-side use of the image size (the host scans, the b64
+  // string length, the parsers, the splitter) takes rec_h() / rec_w(); the model side keeps H / W
+  int rec_H = 0, rec_W = 0, resize_H = 0, resize_W = 0;
+  int rec_h() const { return rec_H > 0 ? rec_H : H; }
+  int rec_w() const { return rec_W > 0 ? rec_W : W; }
+  int resize_h() const { return resize_H > 0 ? resize_H : H; }
+  int resize_w() const { return resize_W > 0 ? resize_W : W; }
+  bool resize_active() const {
+    return rec_h() != H || rec_w() != W || resize_h() != H || resize_w() != W;
+  }
   // input preprocessing applied where the records are parsed (InputPrep, gale/kernels.h); with
   // prep.nchw the records nest [N][C][H][W] and the host scans count their brackets that way
   InputPrep prep;

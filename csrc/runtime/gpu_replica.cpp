@@ -1,6 +1,7 @@
 // GpuReplica (see replica.h): staged JSON bytes -> GPU JSON parser -> hipGraph forward ->
 // softmax rows on the replica's own streams. Kept apart from the host-only replicas so the
 // sanitizer build of the host pipeline (make tsan / make asan) links no GPU code.
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -49,7 +50,8 @@ struct GpuReplica::StepError {
 GpuReplica::GpuReplica(std::shared_ptr<Executor> exec, int H, int W, int C, int classes,
                        bool use_graph, int wait_poll_us, bool gpu_encode, int locality,
                        bool step_graph, bool high_priority, bool step_direct, int top_k)
-    : exec_(std::move(exec)), H_(H), W_(W), C_(C), classes_(classes), use_graph_(use_graph),
+    : exec_(std::move(exec)), H_(H), W_(W), C_(C), classes_(classes), recH_(H), recW_(W),
+      use_graph_(use_graph),
       wait_poll_us_(wait_poll_us), gpu_encode_(gpu_encode), top_k_(gpu_encode ? top_k : 0),
       locality_(locality), step_direct_(step_direct) {
   // (the selection kernel's limits, topk.hip; the engine's configuration is checked before)
@@ -125,8 +127,51 @@ GpuReplica::~GpuReplica() {
     if (s.h_status) hipHostFree(s.h_status);
     if (s.d_status) hipFree(s.d_status);
     if (s.done) hipEventDestroy(s.done);
+    if (s.d_src) hipFree(s.d_src);
   }
+  if (d_rtab_) hipFree(d_rtab_);
   if (stream_) hipStreamDestroy(stream_);
+}
+
+// The input resize of this replica's step: the six tables in one device allocation (each part
+// 16-byte aligned) and, per slot, the source tensor the parse writes. Both are allocated here,
+// once, and never move.
+void GpuReplica::set_input_resize(const codec::ResizeTables& t) {
+  if (resize_) throw std::logic_error("GpuReplica: input resize set twice");
+  if (t.H != H_ || t.W != W_ || !codec::resize_tables_ok(t))
+    throw std::invalid_argument("GpuReplica: resize tables do not match the model input");
+  check_hip(hipSetDevice(exec_->device()), "hipSetDevice");
+  const size_t hb = ((size_t)H_ * 4 + 15) & ~(size_t)15, wb = ((size_t)W_ * 4 + 15) & ~(size_t)15;
+  std::vector<uint8_t> host(3 * hb + 3 * wb, 0);
+  memcpy(host.data(), t.y0.data(), (size_t)H_ * 4);
+  memcpy(host.data() + hb, t.y1.data(), (size_t)H_ * 4);
+  memcpy(host.data() + 2 * hb, t.wy.data(), (size_t)H_ * 4);
+  memcpy(host.data() + 3 * hb, t.x0.data(), (size_t)W_ * 4);
+  memcpy(host.data() + 3 * hb + wb, t.x1.data(), (size_t)W_ * 4);
+  memcpy(host.data() + 3 * hb + 2 * wb, t.wx.data(), (size_t)W_ * 4);
+  check_hip(hipMalloc(reinterpret_cast<void**>(&d_rtab_), host.size()), "hipMalloc(resize tables)");
+  check_hip(hipMemcpy(d_rtab_, host.data(), host.size(), hipMemcpyHostToDevice),
+            "H2D resize tables");
+  rplan_.HS = t.HS, rplan_.WS = t.WS, rplan_.H = H_, rplan_.W = W_, rplan_.C = C_;
+  rplan_.y0 = reinterpret_cast<const int32_t*>(d_rtab_);
+  rplan_.y1 = reinterpret_cast<const int32_t*>(d_rtab_ + hb);
+  rplan_.wy = reinterpret_cast<const float*>(d_rtab_ + 2 * hb);
+  rplan_.x0 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb);
+  rplan_.x1 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb + wb);
+  rplan_.wx = reinterpret_cast<const float*>(d_rtab_ + 3 * hb + 2 * wb);
+  const int mb = exec_->max_batch();
+  const size_t bytes = sizeof(float) * (size_t)mb * t.HS * t.WS * C_;
+  for (Slot& s : slots_) {
+    check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_src), bytes), "hipMalloc(resize source)");
+    // the text of a full batch at the source size (as the constructor sized it for the model's)
+    ensure_device(s, (size_t)mb * t.HS * t.WS * C_ * 12 + 4096);
+    ensure_tiles(s, (int)(((size_t)mb * t.HS * t.WS * C_ * 12) / kJsonTileBytes) + 2 * mb);
+  }
+  fprintf(stderr, "[gale %s] input resize %dx%d -> %dx%d -> crop %dx%d: %zu source bytes per "
+                  "slot, %zu slots\n",
+          name().c_str(), t.HS, t.WS, t.HR, t.WR, H_, W_, bytes, slots_.size());
+  recH_ = t.HS, recW_ = t.WS;
+  resize_ = true;
 }
 
 std::string GpuReplica::name() const { return "gpu" + std::to_string(exec_->device()); }
@@ -225,8 +270,8 @@ void GpuReplica::describe(const Batch& b, Slot& s) {
     }
     if (b64_ && !p.preparsed) {
       p.b64_first = (int32_t)s.b64_offs.size();
-      p.b64_n = codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, H_, W_, C_,
-                                         s.b64_scan)
+      p.b64_n = codec::b64_image_offsets(r.value + r.arr_off, (size_t)r.arr_len, recH_, recW_,
+                                         C_, s.b64_scan)
                     ? (int32_t)s.b64_scan.size()
                     : -1;
       s.b64_offs.insert(s.b64_offs.end(), s.b64_scan.begin(), s.b64_scan.end());
@@ -258,6 +303,7 @@ void GpuReplica::submit(Batch& b) {
     fill_batch(p, s.recs, s.b64_offs, s.meta, reinterpret_cast<uint64_t>(s.d_bytes),
                reinterpret_cast<uint64_t>(exec_->input(slot)), s.h_meta);
     launch_step(b, s, slot);
+    if (resize_) resized_ += p.img;
   }
   check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
   s.t_submit_ns = mono_ns();
@@ -389,6 +435,9 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
   const bool dev = d.device_counts;
   const int32_t* hdr = meta_at<int32_t>(s.d_meta, L.hdr);
   float* in = static_cast<float*>(exec_->input(slot));
+  // input resize: the parse writes the slot's source tensor at the records' size and resize_crop
+  // follows into the executor's input
+  float* parsed = resize_ ? s.d_src : in;
   const float* out = static_cast<const float*>(exec_->output(slot));
   int* status = d.out == StepDesc::TextVerdicts ? s.d_status : nullptr;  // (null: in the table)
   hipError_t c = hipSuccess;
@@ -399,16 +448,21 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
   }
   if (parse && b64_) {
     c = b64_decode_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
-                             s.d_bytes, H_, W_, C_, in,
+                             s.d_bytes, recH_, recW_, C_, parsed,
                              status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
                              dev ? hdr + kHdrB64 : nullptr, &prep_);
     if (c != hipSuccess) return {c, "b64_decode_instances"};
   } else if (parse) {
     c = json_parse_instances(dev ? mb : p.nrec, dev ? L.tiles_cap : p.ntiles,
                              meta_at<JsonRecord>(s.d_meta, L.recs), meta_at<int>(s.d_meta, L.tiles),
-                             s.d_bytes, H_, W_, C_, s.d_tiles, in, st, count_pass,
+                             s.d_bytes, recH_, recW_, C_, s.d_tiles, parsed, st, count_pass,
                              dev ? hdr + kHdrTiles : nullptr, status, nullptr, &prep_);
     if (c != hipSuccess) return {c, "json_parse_instances"};
+  }
+  if (parse && resize_) {
+    c = dev ? resize_crop_dev(mb, hdr + kHdrImages, rplan_, s.d_src, in, st)
+            : resize_crop(p.img, rplan_, s.d_src, in, st);
+    if (c != hipSuccess) return {c, dev ? "resize_crop_dev" : "resize_crop"};
   }
   // the forward: the executor's run with the host's count for plans that are not one device
   // batch, else sized for max_batch with the count read from the header

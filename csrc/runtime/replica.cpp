@@ -24,8 +24,20 @@ StubReplica::StubReplica(int H, int W, int C, int classes, int max_images, int d
   probs_.resize((size_t)max_images * classes);
 }
 
+void StubReplica::set_input_resize(const codec::ResizeTables& t) {
+  if (t.H != H_ || t.W != W_ || !codec::resize_tables_ok(t))
+    throw std::invalid_argument("StubReplica: resize tables do not match the model input");
+  rtab_ = t;
+  resize_ = true;
+  src_.resize((size_t)max_images_ * t.HS * t.WS * C_);
+}
+
 void StubReplica::submit(Batch& b) {
   const size_t per = (size_t)H_ * W_ * C_;
+  // the size the records' images arrive in, and where they are parsed
+  const int RH = resize_ ? rtab_.HS : H_, RW = resize_ ? rtab_.WS : W_;
+  const size_t rper = (size_t)RH * RW * C_;
+  float* const parsed = resize_ ? src_.data() : x_.data();
   int slot = 0;
   b.dev_status.assign(b.recs.size(), codec::OK);
   if (!compute_) {
@@ -43,17 +55,22 @@ void StubReplica::submit(Batch& b) {
     // an NCHW record is a rectangular array of dims (C, H, W) to the dims-agnostic decoder
     const bool nchw = prep_.nchw != 0;
     // (a b64 string's bytes are in record order too: [C][H][W] with nchw)
-    const int st = b64_ ? codec::parse_instances_b64_host(r.value, (size_t)r.len, H_, W_, C_,
-                                                          x_.data() + (size_t)slot * per,
+    const int st = b64_ ? codec::parse_instances_b64_host(r.value, (size_t)r.len, RH, RW, C_,
+                                                          parsed + (size_t)slot * rper,
                                                           max_images_ - slot, &n)
-                        : codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : H_,
-                                                      nchw ? H_ : W_, nchw ? W_ : C_,
-                                                      x_.data() + (size_t)slot * per,
+                        : codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : RH,
+                                                      nchw ? RH : RW, nchw ? RW : C_,
+                                                      parsed + (size_t)slot * rper,
                                                       max_images_ - slot, &n);
     if (st != codec::OK) b.dev_status[ri] = st;
     else if (!prep_.identity())
-      codec::apply_input_prep(x_.data() + (size_t)slot * per, n, H_, W_, C_, nchw, prep_.a,
+      codec::apply_input_prep(parsed + (size_t)slot * rper, n, RH, RW, C_, nchw, prep_.a,
                               prep_.b);
+    if (resize_ && st == codec::OK) {
+      codec::resize_crop_host(src_.data() + (size_t)slot * rper, n, C_, rtab_,
+                              x_.data() + (size_t)slot * per);
+      resized_ += n;
+    }
     for (int i = 0; i < r.images; ++i) {
       const float* img = x_.data() + (size_t)(slot + i) * per;
       float* out = probs_.data() + (size_t)(slot + i) * classes_;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../codec/json_codec.h"
+#include "../codec/resize.h"
 #include "batch_plan.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
@@ -110,6 +111,8 @@ class Replica {
   virtual int64_t preparsed_records() const { return 0; }
   // batches whose step was the forward alone with its inputs in the kernel arguments
   virtual int64_t table_batches() const { return 0; }
+  // images that went through the input resize (the resize_crop kernel or its host twin)
+  virtual int64_t resized_images() const { return 0; }
 };
 
 // CPU stub (SURVEY.md §4 "stub replica for plumbing tests on GPU-less hosts"): parses on the
@@ -129,10 +132,20 @@ class StubReplica : public Replica {
   void set_input_prep(const InputPrep& p) { prep_ = p; }
   // base64 uint8 image records (EngineConfig::input_b64): decoded by the host decoder
   void set_input_b64(bool on) { b64_ = on; }
+  // input resize (codec/resize.h): the records carry t.HS x t.WS images, parsed and preprocessed
+  // at that size into a source buffer and resized into the model-size images by the host twin
+  // of the resize_crop kernel; the logits stay the function of the model-size image. Before
+  // submit(); t.H / t.W must be the replica's
+  void set_input_resize(const codec::ResizeTables& t);
+  int64_t resized_images() const override { return resized_; }
 
  private:
   InputPrep prep_;
   bool b64_ = false;
+  bool resize_ = false;
+  codec::ResizeTables rtab_;
+  std::vector<float> src_;  // resize_: the batch's images at the source size
+  std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_, max_images_, delay_us_;
   bool compute_;
   int locality_ = -1;  // false: a "null" replica (uniform softmax, no parsing) to measure host paths
@@ -194,9 +207,17 @@ class GpuReplica : public Replica {
   // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
   // map, no count pass. Before submit()
   void set_input_b64(bool on) { b64_ = on; }
+  // input resize (codec/resize.h): the records carry t.HS x t.WS images. The tables are uploaded
+  // once and every slot gets a source tensor of max_batch * HS * WS * C floats that never moves
+  // (captured steps stay valid); the step's parse / b64 decode writes it at the source size and
+  // resize_crop follows into the executor's input (emit_step). Before submit(); t.H / t.W must
+  // be the replica's
+  void set_input_resize(const codec::ResizeTables& t);
+  int64_t resized_images() const override { return resized_; }
 
  private:
   struct Slot {
+    float* d_src = nullptr;      // input resize: the batch's images at the source size
     uint8_t* h_bytes = nullptr;  // pinned staging for records that arrived in pageable memory
     uint8_t* d_bytes = nullptr;  // device copy of the batch's JSON text
     size_t h_cap = 0, d_cap = 0;
@@ -247,7 +268,13 @@ class GpuReplica : public Replica {
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
   bool b64_ = false;
+  // input resize: off = the records carry model-size images (recH_ / recW_ == H_ / W_)
+  bool resize_ = false;
+  ResizePlan rplan_;
+  uint8_t* d_rtab_ = nullptr;  // the plan's six tables, one allocation
+  std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_;
+  int recH_, recW_;  // the size the records' images arrive in (parsers, b64 string length)
   bool use_graph_;
   int wait_poll_us_ = 0;
   bool gpu_encode_ = false;

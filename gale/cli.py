@@ -12,6 +12,7 @@
     python -m gale produce <TOPIC> [--images N] [--model M] [--rate R]   synthetic InstObj load
         [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
         [--encoding json|b64]                         b64: base64 uint8 records (--pixels byte)
+        [--size H,W]                                  images of that size (--input-size H,W)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
 
 ``--profile DIR`` re-runs the topology under ``rocprofv3 --kernel-trace --marker-trace --stats``
@@ -193,6 +194,18 @@ def cmd_broker(argv: List[str]) -> int:
     return 0
 
 
+def produce_shape(input_shape, size: str):
+    """(H, W, C) of ``produce``'s images: the model's, or ``--size H,W`` with its channels."""
+    from gale.models.preprocess import RESIZE_MAX, parse_size
+
+    hw = parse_size(size, "--size")
+    if not hw:
+        return tuple(input_shape)
+    if len(hw) != 2 or not all(1 <= v <= RESIZE_MAX for v in hw):
+        raise ValueError(f"--size: expected H,W with 1 <= H, W <= {RESIZE_MAX}, got {size!r}")
+    return (hw[0], hw[1], input_shape[2])
+
+
 def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
@@ -215,19 +228,26 @@ def cmd_produce(argv: List[str]) -> int:
     ap.add_argument("--encoding", default="json", choices=CHOICES["input_format"],
                     help="b64: one {\"b64\": ...} object of base64 uint8 pixels per image "
                          "(--input-format b64); needs --pixels byte")
+    ap.add_argument("--size", default="", metavar="H,W",
+                    help="size of the synthetic images (default: the model's; serve them with "
+                         "--input-size H,W)")
     a = ap.parse_args(argv)
     if a.encoding == "b64" and a.pixels != "byte":
         ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
+    try:
+        shape = produce_shape(net.input_shape, a.size)
+    except ValueError as e:
+        ap.error(str(e))
     if a.encoding == "b64":
-        recs = encode_records_b64(synthetic_pixels(a.images, net.input_shape, a.seed),
+        recs = encode_records_b64(synthetic_pixels(a.images, shape, a.seed),
                                   a.images_per_record, a.layout)
     elif a.pixels == "unit" and a.layout == "nhwc":
-        recs = encode_records(synthetic_images(a.images, net.input_shape, a.seed),
+        recs = encode_records(synthetic_images(a.images, shape, a.seed),
                               a.images_per_record)
     else:  # written by Python's compact json.dumps
         imgs = (synthetic_pixels if a.pixels == "byte" else synthetic_images)(
-            a.images, net.input_shape, a.seed)
+            a.images, shape, a.seed)
         recs = encode_records_text(imgs, a.images_per_record, a.layout)
     p = native().kafka.Producer(a.bootstrap, linger_ms=5, batch_size=1 << 20)
     t0 = time.time()

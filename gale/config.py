@@ -49,6 +49,13 @@ HELP = {
     "top_k": "K > 0: each image's output is {\"classes\": [...], \"scores\": [...]} of its K best "
              "classes, descending by score (ties to the lower class), instead of the whole "
              "softmax row; 1 <= K <= min(classes, 64); 0 = off (default)",
+    "input_size": "HS,WS: the size every image of a record arrives in (default: the model's H,W); "
+                  "the images are resized on the GPU (bilinear, no antialiasing) to "
+                  "--input-resize and centre-cropped to the model's H,W",
+    "input_resize": "HR,WR or S: the size an image is resampled to before the centre crop to the "
+                    "model's H,W; S follows torchvision Resize(S): the shorter side of HS,WS "
+                    "becomes S, the longer int(S*long/short); default: the model's H,W (plain "
+                    "resize, no crop); HR >= H and WR >= W (no padding)",
 }
 
 
@@ -166,6 +173,11 @@ class GaleConfig:
     input_mean: str = ""
     input_std: str = ""
     input_layout: str = "nhwc"         # nchw: records nest [N][C][H][W]
+    # input resize (gale/models/preprocess.py InputResize): records carry input_size images,
+    # resized (bilinear, half-pixel centres, no antialiasing) to input_resize and centre-cropped
+    # to the model's H,W after the preprocessing; both empty = off (model-size records)
+    input_size: str = ""               # "HS,WS": the size every image of a record arrives in
+    input_resize: str = ""             # "HR,WR" or "S" (torchvision Resize(S) on HS,WS)
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
                                        # ingest only with b64_ingest)
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
@@ -262,6 +274,7 @@ class GaleConfig:
         if self.b64_ingest and self.input_format != "b64":
             raise ValueError("--b64-ingest needs --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
+        self.input_resize_plan()  # (ValueError naming --input-size / --input-resize)
         if self.top_k != 0:
             from gale.models import get_model
 
@@ -281,6 +294,19 @@ class GaleConfig:
 
             C = get_model(self.model).input_shape[2]
         return InputPrep.from_config(self, C)
+
+    def input_resize_plan(self, H: Optional[int] = None, W: Optional[int] = None):
+        """The ``InputResize`` of this configuration (H, W: the model's input size)."""
+        from gale.models.preprocess import InputResize
+
+        if H is None or W is None:
+            from gale.models import get_model
+
+            H, W = get_model(self.model).input_shape[:2]
+        try:
+            return InputResize.build(H, W, self.input_size, self.input_resize)
+        except ValueError as e:
+            raise ValueError("--" + str(e).replace("_", "-", 1)) from None
 
     @property
     def effective_group(self) -> str:
@@ -332,7 +358,8 @@ class GaleConfig:
             watchdog_ms=self.watchdog_ms, max_restarts=self.max_restarts,
             restart_backoff_ms=self.restart_backoff_ms, fault=self.fault, seed=self.seed,
             trace=self.trace, input_format=self.input_format, b64_ingest=self.b64_ingest,
-            **self.input_prep(C).engine_entries())
+            **self.input_prep(C).engine_entries(),
+            **self.input_resize_plan(H, W).engine_entries())
 
 
 def _pack_fast() -> bool:

@@ -88,8 +88,14 @@ class Engine:
         # the GPU ingest parses each fetch into an image arena when every replica's batch step
         # can take the images from there: the direct-launch step of a whole-network plan with
         # the prediction text in its epilogue (GpuReplica ptr_input_)
+        resize = cfg.input_resize_plan(H, W)
+        if resize.active and ingest and cfg.ingest_parse:
+            log.info("input resize %dx%d -> %dx%d -> %dx%d: the GPU ingest does not parse (its "
+                     "image arena and the table step address model-size images); the batch step "
+                     "parses from the resident mirror and resizes", resize.HS, resize.WS,
+                     resize.HR, resize.WR, H, W)
         d["ingest_parse"] = bool(
-            (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
+            not resize.active and (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
             and cfg.use_graph and cfg.graph_step and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"
             and reps and all(getattr(r.executor, "step_out_ok", False) for r in reps))
         if (len(devs) > 1 or cfg.locality_split > 1) and cfg.numa_pin:

@@ -13,6 +13,9 @@ raw pixels. The numerics are defined once, here:
 Host (``codec::apply_input_prep``) and device (``json_parse_prep_kernel``) results are
 bit-identical. ``layout="nchw"`` says the record's ``instances`` array nests ``[N][C][H][W]``;
 the model's tensors stay NHWC.
+
+``InputResize`` (below) defines the step that may follow: records that carry images of another
+size are resized (bilinear) and centre-cropped to the model's on the preprocessed values.
 """
 
 from __future__ import annotations
@@ -150,6 +153,139 @@ def fma_f32(x: np.ndarray, a: np.ndarray, b: np.ndarray) -> np.ndarray:
     out = (bits + adj).view(np.float64).reshape(s.shape)
     with np.errstate(over="ignore"):
         return out.astype(np.float32)
+
+
+RESIZE_MAX = 4096  # largest source / resize / model side the resize tables are built for
+
+
+def parse_size(text, name: str) -> Tuple[int, ...]:
+    """``"40,36"`` -> (40, 36), ``"256"`` -> (256,), empty -> (); ValueError naming the option."""
+    if text is None:
+        return ()
+    if isinstance(text, int):
+        return (int(text),)
+    if not isinstance(text, str):
+        text = ",".join(str(v) for v in text)
+    parts = [p.strip() for p in text.split(",")]
+    if parts == [""]:
+        return ()
+    if len(parts) > 2 or not all(p.isdigit() for p in parts):
+        raise ValueError(f"{name}: expected H,W or one number, got {text!r}")
+    return tuple(int(p) for p in parts)
+
+
+def _axis_table(n_src: int, n_rs: int, n_out: int):
+    """Per output index of one axis: (i0, i1, w) of the half-pixel bilinear sample of a source of
+    n_src pixels resized to n_rs, read at the centre crop's n_out pixels (floor offset)."""
+    off = (n_rs - n_out) // 2
+    i0 = np.zeros(n_out, np.int32)
+    i1 = np.zeros(n_out, np.int32)
+    w = np.zeros(n_out, np.float32)
+    den = 2 * n_rs
+    for i in range(n_out):
+        num = (2 * (i + off) + 1) * n_src - n_rs
+        if num < 0:
+            continue
+        q, rem = divmod(num, den)
+        if q >= n_src - 1:
+            i0[i] = i1[i] = n_src - 1
+            continue
+        i0[i], i1[i] = q, q + 1
+        w[i] = np.float32(np.float64(rem) / np.float64(den))
+    return i0, i1, w
+
+
+def _lerp_f32(a: np.ndarray, b: np.ndarray, w: np.ndarray) -> np.ndarray:
+    """a where w == 0 (b is not used), else fma(w, b - a, a): one binary32 subtraction (binary64
+    subtraction narrowed: correctly rounded for binary32 operands) and one fma rounding."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = (b.astype(np.float64) - a.astype(np.float64)).astype(np.float32)
+        ww = np.broadcast_to(w, a.shape)
+        zero = ww == 0
+        r = fma_f32(np.where(zero, np.float32(0), ww), np.where(zero, np.float32(0), d), a)
+    return np.where(zero, a, r).astype(np.float32)
+
+
+@dataclass(frozen=True)
+class InputResize:
+    """Bilinear resize (half-pixel centres, no antialiasing) of HS x WS source images to HR x WR
+    and centre crop (floor offset) to the model's H x W, on the preprocessed fp32 NHWC values.
+
+    The numerics are fixed to the bit (``codec::build_resize_tables`` / ``resize_crop_host`` and
+    the ``resize_crop`` kernel mirror them): per output row y, with oy = (HR - H) // 2,
+    ``num = (2 (y + oy) + 1) HS - HR``, ``den = 2 HR``; num < 0 -> (0, 0, w 0); else
+    y0 = num // den, clamped (HS-1, HS-1, w 0) at the last row, else y1 = y0 + 1 and
+    w = float32(rem / den). ``lerp(a, b, w)`` is a for w == 0, else ``fmaf(w, b - a, a)``;
+    columns first, then rows."""
+
+    HS: int
+    WS: int
+    HR: int
+    WR: int
+    H: int
+    W: int
+
+    @classmethod
+    def build(cls, H: int, W: int, size="", resize="") -> "InputResize":
+        """From the option texts: ``size`` "HS,WS" (empty = the model's), ``resize`` "HR,WR" or
+        "S" (torchvision Resize(S) on HS,WS; empty = the model's). ValueError names the option."""
+        sz = parse_size(size, "input_size")
+        if len(sz) == 1:
+            raise ValueError(f"input_size: expected HS,WS, got {size!r}")
+        HS, WS = sz if sz else (H, W)
+        for v in (HS, WS):
+            if not 1 <= v <= RESIZE_MAX:
+                raise ValueError(f"input_size: {v} outside 1..{RESIZE_MAX}")
+        rs = parse_size(resize, "input_resize")
+        if len(rs) == 1:
+            S = rs[0]
+            if not 1 <= S <= RESIZE_MAX:
+                raise ValueError(f"input_resize: {S} outside 1..{RESIZE_MAX}")
+            if HS <= WS:
+                HR, WR = S, S * WS // HS
+            else:
+                HR, WR = S * HS // WS, S
+        else:
+            HR, WR = rs if rs else (H, W)
+        for v in (HR, WR):
+            if not 1 <= v <= RESIZE_MAX:
+                raise ValueError(f"input_resize: {v} outside 1..{RESIZE_MAX}")
+        if HR < H or WR < W:
+            raise ValueError(f"input_resize: {HR},{WR} is smaller than the model's {H},{W} "
+                             "(no padding)")
+        return cls(HS=HS, WS=WS, HR=HR, WR=WR, H=H, W=W)
+
+    @property
+    def active(self) -> bool:
+        return (self.HS, self.WS, self.HR, self.WR) != (self.H, self.W, self.H, self.W)
+
+    def engine_entries(self) -> Dict[str, Any]:
+        if not self.active:
+            return {}
+        return dict(rec_H=self.HS, rec_W=self.WS, resize_H=self.HR, resize_W=self.WR)
+
+    def tables(self):
+        """(y0, y1, wy, x0, x1, wx): int32 / int32 / float32 per output row, then per column."""
+        return (*_axis_table(self.HS, self.HR, self.H), *_axis_table(self.WS, self.WR, self.W))
+
+    def apply(self, x):
+        """The numpy oracle: [..., HS, WS, C] fp32 (numpy or torch) -> [..., H, W, C]."""
+        is_torch = hasattr(x, "numpy") and not isinstance(x, np.ndarray)
+        xv = x.detach().cpu().numpy() if is_torch else np.asarray(x)
+        xv = xv.astype(np.float32, copy=False)
+        if xv.ndim < 3 or xv.shape[-3:-1] != (self.HS, self.WS):
+            raise ValueError(f"expected [..., {self.HS}, {self.WS}, C], got {xv.shape}")
+        y0, y1, wy, x0, x1, wx = self.tables()
+        r0, r1 = xv[..., y0, :, :], xv[..., y1, :, :]
+        wxc = wx[:, None]
+        t = _lerp_f32(r0[..., x0, :], r0[..., x1, :], wxc)
+        u = _lerp_f32(r1[..., x0, :], r1[..., x1, :], wxc)
+        out = _lerp_f32(t, u, wy[:, None, None])
+        if is_torch:
+            import torch
+
+            return torch.from_numpy(out)
+        return out
 
 
 def prep_or_none(prep: Optional[InputPrep]) -> Optional[InputPrep]:

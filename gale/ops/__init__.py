@@ -177,6 +177,41 @@ def topk(x: torch.Tensor, k: int):
     return texts, indices
 
 
+def resize_tables(HS: int, WS: int, HR: int, WR: int, H: int, W: int, device):
+    """The six tables of an input resize (``codec::build_resize_tables``) as device tensors, in
+    the order the ``resize_crop`` bindings take their pointers: y0, y1, wy, x0, x1, wx."""
+    return [torch.from_numpy(t).to(device)
+            for t in native().build_resize_tables(HS, WS, HR, WR, H, W)]
+
+
+def resize_crop(x: torch.Tensor, resize, size, tables=None) -> torch.Tensor:
+    """Bilinear resize (half-pixel centres, no antialiasing) of x (fp32 [N, HS, WS, C]) to
+    ``resize`` = (HR, WR) and centre crop (floor offset) to ``size`` = (H, W), by the resize
+    kernel (csrc/kernels/resize_crop.hip); bit-identical to ``InputResize.apply``
+    (gale/models/preprocess.py). ``tables``: ``resize_tables(...)`` of the same dimensions on x's
+    device, to reuse them across calls. Returns fp32 [N, H, W, C]."""
+    _check(x, torch.float32, "x")
+    if x.dim() != 4:
+        raise ValueError("gale op: x must be [N, HS, WS, C]")
+    N, HS, WS, C = x.shape
+    (HR, WR), (H, W) = resize, size
+    if N > 65535 or C < 1:
+        raise ValueError("gale op: resize_crop needs N <= 65535 images and C >= 1")
+    if tables is None:
+        tables = resize_tables(HS, WS, HR, WR, H, W, x.device)  # (ValueError on bad sizes)
+    if len(tables) != 6 or tables[0].numel() != H or tables[3].numel() != W:
+        raise ValueError("gale op: resize_crop tables do not match size")
+    for t in tables:
+        if not t.is_cuda or t.device != x.device:
+            raise ValueError("gale op: resize_crop tables must be on x's device")
+    out = torch.empty(N, H, W, C, device=x.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    native().resize_crop(N, HS, WS, H, W, C, [t.data_ptr() for t in tables], x.data_ptr(),
+                         out.data_ptr(), _stream())
+    return out
+
+
 def batchnorm(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
               relu: bool = False, residual: Optional[torch.Tensor] = None,
               res_mode: str = "identity", out: Optional[torch.Tensor] = None) -> torch.Tensor:
