@@ -122,6 +122,15 @@ build/asan/resize_check: csrc/tests/resize_check.cpp csrc/codec/resize.cpp $(HDR
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/resize_check.cpp csrc/codec/resize.cpp -o $@
 
+# the antialiased resize's table builder and host twin (csrc/tests/resize_aa_check.cpp): every
+# (source, resize, model) size of 1..24 per axis within the 8x limit, the 4096 extremes, refusal
+# of every triple over the limit; codec only, no HIP call
+build/asan/resize_aa_check: csrc/tests/resize_aa_check.cpp csrc/codec/resize.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/resize_aa_check.cpp csrc/codec/resize.cpp -o $@
+
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500
 

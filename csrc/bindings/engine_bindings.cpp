@@ -78,6 +78,11 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "rec_W", c.rec_W);
   opt(d, "resize_H", c.resize_H);
   opt(d, "resize_W", c.resize_W);
+  {
+    int aa = 0;  // (InputResize.engine_entries writes 1)
+    opt(d, "resize_antialias", aa);
+    c.resize_antialias = aa != 0;
+  }
   // input preprocessing (gale/models/preprocess.py InputPrep.engine_entries)
   std::vector<float> pa, pb;
   bool nchw = false;
@@ -111,8 +116,15 @@ EngineConfig config_from_dict(const py::dict& d) {
   if (c.resize_active()) {
     codec::ResizeTables t;  // (std::invalid_argument on dimensions no table is built for)
     codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
+    if (c.resize_antialias) {  // (and on a downscale over the antialias limit)
+      codec::ResizeAaTables ta;
+      codec::build_resize_aa_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W,
+                                    ta);
+    }
     // the ingest's image arena and the table step address model-size images
     c.ingest_parse = false;
+  } else if (c.resize_antialias) {
+    throw std::invalid_argument("resize_antialias: no input resize is active");
   }
   return c;
 }
@@ -121,6 +133,20 @@ codec::ResizeTables resize_tables(const EngineConfig& c) {
   codec::ResizeTables t;
   codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
   return t;
+}
+
+codec::ResizeAaTables resize_aa_tables(const EngineConfig& c) {
+  codec::ResizeAaTables t;
+  codec::build_resize_aa_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
+  return t;
+}
+
+// the replica's input resize, in the form the configuration asks for
+template <typename R>
+void set_resize(R& rep, const EngineConfig& c) {
+  if (!c.resize_active()) return;
+  if (c.resize_antialias) rep.set_input_resize_aa(resize_aa_tables(c));
+  else rep.set_input_resize(resize_tables(c));
 }
 
 }  // namespace
@@ -135,7 +161,7 @@ void bind_engine(py::module_& m) {
                                                       delay_us, compute, locality);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
-             if (c.resize_active()) rep->set_input_resize(resize_tables(c));
+             set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },
            py::arg("max_images") = 256, py::arg("delay_us") = 0, py::arg("compute") = true,
@@ -151,7 +177,7 @@ void bind_engine(py::module_& m) {
                                                      step_direct, c.top_k);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
-             if (c.resize_active()) rep->set_input_resize(resize_tables(c));
+             set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },
            py::arg("executor"), py::arg("use_graph") = true, py::arg("wait_poll_us") = 0,

@@ -703,6 +703,40 @@ void bind_host(py::module_& m) {
           return out;
         },
         py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
+  // ---- antialiased input resize: the tables (host form, or device = the kernel's layout with
+  // strided weights and the launch figures) and the host twin of resize_crop_aa ----
+  m.def("build_resize_aa_tables",
+        [](int HS, int WS, int HR, int WR, int H, int W, bool device) -> py::object {
+          codec::ResizeAaTables t;
+          codec::build_resize_aa_tables(HS, WS, HR, WR, H, W, t);
+          auto ia = [](const std::vector<int32_t>& v) {
+            return py::array_t<int32_t>((py::ssize_t)v.size(), v.data());
+          };
+          auto fa = [](const std::vector<float>& v) {
+            return py::array_t<float>((py::ssize_t)v.size(), v.data());
+          };
+          if (!device)
+            return py::make_tuple(ia(t.ys), ia(t.yn), fa(t.wy), ia(t.xs), ia(t.xn), fa(t.wx));
+          const int band = codec::resize_aa_choose_band(t);
+          return py::make_tuple(ia(t.ys), ia(t.yn), fa(codec::resize_aa_strided(t.yn, t.wy, t.ty)),
+                                ia(t.xs), ia(t.xn), fa(codec::resize_aa_strided(t.xn, t.wx, t.tx)),
+                                t.ty, t.tx, band, codec::resize_aa_band_rows(t, band));
+        },
+        py::arg("HS"), py::arg("WS"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"),
+        py::arg("device") = false);
+  m.def("resize_crop_aa_host",
+        [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int HR, int WR, int H,
+           int W) {
+          if (x.ndim() != 4)
+            throw std::invalid_argument("resize_crop_aa_host: x must be [N, HS, WS, C]");
+          codec::ResizeAaTables t;
+          codec::build_resize_aa_tables((int)x.shape(1), (int)x.shape(2), HR, WR, H, W, t);
+          const int C = (int)x.shape(3);
+          py::array_t<float> out({x.shape(0), (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
+          codec::resize_crop_aa_host(x.data(), (int)x.shape(0), C, t, out.mutable_data());
+          return out;
+        },
+        py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
   // ---- nibble transport (text_pack.h) ----
   m.def("text_pack_fast", &codec::text_pack_fast);
   // L3-domain pairing (gale/llc_pair.h), for tests: each call acts on the calling thread

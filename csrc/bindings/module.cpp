@@ -497,6 +497,47 @@ PYBIND11_MODULE(_C, m) {
         py::arg("max_images"), py::arg("d_images"), py::arg("HS"), py::arg("WS"), py::arg("H"),
         py::arg("W"), py::arg("C"), py::arg("tables"), py::arg("src"), py::arg("dst"),
         py::arg("stream"));
+  // the antialiased resize kernel (resize_crop_aa.hip) in its two forms; dims: (HS, WS, HR, WR, H,
+  // W, C); tables: the six device pointers (ys, yn, wy, xs, xn, wx) in the kernel's layout;
+  // launch: (ty, tx, band, band_rows) (build_resize_aa_tables(..., device=True) gives all)
+  auto resize_aa_plan = [](const std::vector<int>& dims, const std::vector<uintptr_t>& t,
+                           const std::vector<int>& launch) {
+    if (dims.size() != 7 || t.size() != 6 || launch.size() != 4)
+      throw std::invalid_argument("resize_crop_aa: seven dims, six table pointers, four figures");
+    gale::ResizeAaPlan p;
+    p.HS = dims[0], p.WS = dims[1], p.HR = dims[2], p.WR = dims[3], p.H = dims[4], p.W = dims[5];
+    p.C = dims[6];
+    p.ty = launch[0], p.tx = launch[1], p.band = launch[2], p.band_rows = launch[3];
+    p.ys = static_cast<const int32_t*>(P(t[0]));
+    p.yn = static_cast<const int32_t*>(P(t[1]));
+    p.wy = static_cast<const float*>(P(t[2]));
+    p.xs = static_cast<const int32_t*>(P(t[3]));
+    p.xn = static_cast<const int32_t*>(P(t[4]));
+    p.wx = static_cast<const float*>(P(t[5]));
+    return p;
+  };
+  m.def("resize_crop_aa",
+        [resize_aa_plan](int images, std::vector<int> dims, std::vector<uintptr_t> tables,
+                         std::vector<int> launch, uintptr_t src, uintptr_t dst, uintptr_t stream) {
+          chk(gale::resize_crop_aa(images, resize_aa_plan(dims, tables, launch),
+                                   static_cast<const float*>(P(src)), static_cast<float*>(P(dst)),
+                                   S(stream)),
+              "resize_crop_aa");
+        },
+        py::arg("images"), py::arg("dims"), py::arg("tables"), py::arg("launch"), py::arg("src"),
+        py::arg("dst"), py::arg("stream"));
+  m.def("resize_crop_aa_dev",
+        [resize_aa_plan](int max_images, uintptr_t d_images, std::vector<int> dims,
+                         std::vector<uintptr_t> tables, std::vector<int> launch, uintptr_t src,
+                         uintptr_t dst, uintptr_t stream) {
+          chk(gale::resize_crop_aa_dev(max_images, static_cast<const int*>(P(d_images)),
+                                       resize_aa_plan(dims, tables, launch),
+                                       static_cast<const float*>(P(src)),
+                                       static_cast<float*>(P(dst)), S(stream)),
+              "resize_crop_aa_dev");
+        },
+        py::arg("max_images"), py::arg("d_images"), py::arg("dims"), py::arg("tables"),
+        py::arg("launch"), py::arg("src"), py::arg("dst"), py::arg("stream"));
   m.attr("FLOAT_TEXT_SLOT") = gale::kFloatTextSlot;
   m.attr("INPUT_TABLE_IMAGES") = gale::kInputTableImages;
   m.attr("INPUT_TABLE_BASES") = gale::kInputTableBases;

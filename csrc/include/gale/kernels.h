@@ -343,6 +343,41 @@ hipError_t resize_crop(int images, const ResizePlan& plan, const float* src, flo
 hipError_t resize_crop_dev(int max_images, const int* d_images, const ResizePlan& plan,
                            const float* src, float* dst, hipStream_t stream);
 
+// ---- antialiased input resize (resize_crop_aa.hip) -------------------------------------------
+// The support-scaled triangle filter (PIL / torch antialias=True) + centre crop of fp32 NHWC
+// images, src [n][HS][WS][C] -> dst [n][H][W][C], in the tap form that csrc/codec/resize.h
+// defines: per output row a run of source rows ys[y] .. ys[y] + yn[y] - 1 with weights
+// wy[y * ty + k], per output column xs / xn / wx[x * tx + k] (device memory; built by
+// codec::build_resize_aa_tables, the weights laid out with a fixed stride per axis by
+// codec::resize_aa_strided). Columns first, then rows, in one launch with no intermediate in
+// global memory: a workgroup stages the column sums of the source rows that a band of `band`
+// output rows touches in LDS. band (codec::resize_aa_choose_band) and band_rows
+// (codec::resize_aa_band_rows: the most source rows a band touches) are computed on the host
+// from the tables; the launcher sizes the LDS from them. Bit-identical to
+// codec::resize_crop_aa_host. src and dst must not overlap.
+struct ResizeAaPlan {
+  int HS = 0, WS = 0, HR = 0, WR = 0, H = 0, W = 0, C = 0;
+  int ty = 0, tx = 0;            // the largest tap count of a row / column = the weights' stride
+  int band = 0, band_rows = 0;   // output rows per workgroup; source rows its LDS tile holds
+  const int32_t* ys = nullptr;   // [H]
+  const int32_t* yn = nullptr;   // [H]
+  const float* wy = nullptr;     // [H][ty]
+  const int32_t* xs = nullptr;   // [W]
+  const int32_t* xn = nullptr;   // [W]
+  const float* wx = nullptr;     // [W][tx]
+};
+// hipErrorInvalidValue, before any launch, for what resize_crop refuses (HR / WR included) and
+// for HR < H, WR < W, HS > 8 HR or WS > 8 WR (the antialias limit), ty / tx outside 1..17, band
+// outside 1..8, band_rows < 1 or band_rows + tx > 64 (the LDS tile). images == 0 launches
+// nothing. 16-byte stores when W * C is a multiple of 4 floats and dst is 16-byte aligned, one
+// store per float otherwise.
+hipError_t resize_crop_aa(int images, const ResizeAaPlan& plan, const float* src, float* dst,
+                          hipStream_t stream);
+// images = min(*d_images, max_images) read on the device; workgroups of later images exit as a
+// whole before any barrier or memory access: the step graph's form
+hipError_t resize_crop_aa_dev(int max_images, const int* d_images, const ResizeAaPlan& plan,
+                              const float* src, float* dst, hipStream_t stream);
+
 // Raw (zero initial state, no final inversion) CRC32C of byte windows [end - len, end) of a
 // device buffer, one wave per window (len <= kCrcChunkBytes): each lane folds 64 bytes with
 // slicing-by-4 tables in LDS, shifts its register over the bytes after its piece (one GF(2)

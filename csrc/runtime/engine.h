@@ -136,6 +136,9 @@ struct EngineConfig {
   // the model's dimension. Every record-side use of the image size (the host scans, the b64
   // string length, the parsers, the splitter) takes rec_h() / rec_w(); the model side keeps H / W
   int rec_H = 0, rec_W = 0, resize_H = 0, resize_W = 0;
+  // the resize is the antialiased tap filter (codec::ResizeAaTables; resize_crop_aa and its host
+  // twin) instead of the two-tap bilinear one; only with resize_active()
+  bool resize_antialias = false;
   int rec_h() const { return rec_H > 0 ? rec_H : H; }
   int rec_w() const { return rec_W > 0 ? rec_W : W; }
   int resize_h() const { return resize_H > 0 ? resize_H : H; }

@@ -159,19 +159,62 @@ void GpuReplica::set_input_resize(const codec::ResizeTables& t) {
   rplan_.x0 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb);
   rplan_.x1 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb + wb);
   rplan_.wx = reinterpret_cast<const float*>(d_rtab_ + 3 * hb + 2 * wb);
+  alloc_resize_source(t.HS, t.WS, t.HR, t.WR, "");
+}
+
+void GpuReplica::alloc_resize_source(int HS, int WS, int HR, int WR, const char* what) {
   const int mb = exec_->max_batch();
-  const size_t bytes = sizeof(float) * (size_t)mb * t.HS * t.WS * C_;
+  const size_t bytes = sizeof(float) * (size_t)mb * HS * WS * C_;
   for (Slot& s : slots_) {
     check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_src), bytes), "hipMalloc(resize source)");
     // the text of a full batch at the source size (as the constructor sized it for the model's)
-    ensure_device(s, (size_t)mb * t.HS * t.WS * C_ * 12 + 4096);
-    ensure_tiles(s, (int)(((size_t)mb * t.HS * t.WS * C_ * 12) / kJsonTileBytes) + 2 * mb);
+    ensure_device(s, (size_t)mb * HS * WS * C_ * 12 + 4096);
+    ensure_tiles(s, (int)(((size_t)mb * HS * WS * C_ * 12) / kJsonTileBytes) + 2 * mb);
   }
-  fprintf(stderr, "[gale %s] input resize %dx%d -> %dx%d -> crop %dx%d: %zu source bytes per "
+  fprintf(stderr, "[gale %s] input resize%s %dx%d -> %dx%d -> crop %dx%d: %zu source bytes per "
                   "slot, %zu slots\n",
-          name().c_str(), t.HS, t.WS, t.HR, t.WR, H_, W_, bytes, slots_.size());
-  recH_ = t.HS, recW_ = t.WS;
+          name().c_str(), what, HS, WS, HR, WR, H_, W_, bytes, slots_.size());
+  recH_ = HS, recW_ = WS;
   resize_ = true;
+}
+
+// The antialiased form: start / count per row and column and the weights with a fixed stride per
+// axis (codec::resize_aa_strided), one device allocation, each part 16-byte aligned; the band
+// height and the LDS rows of the kernel come from the tables here, once.
+void GpuReplica::set_input_resize_aa(const codec::ResizeAaTables& t) {
+  if (resize_) throw std::logic_error("GpuReplica: input resize set twice");
+  if (t.H != H_ || t.W != W_ || !codec::resize_aa_tables_ok(t))
+    throw std::invalid_argument("GpuReplica: resize tables do not match the model input");
+  check_hip(hipSetDevice(exec_->device()), "hipSetDevice");
+  const std::vector<float> wy = codec::resize_aa_strided(t.yn, t.wy, t.ty);
+  const std::vector<float> wx = codec::resize_aa_strided(t.xn, t.wx, t.tx);
+  auto up16 = [](size_t n) { return (n * 4 + 15) & ~(size_t)15; };
+  const size_t hb = up16((size_t)H_), wb = up16((size_t)W_), wyb = up16(wy.size()),
+               wxb = up16(wx.size());
+  const size_t o_yn = hb, o_wy = 2 * hb, o_xs = o_wy + wyb, o_xn = o_xs + wb, o_wx = o_xn + wb;
+  std::vector<uint8_t> host(o_wx + wxb, 0);
+  memcpy(host.data(), t.ys.data(), (size_t)H_ * 4);
+  memcpy(host.data() + o_yn, t.yn.data(), (size_t)H_ * 4);
+  memcpy(host.data() + o_wy, wy.data(), wy.size() * 4);
+  memcpy(host.data() + o_xs, t.xs.data(), (size_t)W_ * 4);
+  memcpy(host.data() + o_xn, t.xn.data(), (size_t)W_ * 4);
+  memcpy(host.data() + o_wx, wx.data(), wx.size() * 4);
+  check_hip(hipMalloc(reinterpret_cast<void**>(&d_rtab_), host.size()), "hipMalloc(resize tables)");
+  check_hip(hipMemcpy(d_rtab_, host.data(), host.size(), hipMemcpyHostToDevice),
+            "H2D resize tables");
+  aplan_.HS = t.HS, aplan_.WS = t.WS, aplan_.HR = t.HR, aplan_.WR = t.WR;
+  aplan_.H = H_, aplan_.W = W_, aplan_.C = C_;
+  aplan_.ty = t.ty, aplan_.tx = t.tx;
+  aplan_.band = codec::resize_aa_choose_band(t);
+  aplan_.band_rows = codec::resize_aa_band_rows(t, aplan_.band);
+  aplan_.ys = reinterpret_cast<const int32_t*>(d_rtab_);
+  aplan_.yn = reinterpret_cast<const int32_t*>(d_rtab_ + o_yn);
+  aplan_.wy = reinterpret_cast<const float*>(d_rtab_ + o_wy);
+  aplan_.xs = reinterpret_cast<const int32_t*>(d_rtab_ + o_xs);
+  aplan_.xn = reinterpret_cast<const int32_t*>(d_rtab_ + o_xn);
+  aplan_.wx = reinterpret_cast<const float*>(d_rtab_ + o_wx);
+  resize_aa_ = true;
+  alloc_resize_source(t.HS, t.WS, t.HR, t.WR, " (antialiased)");
 }
 
 std::string GpuReplica::name() const { return "gpu" + std::to_string(exec_->device()); }
@@ -459,7 +502,11 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
                              dev ? hdr + kHdrTiles : nullptr, status, nullptr, &prep_);
     if (c != hipSuccess) return {c, "json_parse_instances"};
   }
-  if (parse && resize_) {
+  if (parse && resize_ && resize_aa_) {
+    c = dev ? resize_crop_aa_dev(mb, hdr + kHdrImages, aplan_, s.d_src, in, st)
+            : resize_crop_aa(p.img, aplan_, s.d_src, in, st);
+    if (c != hipSuccess) return {c, dev ? "resize_crop_aa_dev" : "resize_crop_aa"};
+  } else if (parse && resize_) {
     c = dev ? resize_crop_dev(mb, hdr + kHdrImages, rplan_, s.d_src, in, st)
             : resize_crop(p.img, rplan_, s.d_src, in, st);
     if (c != hipSuccess) return {c, dev ? "resize_crop_dev" : "resize_crop"};

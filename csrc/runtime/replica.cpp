@@ -32,10 +32,19 @@ void StubReplica::set_input_resize(const codec::ResizeTables& t) {
   src_.resize((size_t)max_images_ * t.HS * t.WS * C_);
 }
 
+void StubReplica::set_input_resize_aa(const codec::ResizeAaTables& t) {
+  if (t.H != H_ || t.W != W_ || !codec::resize_aa_tables_ok(t))
+    throw std::invalid_argument("StubReplica: resize tables do not match the model input");
+  atab_ = t;
+  resize_ = resize_aa_ = true;
+  src_.resize((size_t)max_images_ * t.HS * t.WS * C_);
+}
+
 void StubReplica::submit(Batch& b) {
   const size_t per = (size_t)H_ * W_ * C_;
   // the size the records' images arrive in, and where they are parsed
-  const int RH = resize_ ? rtab_.HS : H_, RW = resize_ ? rtab_.WS : W_;
+  const int RH = !resize_ ? H_ : resize_aa_ ? atab_.HS : rtab_.HS;
+  const int RW = !resize_ ? W_ : resize_aa_ ? atab_.WS : rtab_.WS;
   const size_t rper = (size_t)RH * RW * C_;
   float* const parsed = resize_ ? src_.data() : x_.data();
   int slot = 0;
@@ -67,8 +76,12 @@ void StubReplica::submit(Batch& b) {
       codec::apply_input_prep(parsed + (size_t)slot * rper, n, RH, RW, C_, nchw, prep_.a,
                               prep_.b);
     if (resize_ && st == codec::OK) {
-      codec::resize_crop_host(src_.data() + (size_t)slot * rper, n, C_, rtab_,
-                              x_.data() + (size_t)slot * per);
+      if (resize_aa_)
+        codec::resize_crop_aa_host(src_.data() + (size_t)slot * rper, n, C_, atab_,
+                                   x_.data() + (size_t)slot * per);
+      else
+        codec::resize_crop_host(src_.data() + (size_t)slot * rper, n, C_, rtab_,
+                                x_.data() + (size_t)slot * per);
       resized_ += n;
     }
     for (int i = 0; i < r.images; ++i) {

@@ -137,13 +137,17 @@ class StubReplica : public Replica {
   // of the resize_crop kernel; the logits stay the function of the model-size image. Before
   // submit(); t.H / t.W must be the replica's
   void set_input_resize(const codec::ResizeTables& t);
+  // the same with the antialiased tap filter (codec::ResizeAaTables, resize_crop_aa_host)
+  void set_input_resize_aa(const codec::ResizeAaTables& t);
   int64_t resized_images() const override { return resized_; }
 
  private:
   InputPrep prep_;
   bool b64_ = false;
   bool resize_ = false;
+  bool resize_aa_ = false;  // resize_: by atab_ instead of rtab_
   codec::ResizeTables rtab_;
+  codec::ResizeAaTables atab_;
   std::vector<float> src_;  // resize_: the batch's images at the source size
   std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_, max_images_, delay_us_;
@@ -213,6 +217,8 @@ class GpuReplica : public Replica {
   // resize_crop follows into the executor's input (emit_step). Before submit(); t.H / t.W must
   // be the replica's
   void set_input_resize(const codec::ResizeTables& t);
+  // the same with the antialiased tap filter: the step launches resize_crop_aa / _aa_dev
+  void set_input_resize_aa(const codec::ResizeAaTables& t);
   int64_t resized_images() const override { return resized_; }
 
  private:
@@ -270,7 +276,11 @@ class GpuReplica : public Replica {
   bool b64_ = false;
   // input resize: off = the records carry model-size images (recH_ / recW_ == H_ / W_)
   bool resize_ = false;
+  bool resize_aa_ = false;  // resize_: the antialiased form, by aplan_ instead of rplan_
   ResizePlan rplan_;
+  ResizeAaPlan aplan_;
+  // (with resize_) the slots' source tensors, sized for images of HS x WS, and the log line
+  void alloc_resize_source(int HS, int WS, int HR, int WR, const char* what);
   uint8_t* d_rtab_ = nullptr;  // the plan's six tables, one allocation
   std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_;

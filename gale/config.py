@@ -56,6 +56,9 @@ HELP = {
                     "model's H,W; S follows torchvision Resize(S): the shorter side of HS,WS "
                     "becomes S, the longer int(S*long/short); default: the model's H,W (plain "
                     "resize, no crop); HR >= H and WR >= W (no padding)",
+    "input_antialias": "resample with the antialiased (support-scaled triangle) filter of PIL / "
+                       "torchvision antialias=True instead of two-tap bilinear; needs an active "
+                       "--input-size / --input-resize and a downscale of at most 8x per axis",
 }
 
 
@@ -178,6 +181,7 @@ class GaleConfig:
     # to the model's H,W after the preprocessing; both empty = off (model-size records)
     input_size: str = ""               # "HS,WS": the size every image of a record arrives in
     input_resize: str = ""             # "HR,WR" or "S" (torchvision Resize(S) on HS,WS)
+    input_antialias: bool = False      # the antialiased tap filter on both axes (downscale <= 8x)
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
                                        # ingest only with b64_ingest)
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
@@ -274,7 +278,8 @@ class GaleConfig:
         if self.b64_ingest and self.input_format != "b64":
             raise ValueError("--b64-ingest needs --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
-        self.input_resize_plan()  # (ValueError naming --input-size / --input-resize)
+        # (ValueError naming --input-size / --input-resize / --input-antialias)
+        self.input_resize_plan()
         if self.top_k != 0:
             from gale.models import get_model
 
@@ -304,7 +309,8 @@ class GaleConfig:
 
             H, W = get_model(self.model).input_shape[:2]
         try:
-            return InputResize.build(H, W, self.input_size, self.input_resize)
+            return InputResize.build(H, W, self.input_size, self.input_resize,
+                                     self.input_antialias)
         except ValueError as e:
             raise ValueError("--" + str(e).replace("_", "-", 1)) from None
 

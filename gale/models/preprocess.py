@@ -15,7 +15,8 @@ bit-identical. ``layout="nchw"`` says the record's ``instances`` array nests ``[
 the model's tensors stay NHWC.
 
 ``InputResize`` (below) defines the step that may follow: records that carry images of another
-size are resized (bilinear) and centre-cropped to the model's on the preprocessed values.
+size are resized (bilinear, or with ``antialias`` the support-scaled triangle filter) and
+centre-cropped to the model's on the preprocessed values.
 """
 
 from __future__ import annotations
@@ -206,6 +207,60 @@ def _lerp_f32(a: np.ndarray, b: np.ndarray, w: np.ndarray) -> np.ndarray:
     return np.where(zero, a, r).astype(np.float32)
 
 
+RESIZE_AA_MAX_SCALE = 8  # antialias: n_src <= 8 * n_rs per axis ...
+RESIZE_AA_MAX_TAPS = 2 * RESIZE_AA_MAX_SCALE + 1  # ... so an entry has at most 17 taps
+
+
+def _aa_axis_table(n_src: int, n_rs: int, n_out: int):
+    """The antialiased (support-scaled triangle) filter of one axis: per output index the first
+    tap and the tap count (int32 [n_out]) and all weights concatenated in index order (float32).
+
+    With off = (n_rs - n_out) // 2 and S = max(n_src, n_rs), the integer
+    ``u(i, k) = 2 S - |(2 k + 1) n_rs - (2 (i + off) + 1) n_src|`` is 2 S times the triangle
+    weight; the taps of i are the k in [0, n_src) with u > 0 (a contiguous, non-empty run) and
+    ``w = float32(float64(u) / float64(U))``, U the sum of the run's u."""
+    off = (n_rs - n_out) // 2
+    S = max(n_src, n_rs)
+    start = np.zeros(n_out, np.int32)
+    count = np.zeros(n_out, np.int32)
+    ws = []
+    for i in range(n_out):
+        c = (2 * (i + off) + 1) * n_src
+        # u > 0 <=> c - 2 S < (2 k + 1) n_rs < c + 2 S
+        lo = max((c - 2 * S - n_rs) // (2 * n_rs) + 1, 0)
+        hi = min(-((n_rs - c - 2 * S) // (2 * n_rs)) - 1, n_src - 1)  # (ceil) - 1
+        u = [2 * S - abs((2 * k + 1) * n_rs - c) for k in range(lo, hi + 1)]
+        assert u and min(u) > 0, (n_src, n_rs, n_out, i)
+        assert lo == 0 or 2 * S - abs((2 * lo - 1) * n_rs - c) <= 0
+        assert hi == n_src - 1 or 2 * S - abs((2 * hi + 3) * n_rs - c) <= 0
+        U = sum(u)
+        assert len(u) <= RESIZE_AA_MAX_TAPS and U <= 1 << 26, (n_src, n_rs, n_out, i)
+        start[i], count[i] = lo, len(u)
+        ws.extend(np.float32(np.float64(v) / np.float64(U)) for v in u)
+    return start, count, np.array(ws, np.float32)
+
+
+def _taps_f32(v: np.ndarray, axis: int, start, count, w) -> np.ndarray:
+    """The tap sum along ``axis`` of v: per output index i the value itself where count == 1 (a
+    bit copy), else ``w0 * v0`` (one binary32 multiply) followed by ``fmaf(wk, vk, acc)`` for
+    k = 1 .. count - 1 in ascending order."""
+    v = np.moveaxis(v, axis, -1)
+    offs = np.concatenate(([0], np.cumsum(count)[:-1])).astype(np.int64)
+    start = start.astype(np.int64)
+    first = v[..., start]
+    with np.errstate(over="ignore", invalid="ignore"):
+        acc = (first.astype(np.float64) * w[offs].astype(np.float64)).astype(np.float32)
+        for j in range(1, int(count.max())):
+            live = count > j
+            if not live.any():
+                break
+            wj = np.where(live, w[np.minimum(offs + j, len(w) - 1)], np.float32(0))
+            vj = np.where(live, v[..., np.where(live, start + j, start)], np.float32(0))
+            acc = np.where(live, fma_f32(vj, wj.astype(np.float32), acc), acc)
+    out = np.where(count == 1, first, acc).astype(np.float32)
+    return np.moveaxis(out, -1, axis)
+
+
 @dataclass(frozen=True)
 class InputResize:
     """Bilinear resize (half-pixel centres, no antialiasing) of HS x WS source images to HR x WR
@@ -216,7 +271,13 @@ class InputResize:
     ``num = (2 (y + oy) + 1) HS - HR``, ``den = 2 HR``; num < 0 -> (0, 0, w 0); else
     y0 = num // den, clamped (HS-1, HS-1, w 0) at the last row, else y1 = y0 + 1 and
     w = float32(rem / den). ``lerp(a, b, w)`` is a for w == 0, else ``fmaf(w, b - a, a)``;
-    columns first, then rows."""
+    columns first, then rows.
+
+    ``antialias=True`` replaces the two-tap lerp on both axes by the support-scaled triangle
+    filter of PIL / torch ``antialias=True`` in the tap form of ``_aa_axis_table`` /
+    ``_taps_f32`` (``codec::build_resize_aa_tables`` / ``resize_crop_aa_host`` and the
+    ``resize_crop_aa`` kernel mirror it): columns first, the column sums rounded to binary32,
+    then rows. Each axis must satisfy n_src <= 8 n_rs (at most 17 taps per entry)."""
 
     HS: int
     WS: int
@@ -224,9 +285,10 @@ class InputResize:
     WR: int
     H: int
     W: int
+    antialias: bool = False
 
     @classmethod
-    def build(cls, H: int, W: int, size="", resize="") -> "InputResize":
+    def build(cls, H: int, W: int, size="", resize="", antialias=False) -> "InputResize":
         """From the option texts: ``size`` "HS,WS" (empty = the model's), ``resize`` "HR,WR" or
         "S" (torchvision Resize(S) on HS,WS; empty = the model's). ValueError names the option."""
         sz = parse_size(size, "input_size")
@@ -253,7 +315,19 @@ class InputResize:
         if HR < H or WR < W:
             raise ValueError(f"input_resize: {HR},{WR} is smaller than the model's {H},{W} "
                              "(no padding)")
-        return cls(HS=HS, WS=WS, HR=HR, WR=WR, H=H, W=W)
+        rs = cls(HS=HS, WS=WS, HR=HR, WR=WR, H=H, W=W, antialias=bool(antialias))
+        if rs.antialias:
+            if not rs.active:
+                raise ValueError("input_antialias: needs an input resize (--input-size / "
+                                 "--input-resize are the model's size)")
+            rs._check_aa_limit()
+        return rs
+
+    def _check_aa_limit(self) -> None:
+        for n_src, n_rs in ((self.HS, self.HR), (self.WS, self.WR)):
+            if n_src > RESIZE_AA_MAX_SCALE * n_rs:
+                raise ValueError(f"input_antialias: {n_src} -> {n_rs} is a downscale of more "
+                                 f"than {RESIZE_AA_MAX_SCALE}x")
 
     @property
     def active(self) -> bool:
@@ -262,11 +336,22 @@ class InputResize:
     def engine_entries(self) -> Dict[str, Any]:
         if not self.active:
             return {}
-        return dict(rec_H=self.HS, rec_W=self.WS, resize_H=self.HR, resize_W=self.WR)
+        d = dict(rec_H=self.HS, rec_W=self.WS, resize_H=self.HR, resize_W=self.WR)
+        if self.antialias:
+            d["resize_antialias"] = 1
+        return d
 
     def tables(self):
         """(y0, y1, wy, x0, x1, wx): int32 / int32 / float32 per output row, then per column."""
         return (*_axis_table(self.HS, self.HR, self.H), *_axis_table(self.WS, self.WR, self.W))
+
+    def aa_tables(self):
+        """(ys, yn, wy, xs, xn, wx) of the antialiased filter: int32 [H] first tap and tap count
+        and the float32 weights of all rows concatenated in row order (row y starts at
+        ``yn[:y].sum()``), then the same per column."""
+        self._check_aa_limit()
+        return (*_aa_axis_table(self.HS, self.HR, self.H),
+                *_aa_axis_table(self.WS, self.WR, self.W))
 
     def apply(self, x):
         """The numpy oracle: [..., HS, WS, C] fp32 (numpy or torch) -> [..., H, W, C]."""
@@ -275,12 +360,17 @@ class InputResize:
         xv = xv.astype(np.float32, copy=False)
         if xv.ndim < 3 or xv.shape[-3:-1] != (self.HS, self.WS):
             raise ValueError(f"expected [..., {self.HS}, {self.WS}, C], got {xv.shape}")
-        y0, y1, wy, x0, x1, wx = self.tables()
-        r0, r1 = xv[..., y0, :, :], xv[..., y1, :, :]
-        wxc = wx[:, None]
-        t = _lerp_f32(r0[..., x0, :], r0[..., x1, :], wxc)
-        u = _lerp_f32(r1[..., x0, :], r1[..., x1, :], wxc)
-        out = _lerp_f32(t, u, wy[:, None, None])
+        if self.antialias:
+            ys, yn, wy, xs, xn, wx = self.aa_tables()
+            out = _taps_f32(_taps_f32(xv, -2, xs, xn, wx), -3, ys, yn, wy)
+            out = np.ascontiguousarray(out)
+        else:
+            y0, y1, wy, x0, x1, wx = self.tables()
+            r0, r1 = xv[..., y0, :, :], xv[..., y1, :, :]
+            wxc = wx[:, None]
+            t = _lerp_f32(r0[..., x0, :], r0[..., x1, :], wxc)
+            u = _lerp_f32(r1[..., x0, :], r1[..., x1, :], wxc)
+            out = _lerp_f32(t, u, wy[:, None, None])
         if is_torch:
             import torch
 

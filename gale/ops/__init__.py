@@ -212,6 +212,55 @@ def resize_crop(x: torch.Tensor, resize, size, tables=None) -> torch.Tensor:
     return out
 
 
+class ResizeAaTables:
+    """The device tables of an antialiased input resize in the ``resize_crop_aa`` kernel's layout
+    (ys, yn, wy [H][ty], xs, xn, wx [W][tx]) with the dimensions and the launch figures (ty, tx,
+    band, band_rows) they were built for."""
+
+    def __init__(self, dims, tensors, launch):
+        self.dims, self.tensors, self.launch = tuple(dims), list(tensors), tuple(launch)
+
+    def ptrs(self):
+        return [t.data_ptr() for t in self.tensors]
+
+
+def resize_aa_tables(HS: int, WS: int, HR: int, WR: int, H: int, W: int, device) -> ResizeAaTables:
+    """``codec::build_resize_aa_tables`` on ``device`` for the ``resize_crop_aa`` bindings
+    (ValueError beyond the 8x antialias limit or on other bad sizes)."""
+    *tabs, ty, tx, band, rows = native().build_resize_aa_tables(HS, WS, HR, WR, H, W, device=True)
+    return ResizeAaTables((HS, WS, HR, WR, H, W), [torch.from_numpy(t).to(device) for t in tabs],
+                          (ty, tx, band, rows))
+
+
+def resize_crop_aa(x: torch.Tensor, resize, size, tables=None) -> torch.Tensor:
+    """Antialiased resize (the support-scaled triangle filter of PIL / torch ``antialias=True``,
+    half-pixel centres) of x (fp32 [N, HS, WS, C]) to ``resize`` = (HR, WR) and centre crop (floor
+    offset) to ``size`` = (H, W), by the kernel in csrc/kernels/resize_crop_aa.hip; bit-identical
+    to ``InputResize(..., antialias=True).apply`` (gale/models/preprocess.py). ``tables``:
+    ``resize_aa_tables(...)`` of the same dimensions on x's device, to reuse them across calls.
+    Returns fp32 [N, H, W, C]."""
+    _check(x, torch.float32, "x")
+    if x.dim() != 4:
+        raise ValueError("gale op: x must be [N, HS, WS, C]")
+    N, HS, WS, C = x.shape
+    (HR, WR), (H, W) = resize, size
+    if N > 65535 or C < 1:
+        raise ValueError("gale op: resize_crop_aa needs N <= 65535 images and C >= 1")
+    if tables is None:
+        tables = resize_aa_tables(HS, WS, HR, WR, H, W, x.device)  # (ValueError on bad sizes)
+    if not isinstance(tables, ResizeAaTables) or tables.dims != (HS, WS, HR, WR, H, W):
+        raise ValueError("gale op: resize_crop_aa tables do not match x, resize and size")
+    for t in tables.tensors:
+        if not t.is_cuda or t.device != x.device:
+            raise ValueError("gale op: resize_crop_aa tables must be on x's device")
+    out = torch.empty(N, H, W, C, device=x.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    native().resize_crop_aa(N, [HS, WS, HR, WR, H, W, C], tables.ptrs(), list(tables.launch),
+                            x.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
 def batchnorm(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
               relu: bool = False, residual: Optional[torch.Tensor] = None,
               res_mode: str = "identity", out: Optional[torch.Tensor] = None) -> torch.Tensor:
