@@ -47,8 +47,9 @@ clean:
 # CPU stub replicas under ThreadSanitizer / AddressSanitizer. Host code only (no GPU code is
 # linked; GPU sanitizers are not available on this pool).
 SAN_SRC   := csrc/tests/engine_stress.cpp csrc/runtime/engine.cpp csrc/runtime/replica.cpp \
-             csrc/runtime/pinned_pool.cpp csrc/runtime/trace.cpp csrc/codec/json_codec.cpp \
-             csrc/codec/text_pack.cpp csrc/codec/java8_float.cpp csrc/codec/resize.cpp \
+             csrc/runtime/resize_plan.cpp csrc/runtime/pinned_pool.cpp csrc/runtime/trace.cpp \
+             csrc/codec/json_codec.cpp csrc/codec/text_pack.cpp csrc/codec/java8_float.cpp \
+             csrc/codec/resize.cpp \
              $(wildcard csrc/kafka/*.cpp)
 SAN_FLAGS := -O1 -g -fno-omit-frame-pointer -std=c++17 -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include \
              -Icsrc/include -mavx2 -mfma -msse4.2 -mpclmul -mbmi2 -pthread
@@ -130,6 +131,17 @@ build/asan/resize_aa_check: csrc/tests/resize_aa_check.cpp csrc/codec/resize.cpp
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/resize_aa_check.cpp csrc/codec/resize.cpp -o $@
+
+# the input resize's host plan (csrc/tests/resize_plan_check.cpp): the device image of the tables
+# (layout, padding, payloads), the bound kernel plans and the host dispatch, both forms, every
+# size of 1..12 per axis and the 4096 extremes; plan + codec, no engine, no HIP call
+build/asan/resize_plan_check: csrc/tests/resize_plan_check.cpp csrc/runtime/resize_plan.cpp \
+                              csrc/codec/resize.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma \
+	    -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Icsrc/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/resize_plan_check.cpp csrc/runtime/resize_plan.cpp csrc/codec/resize.cpp -o $@
 
 tsan: build/tsan/engine_stress
 	TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" ./build/tsan/engine_stress 1500

@@ -18,6 +18,12 @@ void opt(const py::dict& d, const char* k, T& dst) {
   if (d.contains(k) && !d[k].is_none()) dst = d[k].cast<T>();
 }
 
+// the input resize an engine with this configuration runs (resize_active())
+InputResize input_resize(const EngineConfig& c) {
+  return InputResize::build(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W,
+                            c.resize_antialias);
+}
+
 EngineConfig config_from_dict(const py::dict& d) {
   EngineConfig c;
   opt(d, "bootstrap", c.bootstrap);
@@ -114,13 +120,9 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "max_records", c.max_records);
   opt(d, "seed", c.seed);
   if (c.resize_active()) {
-    codec::ResizeTables t;  // (std::invalid_argument on dimensions no table is built for)
-    codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
-    if (c.resize_antialias) {  // (and on a downscale over the antialias limit)
-      codec::ResizeAaTables ta;
-      codec::build_resize_aa_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W,
-                                    ta);
-    }
+    // (std::invalid_argument on dimensions no table is built for and, with resize_antialias, on
+    // a downscale over the antialias limit)
+    input_resize(c);
     // the ingest's image arena and the table step address model-size images
     c.ingest_parse = false;
   } else if (c.resize_antialias) {
@@ -129,24 +131,10 @@ EngineConfig config_from_dict(const py::dict& d) {
   return c;
 }
 
-codec::ResizeTables resize_tables(const EngineConfig& c) {
-  codec::ResizeTables t;
-  codec::build_resize_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
-  return t;
-}
-
-codec::ResizeAaTables resize_aa_tables(const EngineConfig& c) {
-  codec::ResizeAaTables t;
-  codec::build_resize_aa_tables(c.rec_h(), c.rec_w(), c.resize_h(), c.resize_w(), c.H, c.W, t);
-  return t;
-}
-
 // the replica's input resize, in the form the configuration asks for
 template <typename R>
 void set_resize(R& rep, const EngineConfig& c) {
-  if (!c.resize_active()) return;
-  if (c.resize_antialias) rep.set_input_resize_aa(resize_aa_tables(c));
-  else rep.set_input_resize(resize_tables(c));
+  if (c.resize_active()) rep.set_input_resize(input_resize(c));
 }
 
 }  // namespace

@@ -12,7 +12,6 @@
 #include <thread>
 
 #include "../codec/json_codec.h"
-#include "../codec/resize.h"
 #include "gale/llc_pair.h"
 #include "../codec/text_pack.h"
 #include "../kafka/broker.h"
@@ -22,6 +21,7 @@
 #include "../runtime/batch_plan.h"
 #include "../runtime/ingest_plan.h"
 #include "../runtime/pack_tap.h"
+#include "../runtime/resize_plan.h"
 #include "../kafka/protocol.h"
 #include "../kafka/wire.h"
 
@@ -677,66 +677,70 @@ void bind_host(py::module_& m) {
         },
         py::arg("x"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("nchw"), py::arg("a"),
         py::arg("b"));
-  // ---- input resize (codec/resize.h): the table builder and the host twin of resize_crop ----
+  // ---- input resize (codec/resize.h, runtime/resize_plan.h): the table builders, the device
+  // image of the tables and the host twins of resize_crop / resize_crop_aa ----
+  // (an int32 / a float array holding a copy of n values)
+  auto ia = [](const void* p, size_t n) {
+    return py::array_t<int32_t>((py::ssize_t)n, static_cast<const int32_t*>(p));
+  };
+  auto fa = [](const void* p, size_t n) {
+    return py::array_t<float>((py::ssize_t)n, static_cast<const float*>(p));
+  };
   m.def("build_resize_tables",
-        [](int HS, int WS, int HR, int WR, int H, int W) {
+        [ia, fa](int HS, int WS, int HR, int WR, int H, int W) {
           codec::ResizeTables t;
           codec::build_resize_tables(HS, WS, HR, WR, H, W, t);
-          auto ia = [](const std::vector<int32_t>& v) {
-            return py::array_t<int32_t>((py::ssize_t)v.size(), v.data());
-          };
-          auto fa = [](const std::vector<float>& v) {
-            return py::array_t<float>((py::ssize_t)v.size(), v.data());
-          };
-          return py::make_tuple(ia(t.y0), ia(t.y1), fa(t.wy), ia(t.x0), ia(t.x1), fa(t.wx));
+          return py::make_tuple(ia(t.y0.data(), H), ia(t.y1.data(), H), fa(t.wy.data(), H),
+                                ia(t.x0.data(), W), ia(t.x1.data(), W), fa(t.wx.data(), W));
         },
         py::arg("HS"), py::arg("WS"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
-  m.def("resize_crop_host",
-        [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int HR, int WR, int H,
-           int W) {
-          if (x.ndim() != 4) throw std::invalid_argument("resize_crop_host: x must be [N, HS, WS, C]");
-          codec::ResizeTables t;
-          codec::build_resize_tables((int)x.shape(1), (int)x.shape(2), HR, WR, H, W, t);
-          const int C = (int)x.shape(3);
-          py::array_t<float> out({x.shape(0), (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
-          codec::resize_crop_host(x.data(), (int)x.shape(0), C, t, out.mutable_data());
-          return out;
-        },
-        py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
-  // ---- antialiased input resize: the tables (host form, or device = the kernel's layout with
-  // strided weights and the launch figures) and the host twin of resize_crop_aa ----
+  // the antialiased tables: host form, or device = the kernel's layout with strided weights and
+  // the launch figures, the sections of the image a replica uploads (pack)
   m.def("build_resize_aa_tables",
-        [](int HS, int WS, int HR, int WR, int H, int W, bool device) -> py::object {
-          codec::ResizeAaTables t;
-          codec::build_resize_aa_tables(HS, WS, HR, WR, H, W, t);
-          auto ia = [](const std::vector<int32_t>& v) {
-            return py::array_t<int32_t>((py::ssize_t)v.size(), v.data());
-          };
-          auto fa = [](const std::vector<float>& v) {
-            return py::array_t<float>((py::ssize_t)v.size(), v.data());
-          };
+        [ia, fa](int HS, int WS, int HR, int WR, int H, int W, bool device) -> py::object {
+          const InputResize r = InputResize::build(HS, WS, HR, WR, H, W, true);
+          const codec::ResizeAaTables& t = r.aa_tables();
           if (!device)
-            return py::make_tuple(ia(t.ys), ia(t.yn), fa(t.wy), ia(t.xs), ia(t.xn), fa(t.wx));
-          const int band = codec::resize_aa_choose_band(t);
-          return py::make_tuple(ia(t.ys), ia(t.yn), fa(codec::resize_aa_strided(t.yn, t.wy, t.ty)),
-                                ia(t.xs), ia(t.xn), fa(codec::resize_aa_strided(t.xn, t.wx, t.tx)),
-                                t.ty, t.tx, band, codec::resize_aa_band_rows(t, band));
+            return py::make_tuple(ia(t.ys.data(), H), ia(t.yn.data(), H),
+                                  fa(t.wy.data(), t.wy.size()), ia(t.xs.data(), W),
+                                  ia(t.xn.data(), W), fa(t.wx.data(), t.wx.size()));
+          const ResizeDeviceImage im = pack(r);
+          auto at = [&](int i) { return im.bytes.data() + im.off[i]; };
+          return py::make_tuple(ia(at(0), H), ia(at(1), H), fa(at(2), (size_t)H * im.ty),
+                                ia(at(3), W), ia(at(4), W), fa(at(5), (size_t)W * im.tx), im.ty,
+                                im.tx, im.band, im.band_rows);
         },
         py::arg("HS"), py::arg("WS"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"),
         py::arg("device") = false);
-  m.def("resize_crop_aa_host",
-        [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int HR, int WR, int H,
-           int W) {
-          if (x.ndim() != 4)
-            throw std::invalid_argument("resize_crop_aa_host: x must be [N, HS, WS, C]");
-          codec::ResizeAaTables t;
-          codec::build_resize_aa_tables((int)x.shape(1), (int)x.shape(2), HR, WR, H, W, t);
-          const int C = (int)x.shape(3);
-          py::array_t<float> out({x.shape(0), (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
-          codec::resize_crop_aa_host(x.data(), (int)x.shape(0), C, t, out.mutable_data());
-          return out;
+  // the device image of an input resize's tables, as a replica uploads it: (bytes, the six
+  // sections' offsets, (ty, tx, band, band_rows) - zeros without antialias)
+  m.def("resize_device_image",
+        [](int HS, int WS, int HR, int WR, int H, int W, bool antialias) {
+          const ResizeDeviceImage im = pack(InputResize::build(HS, WS, HR, WR, H, W, antialias));
+          return py::make_tuple(
+              py::array_t<uint8_t>((py::ssize_t)im.bytes.size(), im.bytes.data()),
+              py::make_tuple(im.off[0], im.off[1], im.off[2], im.off[3], im.off[4], im.off[5]),
+              py::make_tuple(im.ty, im.tx, im.band, im.band_rows));
         },
-        py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
+        py::arg("HS"), py::arg("WS"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"),
+        py::arg("antialias"));
+  // the host twin of the form's kernel (InputResize::apply_host)
+  for (const bool aa : {false, true}) {
+    const char* name = aa ? "resize_crop_aa_host" : "resize_crop_host";
+    m.def(name,
+          [aa, name](py::array_t<float, py::array::c_style | py::array::forcecast> x, int HR,
+                     int WR, int H, int W) {
+            if (x.ndim() != 4)
+              throw std::invalid_argument(std::string(name) + ": x must be [N, HS, WS, C]");
+            const InputResize r =
+                InputResize::build((int)x.shape(1), (int)x.shape(2), HR, WR, H, W, aa);
+            const int C = (int)x.shape(3);
+            py::array_t<float> out({x.shape(0), (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)C});
+            r.apply_host(x.data(), (int)x.shape(0), C, out.mutable_data());
+            return out;
+          },
+          py::arg("x"), py::arg("HR"), py::arg("WR"), py::arg("H"), py::arg("W"));
+  }
   // ---- nibble transport (text_pack.h) ----
   m.def("text_pack_fast", &codec::text_pack_fast);
   // L3-domain pairing (gale/llc_pair.h), for tests: each call acts on the calling thread

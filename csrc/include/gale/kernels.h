@@ -321,7 +321,8 @@ hipError_t b64_decode_instances(int images, const B64Image* imgs, const uint8_t*
 // src [n][HS][WS][C] -> dst [n][H][W][C]. The six tables (device memory; per output row y0 / y1
 // / wy of H entries, per output column x0 / x1 / wx of W entries) are built on the host by
 // codec::build_resize_tables (csrc/codec/resize.h, where the numerics are defined) and uploaded
-// once; the plan travels by value in the kernel arguments. Bit-identical to
+// once (pack / bind, csrc/runtime/resize_plan.h: one device image, the plan's pointers into
+// it); the plan travels by value in the kernel arguments. Bit-identical to
 // codec::resize_crop_host. src and dst must not overlap.
 struct ResizePlan {
   int HS = 0, WS = 0, H = 0, W = 0, C = 0;
@@ -353,7 +354,8 @@ hipError_t resize_crop_dev(int max_images, const int* d_images, const ResizePlan
 // global memory: a workgroup stages the column sums of the source rows that a band of `band`
 // output rows touches in LDS. band (codec::resize_aa_choose_band) and band_rows
 // (codec::resize_aa_band_rows: the most source rows a band touches) are computed on the host
-// from the tables; the launcher sizes the LDS from them. Bit-identical to
+// from the tables (with the device image, pack in csrc/runtime/resize_plan.h); the launcher
+// sizes the LDS from them. Bit-identical to
 // codec::resize_crop_aa_host. src and dst must not overlap.
 struct ResizeAaPlan {
   int HS = 0, WS = 0, HR = 0, WR = 0, H = 0, W = 0, C = 0;

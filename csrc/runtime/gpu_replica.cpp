@@ -1,6 +1,8 @@
 // GpuReplica (see replica.h): staged JSON bytes -> GPU JSON parser -> hipGraph forward ->
 // softmax rows on the replica's own streams. Kept apart from the host-only replicas so the
-// sanitizer build of the host pipeline (make tsan / make asan) links no GPU code.
+// sanitizer build of the host pipeline (make tsan / make asan) links no GPU code. What a batch's
+// metadata holds and how the input resize's tables lie on the device are decided by host-only
+// plans (batch_plan.h, resize_plan.h); this file allocates, copies and launches.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -129,41 +131,25 @@ GpuReplica::~GpuReplica() {
     if (s.done) hipEventDestroy(s.done);
     if (s.d_src) hipFree(s.d_src);
   }
-  if (d_rtab_) hipFree(d_rtab_);
+  if (d_resize_) hipFree(d_resize_);
   if (stream_) hipStreamDestroy(stream_);
 }
 
-// The input resize of this replica's step: the six tables in one device allocation (each part
-// 16-byte aligned) and, per slot, the source tensor the parse writes. Both are allocated here,
-// once, and never move.
-void GpuReplica::set_input_resize(const codec::ResizeTables& t) {
-  if (resize_) throw std::logic_error("GpuReplica: input resize set twice");
-  if (t.H != H_ || t.W != W_ || !codec::resize_tables_ok(t))
+// The input resize of this replica's step: the tables' device image (pack, resize_plan.h) in one
+// device allocation with the kernel plan bound to it and, per slot, the source tensor the parse
+// writes. Both are allocated here, once, and never move.
+void GpuReplica::set_input_resize(const InputResize& r) {
+  if (d_resize_) throw std::logic_error("GpuReplica: input resize set twice");
+  if (r.H() != H_ || r.W() != W_ || !r.ok())
     throw std::invalid_argument("GpuReplica: resize tables do not match the model input");
   check_hip(hipSetDevice(exec_->device()), "hipSetDevice");
-  const size_t hb = ((size_t)H_ * 4 + 15) & ~(size_t)15, wb = ((size_t)W_ * 4 + 15) & ~(size_t)15;
-  std::vector<uint8_t> host(3 * hb + 3 * wb, 0);
-  memcpy(host.data(), t.y0.data(), (size_t)H_ * 4);
-  memcpy(host.data() + hb, t.y1.data(), (size_t)H_ * 4);
-  memcpy(host.data() + 2 * hb, t.wy.data(), (size_t)H_ * 4);
-  memcpy(host.data() + 3 * hb, t.x0.data(), (size_t)W_ * 4);
-  memcpy(host.data() + 3 * hb + wb, t.x1.data(), (size_t)W_ * 4);
-  memcpy(host.data() + 3 * hb + 2 * wb, t.wx.data(), (size_t)W_ * 4);
-  check_hip(hipMalloc(reinterpret_cast<void**>(&d_rtab_), host.size()), "hipMalloc(resize tables)");
-  check_hip(hipMemcpy(d_rtab_, host.data(), host.size(), hipMemcpyHostToDevice),
+  const ResizeDeviceImage image = pack(r);
+  check_hip(hipMalloc(reinterpret_cast<void**>(&d_resize_), image.bytes.size()),
+            "hipMalloc(resize tables)");
+  check_hip(hipMemcpy(d_resize_, image.bytes.data(), image.bytes.size(), hipMemcpyHostToDevice),
             "H2D resize tables");
-  rplan_.HS = t.HS, rplan_.WS = t.WS, rplan_.H = H_, rplan_.W = W_, rplan_.C = C_;
-  rplan_.y0 = reinterpret_cast<const int32_t*>(d_rtab_);
-  rplan_.y1 = reinterpret_cast<const int32_t*>(d_rtab_ + hb);
-  rplan_.wy = reinterpret_cast<const float*>(d_rtab_ + 2 * hb);
-  rplan_.x0 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb);
-  rplan_.x1 = reinterpret_cast<const int32_t*>(d_rtab_ + 3 * hb + wb);
-  rplan_.wx = reinterpret_cast<const float*>(d_rtab_ + 3 * hb + 2 * wb);
-  alloc_resize_source(t.HS, t.WS, t.HR, t.WR, "");
-}
-
-void GpuReplica::alloc_resize_source(int HS, int WS, int HR, int WR, const char* what) {
-  const int mb = exec_->max_batch();
+  resize_ = bind(image, r, C_, d_resize_);
+  const int mb = exec_->max_batch(), HS = r.HS(), WS = r.WS();
   const size_t bytes = sizeof(float) * (size_t)mb * HS * WS * C_;
   for (Slot& s : slots_) {
     check_hip(hipMalloc(reinterpret_cast<void**>(&s.d_src), bytes), "hipMalloc(resize source)");
@@ -173,48 +159,23 @@ void GpuReplica::alloc_resize_source(int HS, int WS, int HR, int WR, const char*
   }
   fprintf(stderr, "[gale %s] input resize%s %dx%d -> %dx%d -> crop %dx%d: %zu source bytes per "
                   "slot, %zu slots\n",
-          name().c_str(), what, HS, WS, HR, WR, H_, W_, bytes, slots_.size());
+          name().c_str(), r.antialias() ? " (antialiased)" : "", HS, WS, r.HR(), r.WR(), H_, W_,
+          bytes, slots_.size());
   recH_ = HS, recW_ = WS;
-  resize_ = true;
 }
 
-// The antialiased form: start / count per row and column and the weights with a fixed stride per
-// axis (codec::resize_aa_strided), one device allocation, each part 16-byte aligned; the band
-// height and the LDS rows of the kernel come from the tables here, once.
-void GpuReplica::set_input_resize_aa(const codec::ResizeAaTables& t) {
-  if (resize_) throw std::logic_error("GpuReplica: input resize set twice");
-  if (t.H != H_ || t.W != W_ || !codec::resize_aa_tables_ok(t))
-    throw std::invalid_argument("GpuReplica: resize tables do not match the model input");
-  check_hip(hipSetDevice(exec_->device()), "hipSetDevice");
-  const std::vector<float> wy = codec::resize_aa_strided(t.yn, t.wy, t.ty);
-  const std::vector<float> wx = codec::resize_aa_strided(t.xn, t.wx, t.tx);
-  auto up16 = [](size_t n) { return (n * 4 + 15) & ~(size_t)15; };
-  const size_t hb = up16((size_t)H_), wb = up16((size_t)W_), wyb = up16(wy.size()),
-               wxb = up16(wx.size());
-  const size_t o_yn = hb, o_wy = 2 * hb, o_xs = o_wy + wyb, o_xn = o_xs + wb, o_wx = o_xn + wb;
-  std::vector<uint8_t> host(o_wx + wxb, 0);
-  memcpy(host.data(), t.ys.data(), (size_t)H_ * 4);
-  memcpy(host.data() + o_yn, t.yn.data(), (size_t)H_ * 4);
-  memcpy(host.data() + o_wy, wy.data(), wy.size() * 4);
-  memcpy(host.data() + o_xs, t.xs.data(), (size_t)W_ * 4);
-  memcpy(host.data() + o_xn, t.xn.data(), (size_t)W_ * 4);
-  memcpy(host.data() + o_wx, wx.data(), wx.size() * 4);
-  check_hip(hipMalloc(reinterpret_cast<void**>(&d_rtab_), host.size()), "hipMalloc(resize tables)");
-  check_hip(hipMemcpy(d_rtab_, host.data(), host.size(), hipMemcpyHostToDevice),
-            "H2D resize tables");
-  aplan_.HS = t.HS, aplan_.WS = t.WS, aplan_.HR = t.HR, aplan_.WR = t.WR;
-  aplan_.H = H_, aplan_.W = W_, aplan_.C = C_;
-  aplan_.ty = t.ty, aplan_.tx = t.tx;
-  aplan_.band = codec::resize_aa_choose_band(t);
-  aplan_.band_rows = codec::resize_aa_band_rows(t, aplan_.band);
-  aplan_.ys = reinterpret_cast<const int32_t*>(d_rtab_);
-  aplan_.yn = reinterpret_cast<const int32_t*>(d_rtab_ + o_yn);
-  aplan_.wy = reinterpret_cast<const float*>(d_rtab_ + o_wy);
-  aplan_.xs = reinterpret_cast<const int32_t*>(d_rtab_ + o_xs);
-  aplan_.xn = reinterpret_cast<const int32_t*>(d_rtab_ + o_xn);
-  aplan_.wx = reinterpret_cast<const float*>(d_rtab_ + o_wx);
-  resize_aa_ = true;
-  alloc_resize_source(t.HS, t.WS, t.HR, t.WR, " (antialiased)");
+// The resize of the step in the bound plan's form: with d_images the count is read on the device
+// and `images` is the launch size (the step graph's form)
+GpuReplica::StepError GpuReplica::launch_resize(const BoundResize& r, int images,
+                                                const int* d_images, const float* src, float* dst,
+                                                hipStream_t st) {
+  if (r.antialias)
+    return d_images ? StepError{resize_crop_aa_dev(images, d_images, r.aa, src, dst, st),
+                                "resize_crop_aa_dev"}
+                    : StepError{resize_crop_aa(images, r.aa, src, dst, st), "resize_crop_aa"};
+  return d_images ? StepError{resize_crop_dev(images, d_images, r.plain, src, dst, st),
+                              "resize_crop_dev"}
+                  : StepError{resize_crop(images, r.plain, src, dst, st), "resize_crop"};
 }
 
 std::string GpuReplica::name() const { return "gpu" + std::to_string(exec_->device()); }
@@ -346,7 +307,7 @@ void GpuReplica::submit(Batch& b) {
     fill_batch(p, s.recs, s.b64_offs, s.meta, reinterpret_cast<uint64_t>(s.d_bytes),
                reinterpret_cast<uint64_t>(exec_->input(slot)), s.h_meta);
     launch_step(b, s, slot);
-    if (resize_) resized_ += p.img;
+    if (d_resize_) resized_ += p.img;
   }
   check_hip(hipEventRecord(s.done, stream_), "hipEventRecord");
   s.t_submit_ns = mono_ns();
@@ -480,7 +441,7 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
   float* in = static_cast<float*>(exec_->input(slot));
   // input resize: the parse writes the slot's source tensor at the records' size and resize_crop
   // follows into the executor's input
-  float* parsed = resize_ ? s.d_src : in;
+  float* parsed = d_resize_ ? s.d_src : in;
   const float* out = static_cast<const float*>(exec_->output(slot));
   int* status = d.out == StepDesc::TextVerdicts ? s.d_status : nullptr;  // (null: in the table)
   hipError_t c = hipSuccess;
@@ -502,14 +463,10 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
                              dev ? hdr + kHdrTiles : nullptr, status, nullptr, &prep_);
     if (c != hipSuccess) return {c, "json_parse_instances"};
   }
-  if (parse && resize_ && resize_aa_) {
-    c = dev ? resize_crop_aa_dev(mb, hdr + kHdrImages, aplan_, s.d_src, in, st)
-            : resize_crop_aa(p.img, aplan_, s.d_src, in, st);
-    if (c != hipSuccess) return {c, dev ? "resize_crop_aa_dev" : "resize_crop_aa"};
-  } else if (parse && resize_) {
-    c = dev ? resize_crop_dev(mb, hdr + kHdrImages, rplan_, s.d_src, in, st)
-            : resize_crop(p.img, rplan_, s.d_src, in, st);
-    if (c != hipSuccess) return {c, dev ? "resize_crop_dev" : "resize_crop"};
+  if (parse && d_resize_) {
+    const StepError e = launch_resize(resize_, dev ? mb : p.img, dev ? hdr + kHdrImages : nullptr,
+                                      s.d_src, in, st);
+    if (e.code != hipSuccess) return e;
   }
   // the forward: the executor's run with the host's count for plans that are not one device
   // batch, else sized for max_batch with the count read from the header

@@ -24,27 +24,18 @@ StubReplica::StubReplica(int H, int W, int C, int classes, int max_images, int d
   probs_.resize((size_t)max_images * classes);
 }
 
-void StubReplica::set_input_resize(const codec::ResizeTables& t) {
-  if (t.H != H_ || t.W != W_ || !codec::resize_tables_ok(t))
+void StubReplica::set_input_resize(const InputResize& r) {
+  if (r.H() != H_ || r.W() != W_ || !r.ok())
     throw std::invalid_argument("StubReplica: resize tables do not match the model input");
-  rtab_ = t;
-  resize_ = true;
-  src_.resize((size_t)max_images_ * t.HS * t.WS * C_);
-}
-
-void StubReplica::set_input_resize_aa(const codec::ResizeAaTables& t) {
-  if (t.H != H_ || t.W != W_ || !codec::resize_aa_tables_ok(t))
-    throw std::invalid_argument("StubReplica: resize tables do not match the model input");
-  atab_ = t;
-  resize_ = resize_aa_ = true;
-  src_.resize((size_t)max_images_ * t.HS * t.WS * C_);
+  resize_ = r;
+  src_.resize((size_t)max_images_ * r.HS() * r.WS() * C_);
 }
 
 void StubReplica::submit(Batch& b) {
   const size_t per = (size_t)H_ * W_ * C_;
   // the size the records' images arrive in, and where they are parsed
-  const int RH = !resize_ ? H_ : resize_aa_ ? atab_.HS : rtab_.HS;
-  const int RW = !resize_ ? W_ : resize_aa_ ? atab_.WS : rtab_.WS;
+  const int RH = resize_ ? resize_->HS() : H_;
+  const int RW = resize_ ? resize_->WS() : W_;
   const size_t rper = (size_t)RH * RW * C_;
   float* const parsed = resize_ ? src_.data() : x_.data();
   int slot = 0;
@@ -76,12 +67,8 @@ void StubReplica::submit(Batch& b) {
       codec::apply_input_prep(parsed + (size_t)slot * rper, n, RH, RW, C_, nchw, prep_.a,
                               prep_.b);
     if (resize_ && st == codec::OK) {
-      if (resize_aa_)
-        codec::resize_crop_aa_host(src_.data() + (size_t)slot * rper, n, C_, atab_,
-                                   x_.data() + (size_t)slot * per);
-      else
-        codec::resize_crop_host(src_.data() + (size_t)slot * rper, n, C_, rtab_,
-                                x_.data() + (size_t)slot * per);
+      resize_->apply_host(src_.data() + (size_t)slot * rper, n, C_,
+                          x_.data() + (size_t)slot * per);
       resized_ += n;
     }
     for (int i = 0; i < r.images; ++i) {

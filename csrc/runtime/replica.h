@@ -7,19 +7,21 @@
 // overlaps device work on batch k:
 //   submit(b)  — enqueue (returns immediately for the GPU replica)
 //   wait(b)    — block until b's outputs and per-record statuses are on the host
+// Both replicas take the engine's input resize as one InputResize (resize_plan.h), in either form.
 #pragma once
 #include <stdint.h>
 
 #include <atomic>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "../codec/json_codec.h"
-#include "../codec/resize.h"
 #include "batch_plan.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
+#include "resize_plan.h"
 
 namespace gale {
 
@@ -132,22 +134,17 @@ class StubReplica : public Replica {
   void set_input_prep(const InputPrep& p) { prep_ = p; }
   // base64 uint8 image records (EngineConfig::input_b64): decoded by the host decoder
   void set_input_b64(bool on) { b64_ = on; }
-  // input resize (codec/resize.h): the records carry t.HS x t.WS images, parsed and preprocessed
-  // at that size into a source buffer and resized into the model-size images by the host twin
-  // of the resize_crop kernel; the logits stay the function of the model-size image. Before
-  // submit(); t.H / t.W must be the replica's
-  void set_input_resize(const codec::ResizeTables& t);
-  // the same with the antialiased tap filter (codec::ResizeAaTables, resize_crop_aa_host)
-  void set_input_resize_aa(const codec::ResizeAaTables& t);
+  // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images, parsed
+  // and preprocessed at that size into a source buffer and resized into the model-size images by
+  // the form's host twin (InputResize::apply_host); the logits stay the function of the
+  // model-size image. Before submit(); r.H() / r.W() must be the replica's
+  void set_input_resize(const InputResize& r);
   int64_t resized_images() const override { return resized_; }
 
  private:
   InputPrep prep_;
   bool b64_ = false;
-  bool resize_ = false;
-  bool resize_aa_ = false;  // resize_: by atab_ instead of rtab_
-  codec::ResizeTables rtab_;
-  codec::ResizeAaTables atab_;
+  std::optional<InputResize> resize_;
   std::vector<float> src_;  // resize_: the batch's images at the source size
   std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_, max_images_, delay_us_;
@@ -211,14 +208,13 @@ class GpuReplica : public Replica {
   // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
   // map, no count pass. Before submit()
   void set_input_b64(bool on) { b64_ = on; }
-  // input resize (codec/resize.h): the records carry t.HS x t.WS images. The tables are uploaded
-  // once and every slot gets a source tensor of max_batch * HS * WS * C floats that never moves
-  // (captured steps stay valid); the step's parse / b64 decode writes it at the source size and
-  // resize_crop follows into the executor's input (emit_step). Before submit(); t.H / t.W must
-  // be the replica's
-  void set_input_resize(const codec::ResizeTables& t);
-  // the same with the antialiased tap filter: the step launches resize_crop_aa / _aa_dev
-  void set_input_resize_aa(const codec::ResizeAaTables& t);
+  // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images. The
+  // tables' device image (pack) is uploaded once and every slot gets a source tensor of
+  // max_batch * HS * WS * C floats that never moves (captured steps stay valid); the step's
+  // parse / b64 decode writes it at the source size and resize_crop, or resize_crop_aa for the
+  // antialiased form, follows into the executor's input (emit_step). Before submit(), once;
+  // r.H() / r.W() must be the replica's
+  void set_input_resize(const InputResize& r);
   int64_t resized_images() const override { return resized_; }
 
  private:
@@ -270,18 +266,16 @@ class GpuReplica : public Replica {
   StepDesc step_desc() const;
   StepError emit_step(Slot& s, int slot, hipStream_t st, const StepDesc& d, bool count_pass,
                       bool parse);
+  static StepError launch_resize(const BoundResize& r, int images, const int* d_images,
+                                 const float* src, float* dst, hipStream_t st);
   static void* mapped_alloc(size_t bytes, const char* what);
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
   bool b64_ = false;
-  // input resize: off = the records carry model-size images (recH_ / recW_ == H_ / W_)
-  bool resize_ = false;
-  bool resize_aa_ = false;  // resize_: the antialiased form, by aplan_ instead of rplan_
-  ResizePlan rplan_;
-  ResizeAaPlan aplan_;
-  // (with resize_) the slots' source tensors, sized for images of HS x WS, and the log line
-  void alloc_resize_source(int HS, int WS, int HR, int WR, const char* what);
-  uint8_t* d_rtab_ = nullptr;  // the plan's six tables, one allocation
+  // input resize: the tables' device image (one allocation; null = off, the records carry
+  // model-size images, recH_ / recW_ == H_ / W_) and the kernel plan bound to it
+  uint8_t* d_resize_ = nullptr;
+  BoundResize resize_;
   std::atomic<int64_t> resized_{0};
   int H_, W_, C_, classes_;
   int recH_, recW_;  // the size the records' images arrive in (parsers, b64 string length)
