@@ -108,6 +108,21 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "b64_ingest", c.b64_ingest);
   if (c.b64_ingest && !c.input_b64)
     throw std::invalid_argument("b64_ingest needs input_format b64");
+  // YUV 4:2:0 frames in the b64 strings (gale/models/preprocess.py YuvConvert.engine_entries;
+  // absent = RGB bytes)
+  {
+    std::string pf = "rgb", ym = "bt601", yr = "limited";
+    opt(d, "pixel_format", pf);
+    opt(d, "yuv_matrix", ym);
+    opt(d, "yuv_range", yr);
+    c.yuv_format = pf == "rgb"    ? (int)YUV_NONE
+                   : pf == "i420" ? (int)YUV_I420
+                   : pf == "nv12" ? (int)YUV_NV12
+                                  : throw std::invalid_argument("pixel_format: rgb, i420 or nv12");
+    if (!yuv_coeffs(ym == "bt601" ? 0 : ym == "bt709" ? 1 : -1,
+                    yr == "limited" ? 0 : yr == "full" ? 1 : -1, &c.yuv))
+      throw std::invalid_argument("yuv_matrix: bt601 or bt709; yuv_range: limited or full");
+  }
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
   opt(d, "slo_p99_ms", c.slo_p99_ms);
@@ -127,6 +142,15 @@ EngineConfig config_from_dict(const py::dict& d) {
     c.ingest_parse = false;
   } else if (c.resize_antialias) {
     throw std::invalid_argument("resize_antialias: no input resize is active");
+  }
+  if (c.yuv_format) {
+    if (!c.input_b64) throw std::invalid_argument("pixel_format i420 / nv12 needs input_format b64");
+    if (c.prep.nchw) throw std::invalid_argument("pixel_format i420 / nv12: no nchw layout");
+    if (c.C != 3) throw std::invalid_argument("pixel_format i420 / nv12 needs a 3-channel model");
+    if ((c.rec_h() | c.rec_w()) & 1)
+      throw std::invalid_argument("pixel_format i420 / nv12 needs even record-side H, W");
+    // the ingest's b64 decode and its arena hold RGB strings' images: CRC-only
+    c.ingest_parse = false;
   }
   return c;
 }
@@ -149,6 +173,7 @@ void bind_engine(py::module_& m) {
                                                       delay_us, compute, locality);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
+             rep->set_input_yuv(c.yuv_format, c.yuv);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },
@@ -165,6 +190,7 @@ void bind_engine(py::module_& m) {
                                                      step_direct, c.top_k);
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
+             rep->set_input_yuv(c.yuv_format, c.yuv);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },

@@ -662,6 +662,86 @@ void bind_host(py::module_& m) {
       return py::none();
     return py::cast(spans);
   });
+  // ---- the byte-count forms of the b64 scan / offsets / splitter, and YUV 4:2:0 frames ----
+  m.def("scan_instances_b64_bytes", [](py::bytes b, int64_t nbytes) {
+    const std::string_view s = view(b);
+    const codec::Scan sc = codec::scan_instances_b64_bytes(
+        reinterpret_cast<const uint8_t*>(s.data()), s.size(), nbytes);
+    return py::make_tuple(sc.status, sc.arr_off, sc.arr_len, sc.images);
+  });
+  m.def("b64_image_offsets_bytes", [](py::bytes arr, int64_t nbytes) -> py::object {
+    const std::string_view s = view(arr);
+    std::vector<uint32_t> offs;
+    if (!codec::b64_image_offsets_bytes(reinterpret_cast<const uint8_t*>(s.data()), s.size(),
+                                        nbytes, offs))
+      return py::none();
+    return py::cast(offs);
+  });
+  m.def("split_instances_b64_bytes", [](py::bytes arr, int64_t nbytes) -> py::object {
+    const std::string_view s = view(arr);
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    if (!codec::split_instances_b64_bytes(reinterpret_cast<const uint8_t*>(s.data()), s.size(),
+                                          nbytes, spans))
+      return py::none();
+    return py::cast(spans);
+  });
+  m.def("yuv_coeffs", [](const std::string& matrix, const std::string& range) {
+    // (cy, crv, cgu, cgv, cbu, yo): the literals of csrc/codec/yuv.h
+    YuvCoeffs k;
+    const int mi = matrix == "bt601" ? 0 : matrix == "bt709" ? 1 : -1;
+    const int ri = range == "limited" ? 0 : range == "full" ? 1 : -1;
+    if (!yuv_coeffs(mi, ri, &k)) throw std::invalid_argument("yuv_coeffs: matrix / range");
+    return py::make_tuple(k.cy, k.crv, k.cgu, k.cgv, k.cbu, k.yo);
+  });
+  m.def("yuv420_to_rgb_host",
+        [](py::bytes frame, int HS, int WS, const std::string& format,
+           std::vector<int32_t> coeffs, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b) {
+          // one frame -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep (3+ values)
+          const std::string_view s = view(frame);
+          if (coeffs.size() != 6 || (a && a->size() < 3) || (b && b->size() < 3) ||
+              bool(a) != bool(b))
+            throw std::invalid_argument("yuv420_to_rgb_host: coeffs (6), a / b (>= 3 each)");
+          const int fmt = format == "i420" ? YUV_I420 : format == "nv12" ? YUV_NV12 : YUV_NONE;
+          if (fmt == YUV_NONE || HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1) ||
+              (int64_t)s.size() != yuv420_bytes(HS, WS))
+            throw std::invalid_argument("yuv420_to_rgb_host: format / size / byte count");
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          codec::yuv420_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, fmt, k,
+                                    rgb.mutable_data(), f32.mutable_data(),
+                                    a ? a->data() : nullptr, b ? b->data() : nullptr);
+          return py::make_tuple(rgb, f32);
+        },
+        py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("parse_instances_yuv_host",
+        [](py::bytes b, int HS, int WS, const std::string& format, std::vector<int32_t> coeffs,
+           int max_images) {
+          // (status, float32 [N, HS, WS, 3]: (float)RGB of every frame)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          if (coeffs.size() != 6) throw std::invalid_argument("parse_instances_yuv_host: coeffs");
+          const int fmt = format == "i420" ? YUV_I420 : format == "nv12" ? YUV_NV12 : YUV_NONE;
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          int n = 0;
+          int st = codec::parse_instances_yuv_host(p, s.size(), HS, WS, fmt, k, nullptr,
+                                                   max_images, &n);
+          if (st != codec::OK) n = 0;
+          py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
+                                  (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
+          if (st == codec::OK)
+            st = codec::parse_instances_yuv_host(p, s.size(), HS, WS, fmt, k, out.mutable_data(),
+                                                 max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("max_images") = -1);
   m.def("apply_input_prep",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
            bool nchw, std::vector<float> a, std::vector<float> b) {

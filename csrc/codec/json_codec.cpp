@@ -388,22 +388,30 @@ struct B64Table {
   }
 };
 
-int walk_b64_array(const uint8_t* arr, size_t len, int H, int W, int C,
-                   std::vector<B64Elem>& elems) {
+int walk_b64_array(const uint8_t* arr, size_t len, int64_t nbytes, std::vector<B64Elem>& elems) {
   elems.clear();
-  if (len < 2 || arr[0] != '[' || H <= 0 || W <= 0 || C <= 0) return BAD_ENVELOPE;
+  if (len < 2 || arr[0] != '[' || nbytes <= 0) return BAD_ENVELOPE;
   size_t end = 0;
   int64_t N = 0;
-  const int st = walk_b64(arr, 0, len, (size_t)b64_chars(H, W, C), &end, &N, &elems);
+  const int st = walk_b64(arr, 0, len, (size_t)b64_chars_bytes(nbytes), &end, &N, &elems);
   if (st != OK) return st;
   return end == len ? OK : BAD_ENVELOPE;
 }
 
 }  // namespace
 
+// H * W * C bytes of an image; 0 for a non-positive dimension
+static int64_t image_bytes(int H, int W, int C) {
+  return H <= 0 || W <= 0 || C <= 0 ? 0 : (int64_t)H * W * C;
+}
+
 Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C) {
+  return scan_instances_b64_bytes(p, n, image_bytes(H, W, C));
+}
+
+Scan scan_instances_b64_bytes(const uint8_t* p, size_t n, int64_t nbytes) {
   Scan s;
-  if (H <= 0 || W <= 0 || C <= 0) { s.status = BAD_SHAPE; return s; }
+  if (nbytes <= 0) { s.status = BAD_SHAPE; return s; }
   // the {"instances": prefix (as scan_envelope reads it)
   size_t i = skip_ws(p, 0, n);
   if (i >= n || p[i] != '{') { s.status = BAD_ENVELOPE; return s; }
@@ -435,7 +443,7 @@ Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C) {
   const size_t beg = i;
   size_t end = 0;
   int64_t N = 0;
-  s.status = walk_b64(p, beg, n, (size_t)b64_chars(H, W, C), &end, &N, nullptr);
+  s.status = walk_b64(p, beg, n, (size_t)b64_chars_bytes(nbytes), &end, &N, nullptr);
   if (s.status != OK) return s;
   // the "] ws } ws" suffix
   i = skip_ws(p, end, n);
@@ -453,9 +461,14 @@ Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C) {
 
 bool b64_image_offsets(const uint8_t* arr, size_t len, int H, int W, int C,
                        std::vector<uint32_t>& offs) {
+  return b64_image_offsets_bytes(arr, len, image_bytes(H, W, C), offs);
+}
+
+bool b64_image_offsets_bytes(const uint8_t* arr, size_t len, int64_t nbytes,
+                             std::vector<uint32_t>& offs) {
   std::vector<B64Elem> elems;
   offs.clear();
-  if (len > UINT32_MAX || walk_b64_array(arr, len, H, W, C, elems) != OK) return false;
+  if (len > UINT32_MAX || walk_b64_array(arr, len, nbytes, elems) != OK) return false;
   offs.reserve(elems.size());
   for (const B64Elem& e : elems) offs.push_back((uint32_t)e.str);
   return true;
@@ -463,9 +476,14 @@ bool b64_image_offsets(const uint8_t* arr, size_t len, int H, int W, int C,
 
 bool split_instances_b64(const uint8_t* arr, size_t len, int H, int W, int C,
                          std::vector<std::pair<uint32_t, uint32_t>>& spans) {
+  return split_instances_b64_bytes(arr, len, image_bytes(H, W, C), spans);
+}
+
+bool split_instances_b64_bytes(const uint8_t* arr, size_t len, int64_t nbytes,
+                               std::vector<std::pair<uint32_t, uint32_t>>& spans) {
   std::vector<B64Elem> elems;
   spans.clear();
-  if (len > UINT32_MAX || walk_b64_array(arr, len, H, W, C, elems) != OK) return false;
+  if (len > UINT32_MAX || walk_b64_array(arr, len, nbytes, elems) != OK) return false;
   spans.reserve(elems.size());
   for (const B64Elem& e : elems) spans.emplace_back((uint32_t)e.begin, (uint32_t)e.end);
   return true;
@@ -479,7 +497,7 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
   if (s.status != OK) return s.status;
   if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
   std::vector<B64Elem> elems;
-  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, H, W, C, elems);
+  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, image_bytes(H, W, C), elems);
   if (st != OK) return st;
   const size_t per = (size_t)H * W * C, L = (size_t)b64_chars(H, W, C);
   const size_t pad = (3 - per % 3) % 3;
@@ -503,6 +521,42 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
       for (size_t j = 0; j < 3 && o + j < per; ++j)
         dst[o + j] = (float)((v >> (16 - 8 * j)) & 0xFF);
     }
+  }
+  *images = s.images;
+  return OK;
+}
+
+int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                             const YuvCoeffs& k, float* out, int max_images, int* images) {
+  static const B64Table table;
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1) ||
+      (format != YUV_I420 && format != YUV_NV12))
+    return BAD_SHAPE;
+  const int64_t B = yuv420_bytes(HS, WS);
+  const Scan s = scan_instances_b64_bytes(p, n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  std::vector<B64Elem> elems;
+  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, B, elems);
+  if (st != OK) return st;
+  // (B is a multiple of 3: every character of the L = 4 B / 3 is a data character)
+  std::vector<uint8_t> frame((size_t)B);
+  const size_t per = (size_t)HS * WS * 3;
+  for (size_t e = 0; e < elems.size(); ++e) {
+    const uint8_t* q = p + s.arr_off + elems[e].str;
+    for (size_t g = 0; g < (size_t)B / 3; ++g) {
+      uint32_t v = 0;
+      for (size_t j = 0; j < 4; ++j) {
+        const uint8_t x = table.v[q[4 * g + j]];
+        if (x == 0xFF) return BAD_NUMBER;
+        v = (v << 6) | x;
+      }
+      frame[3 * g] = (uint8_t)(v >> 16);
+      frame[3 * g + 1] = (uint8_t)(v >> 8);
+      frame[3 * g + 2] = (uint8_t)v;
+    }
+    if (out) yuv420_to_rgb_host(frame.data(), HS, WS, format, k, nullptr, out + e * per);
   }
   *images = s.images;
   return OK;

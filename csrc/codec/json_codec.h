@@ -23,6 +23,8 @@
 #include <utility>
 #include <vector>
 
+#include "yuv.h"
+
 namespace gale {
 namespace codec {
 
@@ -88,6 +90,11 @@ void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, cons
 
 // Characters of one image's string.
 inline int64_t b64_chars(int H, int W, int C) { return 4 * (((int64_t)H * W * C + 2) / 3); }
+// The same from the string's byte count: the scan, b64_image_offsets and split_instances_b64
+// below have a *_bytes form that takes the bytes one string carries (an H x W x C image: H*W*C;
+// a YUV 4:2:0 frame: yuv420_bytes, yuv.h); the (H, W, C) forms forward to it. nbytes <= 0 is
+// what a non-positive dimension is there.
+inline int64_t b64_chars_bytes(int64_t nbytes) { return 4 * ((nbytes + 2) / 3); }
 
 // Envelope and element-list check + image count. Walks the elements and never reads a string's
 // body: after the opening quote it checks the closing quote L characters on. O(images), every
@@ -97,16 +104,21 @@ inline int64_t b64_chars(int H, int W, int C) { return 4 * (((int64_t)H * W * C 
 // object, a value that is not a string, a closing quote not at L characters), TOO_LARGE
 // (more than 2^30 images). The characters themselves are judged by the decoder (BAD_NUMBER).
 Scan scan_instances_b64(const uint8_t* p, size_t n, int H, int W, int C);
+Scan scan_instances_b64_bytes(const uint8_t* p, size_t n, int64_t nbytes);
 
 // Of a scanned record's instances array `arr[0..len)`: the offset (from arr) of the first
 // character of every image's string. false when the element list is not what the scan accepted.
 bool b64_image_offsets(const uint8_t* arr, size_t len, int H, int W, int C,
                        std::vector<uint32_t>& offs);
+bool b64_image_offsets_bytes(const uint8_t* arr, size_t len, int64_t nbytes,
+                             std::vector<uint32_t>& offs);
 
 // split_instances for b64 records: the byte spans [begin, end) of the elements (each image's
 // {"b64":"..."} object).
 bool split_instances_b64(const uint8_t* arr, size_t len, int H, int W, int C,
                          std::vector<std::pair<uint32_t, uint32_t>>& spans);
+bool split_instances_b64_bytes(const uint8_t* arr, size_t len, int64_t nbytes,
+                               std::vector<std::pair<uint32_t, uint32_t>>& spans);
 
 // Full host decoder: the scan's verdicts, then every string decoded into out[N*H*W*C] as
 // (float)byte in string order (what parse_instances_host gives for the same pixels written as
@@ -114,6 +126,15 @@ bool split_instances_b64(const uint8_t* arr, size_t len, int H, int W, int C,
 // BAD_NUMBER; unused low bits of the last data character are ignored. out may be null.
 int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
                              int max_images, int* images);
+
+// Full host decoder of YUV 4:2:0 frame records (yuv.h): the same envelope, element list and
+// verdicts with strings of yuv420_bytes(HS, WS) bytes (L = 4 B / 3 characters, never a '='; a
+// character outside the alphabet anywhere is BAD_NUMBER), every frame converted by
+// yuv420_to_rgb_host into out[N][HS][WS][3] as (float)RGB - what parse_instances_b64_host gives
+// for the converted image sent as an RGB record. Odd or non-positive sizes and unknown formats
+// are BAD_SHAPE. out may be null.
+int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                             const YuvCoeffs& k, float* out, int max_images, int* images);
 
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.

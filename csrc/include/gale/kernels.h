@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
+
 namespace gale {
 
 // Geometry of one convolution (or fully connected layer expressed as a 1x1 convolution over a
@@ -315,6 +317,29 @@ static_assert(sizeof(B64Image) == 16, "B64Image layout (host <-> device tables)"
 hipError_t b64_decode_instances(int images, const B64Image* imgs, const uint8_t* bytes, int H,
                                 int W, int C, float* out, int* status, hipStream_t stream,
                                 const int* d_images = nullptr, const InputPrep* prep = nullptr);
+
+// GPU decoder of base64 YUV 4:2:0 video-frame records (input pixel formats "i420" / "nv12",
+// b64_yuv.hip): every frame's string - L = 4 B / 3 characters of standard base64, B = HS*WS*3/2,
+// never a '=' - becomes the HS*WS*3 floats of its RGB image in the fp32 NHWC batch tensor, by the
+// integer conversion that csrc/codec/yuv.h defines (format: YUV_I420 or YUV_NV12; coeffs: its
+// table, by value in the kernel arguments like prep): the bits b64_decode_instances gives for
+// the converted image sent as an RGB record with the same prep. imgs, status (2 for a character
+// outside the alphabet anywhere in one of the record's strings; the frame is written anyway,
+// within its own slot), d_images and the read bounds around a string are b64_decode_instances'.
+// A workgroup decodes `pairs` whole row pairs of one frame into LDS and converts them; pairs = 0:
+// b64_yuv_pairs(HS, WS), about 4096 pixels a workgroup. 16-byte stores when the image's base is
+// 16-byte aligned, one float per lane otherwise; both contiguous over a wave.
+// hipErrorInvalidValue, before any launch: odd or non-positive HS / WS, C != 3, a null pointer,
+// an unknown format, an nchw prep, more than 65535 images, a frame of more than 2^30 floats,
+// pairs outside 0 .. HS / 2, or a block of b64_yuv_lds_bytes(WS, pairs) > kYuvLdsBudget (a
+// single row pair of WS > 21 836). images == 0 launches nothing.
+constexpr size_t kYuvLdsBudget = 64 * 1024;
+int b64_yuv_pairs(int HS, int WS);
+size_t b64_yuv_lds_bytes(int WS, int pairs);
+hipError_t b64_yuv_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                             int WS, int C, float* out, int* status, hipStream_t stream,
+                             const int* d_images, const InputPrep* prep, int format,
+                             const YuvCoeffs& coeffs, int pairs = 0);
 
 // ---- input resize (resize_crop.hip) ---------------------------------------------------------
 // Bilinear resize (half-pixel centres, no antialiasing) + centre crop of fp32 NHWC images:

@@ -953,11 +953,10 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
     if (b64) {
       // image count and string offsets from the host scan (~20 bytes touched per image)
       const uint8_t* v = f.buf.get() + rr.value_off;
-      codec::Scan s = codec::scan_instances_b64(v, (size_t)rr.value_len, cfg_.rec_h(),
-                                                cfg_.rec_w(), cfg_.C);
+      codec::Scan s = codec::scan_instances_b64_bytes(v, (size_t)rr.value_len, cfg_.rec_bytes());
       if (s.status == codec::OK &&
-          (!codec::b64_image_offsets(v + s.arr_off, (size_t)s.arr_len, cfg_.rec_h(), cfg_.rec_w(),
-                                     cfg_.C, offs) ||
+          (!codec::b64_image_offsets_bytes(v + s.arr_off, (size_t)s.arr_len, cfg_.rec_bytes(),
+                                           offs) ||
            (int64_t)offs.size() != s.images))
         s.status = codec::BAD_SHAPE;
       io.status[i] = s.status;
@@ -984,8 +983,11 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       arena_bytes ? reinterpret_cast<float*>(dev + pool.mirror_extra_offset()) : nullptr;
   try {
     if (b64)
+      // (a YUV frame's string is that of an (HS / 2) x WS x 3 byte image to the ingest's plan,
+      // which checks it against its record; there is no arena, so nothing is decoded)
       ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
-                      cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
+                      cfg_.yuv_format ? cfg_.rec_h() / 2 : cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io,
+                      arena, arena_bytes);
     else
       ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
                   cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
@@ -995,6 +997,7 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
     return false;
   }
   b64_records_ += b64_accepted;  // (as the host path: records the scan accepted)
+  if (cfg_.yuv_format) yuv_records_ += b64_accepted;
   std::vector<char> corrupt(n, 0);
   for (size_t b = 0; b < f.batches.size(); ++b)
     if (!io.batch_ok[b])
@@ -1069,7 +1072,7 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
             scan_c = nchw ? rec_w : cfg_.C;
   const bool b64 = cfg_.input_b64;
   auto scan = [&](const uint8_t* p, size_t n) {
-    return b64 ? codec::scan_instances_b64(p, n, rec_h, rec_w, cfg_.C)
+    return b64 ? codec::scan_instances_b64_bytes(p, n, cfg_.rec_bytes())
                : codec::scan_instances(p, n, scan_h, scan_w, scan_c);
   };
   if (cfg_.check_crcs && !f.crc_checked) {
@@ -1131,7 +1134,10 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       r.arr_len = s.arr_len;
       r.images = s.images;
       if (r.status == codec::OK && fault_hit(parse_error_p_)) r.status = codec::BAD_ENVELOPE;
-      if (b64 && r.status == codec::OK) ++b64_records_;
+      if (b64 && r.status == codec::OK) {
+        ++b64_records_;
+        if (cfg_.yuv_format) ++yuv_records_;
+      }
     }
     if (r.status == codec::OK && r.images > cfg_.max_batch) {
       images_in_ += r.images;
@@ -1665,8 +1671,8 @@ void Engine::emit(InRecord& r, std::string value, bool null_value, kafka::Produc
 bool Engine::split_record(InRecord& r, std::vector<InRecord>& good) {
   std::vector<std::pair<uint32_t, uint32_t>> spans;
   const uint8_t* arr = r.value + r.arr_off;
-  const bool ok = cfg_.input_b64 ? codec::split_instances_b64(arr, (size_t)r.arr_len, cfg_.rec_h(),
-                                                              cfg_.rec_w(), cfg_.C, spans)
+  const bool ok = cfg_.input_b64 ? codec::split_instances_b64_bytes(arr, (size_t)r.arr_len,
+                                                                    cfg_.rec_bytes(), spans)
                                  : codec::split_instances(arr, (size_t)r.arr_len, spans);
   if (!ok || (int)spans.size() != r.images) return false;
   const int mb = cfg_.max_batch;
@@ -1808,6 +1814,7 @@ std::map<std::string, double> Engine::stats() const {
   s["poison_unknown_span"] = (double)poison_unknown_span_;
   s["split_records"] = (double)split_records_;
   s["b64_records"] = (double)b64_records_;
+  s["yuv_records"] = (double)yuv_records_;
   s["sparse_fetches"] = (double)sparse_fetches_;
   s["restored_fetches"] = (double)restored_fetches_;
   {

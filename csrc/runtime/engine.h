@@ -157,6 +157,16 @@ struct EngineConfig {
   // input_b64 with a GPU ingest attached (Ingest::run_b64): batch CRCs on the device and, with
   // ingest_parse, every string decoded into the fetch's image arena - the table step
   bool b64_ingest = false;
+  // input pixel format of b64 records (csrc/codec/yuv.h): YUV_NONE = interleaved RGB bytes;
+  // YUV_I420 / YUV_NV12 = every string is a YUV 4:2:0 frame of rec_h() x rec_w() (both even,
+  // C == 3, no nchw), converted with `yuv` where the strings are decoded. A GPU ingest then runs
+  // in its CRC-only form (ingest_parse off): the step decodes from the resident mirror
+  int yuv_format = 0;
+  YuvCoeffs yuv;
+  // bytes one b64 string carries
+  int64_t rec_bytes() const {
+    return yuv_format ? yuv420_bytes(rec_h(), rec_w()) : (int64_t)rec_h() * rec_w() * C;
+  }
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
   int max_wait_us = 2000;          // latency bound on batch formation
@@ -437,6 +447,7 @@ class Engine {
   std::atomic<int64_t> poison_unknown_span_{0};  // legacy wrapper poison on an estimated span
   std::atomic<int64_t> split_records_{0}, split_fragments_{0};
   std::atomic<int64_t> b64_records_{0};  // records the b64 scan accepted (handed to a decoder)
+  std::atomic<int64_t> yuv_records_{0};  // those of them that carry YUV 4:2:0 frames
   std::atomic<int64_t> sparse_fetches_{0}, restored_fetches_{0};  // bounce receive (pack_tap.h)
   Histogram h_queue_us_, h_device_us_, h_engine_e2e_us_, h_record_e2e_ms_, h_batch_images_;
   Histogram h_slo_win_us_;  // e2e latency of the SLO controller's current window

@@ -134,6 +134,9 @@ class StubReplica : public Replica {
   void set_input_prep(const InputPrep& p) { prep_ = p; }
   // base64 uint8 image records (EngineConfig::input_b64): decoded by the host decoder
   void set_input_b64(bool on) { b64_ = on; }
+  // b64 records that carry YUV 4:2:0 frames (EngineConfig::yuv_format, csrc/codec/yuv.h): decoded
+  // and converted by the host twin (codec::parse_instances_yuv_host); with set_input_b64
+  void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images, parsed
   // and preprocessed at that size into a source buffer and resized into the model-size images by
   // the form's host twin (InputResize::apply_host); the logits stay the function of the
@@ -144,6 +147,8 @@ class StubReplica : public Replica {
  private:
   InputPrep prep_;
   bool b64_ = false;
+  int yuv_format_ = 0;
+  YuvCoeffs yuv_;
   std::optional<InputResize> resize_;
   std::vector<float> src_;  // resize_: the batch's images at the source size
   std::atomic<int64_t> resized_{0};
@@ -208,6 +213,12 @@ class GpuReplica : public Replica {
   // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
   // map, no count pass. Before submit()
   void set_input_b64(bool on) { b64_ = on; }
+  // b64 records that carry YUV 4:2:0 frames (EngineConfig::yuv_format, csrc/codec/yuv.h): the
+  // step runs b64_yuv_instances where it runs b64_decode_instances otherwise - same descriptor
+  // table, status words and output tensor, strings of yuv420_bytes(recH_, recW_) bytes; C must
+  // be 3 and the prep not nchw (the launcher refuses otherwise). With set_input_b64, before
+  // submit()
+  void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images. The
   // tables' device image (pack) is uploaded once and every slot gets a source tensor of
   // max_batch * HS * WS * C floats that never moves (captured steps stay valid); the step's
@@ -272,6 +283,12 @@ class GpuReplica : public Replica {
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
   bool b64_ = false;
+  int yuv_format_ = 0;  // YuvFormat of the b64 strings (0: RGB bytes)
+  YuvCoeffs yuv_;
+  // bytes one b64 string carries
+  int64_t rec_bytes() const {
+    return yuv_format_ ? yuv420_bytes(recH_, recW_) : (int64_t)recH_ * recW_ * C_;
+  }
   // input resize: the tables' device image (one allocation; null = off, the records carry
   // model-size images, recH_ / recW_ == H_ / W_) and the kernel plan bound to it
   uint8_t* d_resize_ = nullptr;

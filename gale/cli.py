@@ -13,6 +13,8 @@
         [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
         [--encoding json|b64]                         b64: base64 uint8 records (--pixels byte)
         [--size H,W]                                  images of that size (--input-size H,W)
+        [--pixel-format rgb|i420|nv12]                YUV 4:2:0 frames (--encoding b64;
+                                                      --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
 
 ``--profile DIR`` re-runs the topology under ``rocprofv3 --kernel-trace --marker-trace --stats``
@@ -61,8 +63,8 @@ def _topology_parser() -> argparse.ArgumentParser:
             ap.add_argument(flag, action=argparse.BooleanOptionalAction, default=None)
         else:
             kw = dict(default=None, type={"int": int, "float": float}.get(t, str))
-            if f.name in CHOICES:
-                kw["choices"] = CHOICES[f.name]
+            if f.name in CHOICES:  # ("" = not given: not a value to type)
+                kw["choices"] = tuple(c for c in CHOICES[f.name] if c)
             if f.name in HELP:
                 kw["help"] = HELP[f.name]
             if f.name == "top_k":
@@ -209,7 +211,8 @@ def produce_shape(input_shape, size: str):
 def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
-                           synthetic_images, synthetic_pixels)
+                           encode_records_yuv, synthetic_images, synthetic_pixels,
+                           synthetic_yuv_planes)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -231,15 +234,30 @@ def cmd_produce(argv: List[str]) -> int:
     ap.add_argument("--size", default="", metavar="H,W",
                     help="size of the synthetic images (default: the model's; serve them with "
                          "--input-size H,W)")
+    ap.add_argument("--pixel-format", default="rgb", choices=CHOICES["input_pixel_format"],
+                    help="i420 / nv12: synthetic YUV 4:2:0 frames of HS*WS*3/2 bytes (serve them "
+                         "with --input-pixel-format); needs --encoding b64, the nhwc layout, a "
+                         "3-channel model and even sizes")
     a = ap.parse_args(argv)
-    if a.encoding == "b64" and a.pixels != "byte":
+    yuv = a.pixel_format != "rgb"
+    if yuv and a.encoding != "b64":
+        ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64")
+    if yuv and a.layout != "nhwc":
+        ap.error(f"--pixel-format {a.pixel_format} has its own plane order: no --layout nchw")
+    if a.encoding == "b64" and a.pixels != "byte" and not yuv:
         ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
     try:
         shape = produce_shape(net.input_shape, a.size)
     except ValueError as e:
         ap.error(str(e))
-    if a.encoding == "b64":
+    if yuv:
+        if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
+            ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
+                     f"{shape}")
+        recs = encode_records_yuv(*synthetic_yuv_planes(a.images, shape[0], shape[1], a.seed),
+                                  a.pixel_format, a.images_per_record)
+    elif a.encoding == "b64":
         recs = encode_records_b64(synthetic_pixels(a.images, shape, a.seed),
                                   a.images_per_record, a.layout)
     elif a.pixels == "unit" and a.layout == "nhwc":

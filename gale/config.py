@@ -40,6 +40,13 @@ CHOICES = {
     # what a record's instances array holds: "json" nested number arrays, "b64" one
     # {"b64": "<base64 of H*W*C uint8 values>"} object per image, decoded on the GPU
     "input_format": ("json", "b64"),
+    # what a b64 record's bytes are: interleaved RGB, or a YUV 4:2:0 video frame (I420: three
+    # planes; NV12: a Y plane and an interleaved UV plane) converted to RGB on the GPU
+    # (gale/models/preprocess.py YuvConvert)
+    "input_pixel_format": ("rgb", "i420", "nv12"),
+    # the YUV formats' matrix and range; "" = not given (bt601, limited)
+    "input_yuv_matrix": ("", "bt601", "bt709"),
+    "input_yuv_range": ("", "limited", "full"),
 }
 
 TOP_K_MAX = 64  # --top-k: one winner per lane of the selection kernel's wave
@@ -56,6 +63,13 @@ HELP = {
                     "model's H,W; S follows torchvision Resize(S): the shorter side of HS,WS "
                     "becomes S, the longer int(S*long/short); default: the model's H,W (plain "
                     "resize, no crop); HR >= H and WR >= W (no padding)",
+    "input_pixel_format": "i420 / nv12: every b64 string is a YUV 4:2:0 frame of HS*WS*3/2 bytes "
+                          "(HS,WS even; the model must have 3 channels), converted to RGB on the "
+                          "GPU; needs --input-format b64 and the nhwc layout; rgb (default): "
+                          "interleaved RGB bytes",
+    "input_yuv_matrix": "bt601 (default) or bt709; only with a YUV --input-pixel-format",
+    "input_yuv_range": "limited (default: Y 16..235, chroma 16..240) or full; only with a YUV "
+                       "--input-pixel-format",
     "input_antialias": "resample with the antialiased (support-scaled triangle) filter of PIL / "
                        "torchvision antialias=True instead of two-tap bilinear; needs an active "
                        "--input-size / --input-resize and a downscale of at most 8x per axis",
@@ -184,6 +198,9 @@ class GaleConfig:
     input_antialias: bool = False      # the antialiased tap filter on both axes (downscale <= 8x)
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
                                        # ingest only with b64_ingest)
+    input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames
+    input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
+    input_yuv_range: str = ""          # limited (default) | full, YUV formats only
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
                                        # the device, strings decoded into the fetch's image
                                        # arena, the table step); needs gpu_ingest, no effect
@@ -279,7 +296,8 @@ class GaleConfig:
             raise ValueError("--b64-ingest needs --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
         # (ValueError naming --input-size / --input-resize / --input-antialias)
-        self.input_resize_plan()
+        rs = self.input_resize_plan()
+        self._validate_pixel_format(rs)
         if self.top_k != 0:
             from gale.models import get_model
 
@@ -289,6 +307,37 @@ class GaleConfig:
                                  f"{min(classes, TOP_K_MAX)} (the smaller of {self.model}'s "
                                  f"{classes} classes and {TOP_K_MAX})")
         return self
+
+    def _validate_pixel_format(self, rs) -> None:
+        """ValueError naming the option for a YUV pixel format that cannot be served."""
+        if self.input_pixel_format == "rgb":
+            for k in ("input_yuv_matrix", "input_yuv_range"):
+                if getattr(self, k):
+                    raise ValueError(f"--{k.replace('_', '-')} applies to the YUV formats only: "
+                                     "it needs --input-pixel-format i420 or nv12")
+            return
+        from gale.models import get_model
+
+        fmt = self.input_pixel_format
+        if self.input_format != "b64":
+            raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64")
+        if self.input_layout != "nhwc":
+            raise ValueError(f"--input-pixel-format {fmt} has its own plane order: "
+                             "--input-layout nchw does not apply")
+        C = get_model(self.model).input_shape[2]
+        if C != 3:
+            raise ValueError(f"--input-pixel-format {fmt} gives 3-channel RGB; {self.model} "
+                             f"takes C = {C}")
+        if rs.HS % 2 or rs.WS % 2:
+            opt = "--input-size" if self.input_size else "--input-pixel-format"
+            raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
+                             f"HS,WS, got {rs.HS},{rs.WS}")
+
+    def input_yuv(self):
+        """The ``YuvConvert`` of this configuration, None for rgb."""
+        from gale.models.preprocess import YuvConvert
+
+        return YuvConvert.from_config(self)
 
     def input_prep(self, C: Optional[int] = None):
         """The ``InputPrep`` of this configuration (C: the model's input channels)."""
@@ -365,7 +414,8 @@ class GaleConfig:
             restart_backoff_ms=self.restart_backoff_ms, fault=self.fault, seed=self.seed,
             trace=self.trace, input_format=self.input_format, b64_ingest=self.b64_ingest,
             **self.input_prep(C).engine_entries(),
-            **self.input_resize_plan(H, W).engine_entries())
+            **self.input_resize_plan(H, W).engine_entries(),
+            **(self.input_yuv().engine_entries() if self.input_yuv() else {}))
 
 
 def _pack_fast() -> bool:

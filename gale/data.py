@@ -74,6 +74,49 @@ def encode_records_b64(images_u8: np.ndarray, images_per_record: int = 1,
     return out
 
 
+def pack_yuv420(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str) -> np.ndarray:
+    """uint8 planes Y [N, HS, WS], U / V [N, HS/2, WS/2] -> uint8 [N, HS*WS*3/2] frames: I420
+    (Y, U, V planes) or NV12 (Y plane, interleaved UV plane)."""
+    Y, U, V = (np.asarray(p) for p in (Y, U, V))
+    if any(p.dtype != np.uint8 or p.ndim != 3 for p in (Y, U, V)):
+        raise ValueError("pack_yuv420: uint8 [N, rows, cols] planes")
+    N, HS, WS = Y.shape
+    if HS % 2 or WS % 2 or U.shape != (N, HS // 2, WS // 2) or V.shape != U.shape:
+        raise ValueError(f"pack_yuv420: Y {Y.shape} needs even sizes and U, V of "
+                         f"{(N, HS // 2, WS // 2)}, got {U.shape}, {V.shape}")
+    if pixel_format == "i420":
+        chroma = [U.reshape(N, -1), V.reshape(N, -1)]
+    elif pixel_format == "nv12":
+        chroma = [np.stack([U, V], axis=-1).reshape(N, -1)]
+    else:
+        raise ValueError(f"pixel_format={pixel_format!r}: expected i420 or nv12")
+    return np.ascontiguousarray(np.concatenate([Y.reshape(N, -1), *chroma], axis=1))
+
+
+def encode_records_yuv(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str,
+                       images_per_record: int = 1) -> List[bytes]:
+    """uint8 planes (``pack_yuv420``) -> ``{"instances":[{"b64":"..."},...]}`` records of YUV
+    4:2:0 frames (--input-format b64 --input-pixel-format i420 | nv12): each frame's HS*WS*3/2
+    bytes in standard base64 (never padded: the byte count is a multiple of 3)."""
+    frames = pack_yuv420(Y, U, V, pixel_format)
+    out = []
+    for i in range(0, frames.shape[0], images_per_record):
+        elems = [b'{"b64":"' + base64.b64encode(fr.tobytes()) + b'"}'
+                 for fr in frames[i:i + images_per_record]]
+        out.append(b'{"instances":[' + b",".join(elems) + b"]}")
+    return out
+
+
+def synthetic_yuv_planes(n: int, HS: int, WS: int, seed: int = 0):
+    """Deterministic uint8 planes (Y [n, HS, WS], U, V [n, HS/2, WS/2]) of synthetic frames."""
+    if HS % 2 or WS % 2:
+        raise ValueError(f"a 4:2:0 frame needs even sizes, got {HS},{WS}")
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 256, (n, HS, WS), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS // 2, WS // 2), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS // 2, WS // 2), dtype=np.uint8))
+
+
 def encode_batches(records: Sequence[bytes], records_per_batch: int = 64) -> List[bytes]:
     """Group records into Kafka RecordBatch v2 blobs (for the broker's shared-append preload)."""
     K = native().kafka

@@ -94,8 +94,13 @@ class Engine:
                      "image arena and the table step address model-size images); the batch step "
                      "parses from the resident mirror and resizes", resize.HS, resize.WS,
                      resize.HR, resize.WR, H, W)
+        yuv = cfg.input_pixel_format != "rgb"
+        if yuv and ingest and cfg.ingest_parse and not resize.active:  # (one line for the rule)
+            log.info("input pixel format %s: the GPU ingest does not decode (its b64 decode and "
+                     "image arena hold RGB strings' images): CRC-only; the batch step decodes "
+                     "and converts from the resident mirror", cfg.input_pixel_format)
         d["ingest_parse"] = bool(
-            not resize.active and (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
+            not resize.active and not yuv and (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
             and cfg.use_graph and cfg.graph_step and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"
             and reps and all(getattr(r.executor, "step_out_ok", False) for r in reps))
         if (len(devs) > 1 or cfg.locality_split > 1) and cfg.numa_pin:

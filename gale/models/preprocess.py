@@ -14,6 +14,10 @@ Host (``codec::apply_input_prep``) and device (``json_parse_prep_kernel``) resul
 bit-identical. ``layout="nchw"`` says the record's ``instances`` array nests ``[N][C][H][W]``;
 the model's tensors stay NHWC.
 
+``YuvConvert`` (below) defines what may come first: ``b64`` records that carry YUV 4:2:0 video
+frames (``--input-pixel-format i420 | nv12``) are converted to 0..255 RGB in integers before the
+fma above.
+
 ``InputResize`` (below) defines the step that may follow: records that carry images of another
 size are resized (bilinear, or with ``antialias`` the support-scaled triangle filter) and
 centre-cropped to the model's on the preprocessed values.
@@ -21,6 +25,7 @@ centre-cropped to the model's on the preprocessed values.
 
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
@@ -376,6 +381,130 @@ class InputResize:
 
             return torch.from_numpy(out)
         return out
+
+
+PIXEL_FORMATS = ("rgb", "i420", "nv12")
+YUV_MATRICES = ("bt601", "bt709")
+YUV_RANGES = ("limited", "full")
+YUV_SHIFT = 20  # the coefficients' fixed point
+
+
+@functools.lru_cache(maxsize=None)
+def _yuv_rationals(matrix: str, range_: str):
+    """(sy, crv, cgu, cgv, cbu) of the real-valued matrix, as exact fractions."""
+    from fractions import Fraction as F
+
+    kr, kb = {"bt601": (F(299, 1000), F(114, 1000)),
+              "bt709": (F(2126, 10000), F(722, 10000))}[matrix]
+    kg = 1 - kr - kb
+    sy, sc = {"limited": (F(255, 219), F(255, 224)), "full": (F(1), F(1))}[range_]
+    return (sy, 2 * (1 - kr) * sc, -2 * kb * (1 - kb) / kg * sc, -2 * kr * (1 - kr) / kg * sc,
+            2 * (1 - kb) * sc)
+
+
+def _round_half_even(q) -> int:
+    n, d = q.numerator, q.denominator
+    fl, rem = divmod(n, d)
+    if 2 * rem > d or (2 * rem == d and fl % 2):
+        return fl + 1
+    return fl
+
+
+@dataclass(frozen=True)
+class YuvConvert:
+    """YUV 4:2:0 frames (``--input-pixel-format i420 | nv12``) to RGB, in integers.
+
+    A frame of HS x WS pixels (both even) is ``B = HS*WS*3/2`` bytes: I420 ``Y[HS][WS]``,
+    ``U[HS/2][WS/2]``, ``V[HS/2][WS/2]``; NV12 ``Y[HS][WS]``, ``UV[HS/2][WS/2][2]``. Pixel (y, x)
+    takes ``Y[y][x]`` and the chroma sample ``(y >> 1, x >> 1)`` (nearest neighbour). With
+    ``yo = 16`` (limited) or 0 (full), in signed 32-bit arithmetic (``>>``: arithmetic shift)::
+
+        R = clamp((cy (Y - yo)                  + crv (V - 128) + 2^19) >> 20, 0, 255)
+        G = clamp((cy (Y - yo) + cgu (U - 128) + cgv (V - 128) + 2^19) >> 20, 0, 255)
+        B = clamp((cy (Y - yo) + cbu (U - 128)                  + 2^19) >> 20, 0, 255)
+
+    The coefficients are the exact rationals ``sy``, ``2(1-Kr) sc``, ``-2Kb(1-Kb)/Kg sc``,
+    ``-2Kr(1-Kr)/Kg sc``, ``2(1-Kb) sc`` times 2^20, rounded half to even (Kg = 1 - Kr - Kb;
+    bt601 Kr, Kb = 0.299, 0.114; bt709 0.2126, 0.0722; limited sy = 255/219, sc = 255/224; full
+    1, 1). ``codec::yuv420_to_rgb_host`` (csrc/codec/yuv.h, which holds them as literals) and the
+    ``b64_yuv_instances`` kernel give the same bits. There is no pre-clamp of ``Y - yo``."""
+
+    format: str = "i420"
+    matrix: str = "bt601"
+    range: str = "limited"
+
+    def __post_init__(self):
+        if self.format not in PIXEL_FORMATS[1:]:
+            raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
+                             f"{PIXEL_FORMATS[1:]} for a YUV conversion")
+        if self.matrix not in YUV_MATRICES:
+            raise ValueError(f"input_yuv_matrix={self.matrix!r}: expected one of {YUV_MATRICES}")
+        if self.range not in YUV_RANGES:
+            raise ValueError(f"input_yuv_range={self.range!r}: expected one of {YUV_RANGES}")
+
+    @classmethod
+    def from_config(cls, cfg) -> Optional["YuvConvert"]:
+        """The conversion of a configuration, None for ``rgb``. (GaleConfig.validate refuses the
+        combinations that have none.)"""
+        if cfg.input_pixel_format == "rgb":
+            return None
+        return cls(cfg.input_pixel_format, cfg.input_yuv_matrix or "bt601",
+                   cfg.input_yuv_range or "limited")
+
+    def rationals(self):
+        return _yuv_rationals(self.matrix, self.range)
+
+    @property
+    def yo(self) -> int:
+        return 16 if self.range == "limited" else 0
+
+    def coeffs(self) -> Tuple[int, int, int, int, int]:
+        """(cy, crv, cgu, cgv, cbu)."""
+        return tuple(_round_half_even(q * (1 << YUV_SHIFT)) for q in self.rationals())
+
+    @staticmethod
+    def frame_bytes(HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or HS % 2 or WS % 2:
+            raise ValueError(f"a 4:2:0 frame needs even, positive sizes, got {HS},{WS}")
+        return HS * WS * 3 // 2
+
+    def engine_entries(self) -> Dict[str, Any]:
+        return dict(pixel_format=self.format, yuv_matrix=self.matrix, yuv_range=self.range)
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``b64_yuv_instances`` binding."""
+        return dict(format=self.format, coeffs=[*self.coeffs(), self.yo])
+
+    def accumulators(self, Y, U, V):
+        """The three int64 accumulators (rounding term included) of int arrays Y, U, V."""
+        cy, crv, cgu, cgv, cbu = self.coeffs()
+        Y, U, V = (np.asarray(v).astype(np.int64) for v in (Y, U, V))
+        yy = cy * (Y - self.yo) + (1 << (YUV_SHIFT - 1))
+        u, v = U - 128, V - 128
+        return yy + crv * v, yy + cgu * u + cgv * v, yy + cbu * u
+
+    def planes(self, frame, HS: int, WS: int):
+        """uint8 [..., B] frames -> (Y [..., HS, WS], U, V [..., HS/2, WS/2])."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        lead, hw = f.shape[:-1], HS * WS
+        Y = f[..., :hw].reshape(*lead, HS, WS)
+        if self.format == "nv12":
+            uv = f[..., hw:].reshape(*lead, HS // 2, WS // 2, 2)
+            return Y, uv[..., 0], uv[..., 1]
+        U = f[..., hw:hw + hw // 4].reshape(*lead, HS // 2, WS // 2)
+        V = f[..., hw + hw // 4:].reshape(*lead, HS // 2, WS // 2)
+        return Y, U, V
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint8 [..., HS, WS, 3] RGB."""
+        Y, U, V = self.planes(frame, HS, WS)
+        up = lambda c: np.repeat(np.repeat(c, 2, axis=-2), 2, axis=-1)  # noqa: E731
+        acc = self.accumulators(Y, up(U), up(V))
+        assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
+        return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
 
 
 def prep_or_none(prep: Optional[InputPrep]) -> Optional[InputPrep]:
