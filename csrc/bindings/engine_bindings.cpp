@@ -115,10 +115,14 @@ EngineConfig config_from_dict(const py::dict& d) {
     opt(d, "pixel_format", pf);
     opt(d, "yuv_matrix", ym);
     opt(d, "yuv_range", yr);
-    c.yuv_format = pf == "rgb"    ? (int)YUV_NONE
-                   : pf == "i420" ? (int)YUV_I420
-                   : pf == "nv12" ? (int)YUV_NV12
-                                  : throw std::invalid_argument("pixel_format: rgb, i420 or nv12");
+    // (the packed formats of csrc/codec/pixfmt.h: bgr24, rgba, bgra, gray)
+    c.packed_format = packed_format_of(pf.c_str());
+    if (pf == "i420" || pf == "nv12")
+      c.yuv_format = pf == "i420" ? (int)YUV_I420 : (int)YUV_NV12;
+    else if (pf != "rgb" && !c.packed_format)
+      throw std::invalid_argument("pixel_format: rgb, i420, nv12, bgr24, rgba, bgra or gray");
+    if (c.packed_format && (d.contains("yuv_matrix") || d.contains("yuv_range")))
+      throw std::invalid_argument("yuv_matrix / yuv_range need pixel_format i420 or nv12");
     if (!yuv_coeffs(ym == "bt601" ? 0 : ym == "bt709" ? 1 : -1,
                     yr == "limited" ? 0 : yr == "full" ? 1 : -1, &c.yuv))
       throw std::invalid_argument("yuv_matrix: bt601 or bt709; yuv_range: limited or full");
@@ -152,6 +156,13 @@ EngineConfig config_from_dict(const py::dict& d) {
     // the ingest's b64 decode and its arena hold RGB strings' images: CRC-only
     c.ingest_parse = false;
   }
+  if (c.packed_format) {
+    const std::string what = "pixel_format bgr24 / rgba / bgra / gray";
+    if (!c.input_b64) throw std::invalid_argument(what + " needs input_format b64");
+    if (c.prep.nchw) throw std::invalid_argument(what + ": no nchw layout");
+    if (c.C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
+    c.ingest_parse = false;  // (as for YUV)
+  }
   return c;
 }
 
@@ -174,6 +185,7 @@ void bind_engine(py::module_& m) {
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
              rep->set_input_yuv(c.yuv_format, c.yuv);
+             rep->set_input_packed(c.packed_format);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },
@@ -191,6 +203,7 @@ void bind_engine(py::module_& m) {
              rep->set_input_prep(c.prep);
              rep->set_input_b64(c.input_b64);
              rep->set_input_yuv(c.yuv_format, c.yuv);
+             rep->set_input_packed(c.packed_format);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },

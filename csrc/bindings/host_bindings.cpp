@@ -742,6 +742,49 @@ void bind_host(py::module_& m) {
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
         py::arg("max_images") = -1);
+  // ---- packed pixel formats (csrc/codec/pixfmt.h) ----
+  m.def("packed_bpp", [](const std::string& format) {
+    return packed_bpp(packed_format_of(format.c_str()));
+  });
+  m.def("packed_to_rgb_host",
+        [](py::bytes image, int HS, int WS, const std::string& format,
+           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b) {
+          // one image -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep (3+ values)
+          const std::string_view s = view(image);
+          if ((a && a->size() < 3) || (b && b->size() < 3) || bool(a) != bool(b))
+            throw std::invalid_argument("packed_to_rgb_host: a / b (>= 3 each)");
+          const int fmt = packed_format_of(format.c_str());
+          if (fmt == PACKED_NONE || HS <= 0 || WS <= 0 ||
+              (int64_t)s.size() != packed_bytes(HS, WS, fmt))
+            throw std::invalid_argument("packed_to_rgb_host: format / size / byte count");
+          py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          codec::packed_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, fmt,
+                                    rgb.mutable_data(), f32.mutable_data(),
+                                    a ? a->data() : nullptr, b ? b->data() : nullptr);
+          return py::make_tuple(rgb, f32);
+        },
+        py::arg("image"), py::arg("HS"), py::arg("WS"), py::arg("format"),
+        py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("parse_instances_packed_host",
+        [](py::bytes b, int HS, int WS, const std::string& format, int max_images) {
+          // (status, float32 [N, HS, WS, 3]: (float)RGB of every image)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          const int fmt = packed_format_of(format.c_str());
+          int n = 0;
+          int st = codec::parse_instances_packed_host(p, s.size(), HS, WS, fmt, nullptr,
+                                                      max_images, &n);
+          if (st != codec::OK) n = 0;
+          py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
+                                  (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
+          if (st == codec::OK)
+            st = codec::parse_instances_packed_host(p, s.size(), HS, WS, fmt, out.mutable_data(),
+                                                    max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"),
+        py::arg("max_images") = -1);
   m.def("apply_input_prep",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
            bool nchw, std::vector<float> a, std::vector<float> b) {

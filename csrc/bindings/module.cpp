@@ -330,6 +330,33 @@ PYBIND11_MODULE(_C, m) {
         py::arg("coeffs") = std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
         py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false,
         py::arg("pairs") = 0);
+  m.def("b64_packed_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,
+           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b, bool nchw) {
+          // imgs / d_images / a / b / nchw: as b64_decode_instances. format: "bgr24" | "rgba" |
+          // "bgra" | "gray" (anything else reaches the launcher as an unknown format). Returns
+          // the launcher's hipError_t as an int (0 = launched): its refusals are part of the
+          // contract, so they do not throw
+          gale::InputPrep prep;
+          const bool with_prep = a || b || nchw;
+          if ((a && a->size() != 4) || (b && b->size() != 4))
+            throw std::invalid_argument("b64_packed_instances: a / b take four coefficients");
+          for (int i = 0; i < 4; ++i) {
+            if (a) prep.a[i] = (*a)[i];
+            if (b) prep.b[i] = (*b)[i];
+          }
+          prep.nchw = nchw ? 1 : 0;
+          return (int)gale::b64_packed_instances(
+              images, static_cast<const gale::B64Image*>(P(imgs)),
+              static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+              static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+              with_prep ? &prep : nullptr, gale::packed_format_of(format.c_str()));
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("format") = "bgr24", py::arg("a") = py::none(),
+        py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("b64_yuv_pairs", &gale::b64_yuv_pairs);
   m.def("b64_yuv_lds_bytes", &gale::b64_yuv_lds_bytes);
   m.attr("YUV_LDS_BUDGET") = (int)gale::kYuvLdsBudget;

@@ -562,6 +562,47 @@ int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int for
   return OK;
 }
 
+int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                float* out, int max_images, int* images) {
+  static const B64Table table;
+  *images = 0;
+  const int64_t B = packed_bytes(HS, WS, format);
+  if (B <= 0) return BAD_SHAPE;
+  const Scan s = scan_instances_b64_bytes(p, n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  std::vector<B64Elem> elems;
+  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, B, elems);
+  if (st != OK) return st;
+  // (padding judged as parse_instances_b64_host judges it)
+  const size_t L = (size_t)b64_chars_bytes(B), pad = (3 - (size_t)B % 3) % 3;
+  std::vector<uint8_t> image(L / 4 * 3);
+  const size_t per = (size_t)HS * WS * 3;
+  for (size_t e = 0; e < elems.size(); ++e) {
+    const uint8_t* q = p + s.arr_off + elems[e].str;
+    for (size_t g = 0; g < L; g += 4) {
+      uint32_t v = 0;
+      for (size_t j = 0; j < 4; ++j) {
+        uint8_t x = table.v[q[g + j]];
+        if (g + j >= L - pad) {
+          if (q[g + j] != '=') return BAD_NUMBER;
+          x = 0;
+        } else if (x == 0xFF) {
+          return BAD_NUMBER;
+        }
+        v = (v << 6) | x;
+      }
+      const size_t o = g / 4 * 3;
+      image[o] = (uint8_t)(v >> 16);
+      image[o + 1] = (uint8_t)(v >> 8);
+      image[o + 2] = (uint8_t)v;
+    }
+    if (out) packed_to_rgb_host(image.data(), HS, WS, format, nullptr, out + e * per);
+  }
+  *images = s.images;
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

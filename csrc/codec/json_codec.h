@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "pixfmt.h"
 #include "yuv.h"
 
 namespace gale {
@@ -135,6 +136,16 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
 // are BAD_SHAPE. out may be null.
 int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                              const YuvCoeffs& k, float* out, int max_images, int* images);
+
+// Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
+// envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes
+// (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3 of them '='; a character outside
+// the alphabet in the data part or a non-'=' in the padding is BAD_NUMBER), every image unpacked
+// by packed_to_rgb_host into out[N][HS][WS][3] as (float)RGB - what parse_instances_b64_host
+// gives for the unpacked image sent as an RGB record. An unknown format or a non-positive size
+// is BAD_SHAPE. out may be null.
+int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                float* out, int max_images, int* images);
 
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.

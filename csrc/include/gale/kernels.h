@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../codec/pixfmt.h"  // PackedFormat (no HIP: shared with the host codec)
 #include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
 
 namespace gale {
@@ -340,6 +341,23 @@ hipError_t b64_yuv_instances(int images, const B64Image* imgs, const uint8_t* by
                              int WS, int C, float* out, int* status, hipStream_t stream,
                              const int* d_images, const InputPrep* prep, int format,
                              const YuvCoeffs& coeffs, int pairs = 0);
+
+// GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
+// "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard
+// base64, B = HS*WS*P bytes (csrc/codec/pixfmt.h), padded like an RGB string - becomes the
+// HS*WS*3 floats of its RGB image in the fp32 NHWC batch tensor: the bits b64_decode_instances
+// gives for the unpacked image sent as an RGB record with the same prep (whose coefficients are
+// indexed by model channel, R, G, B). Alpha is dropped. imgs, status (2 for a character outside
+// the alphabet in the data part or a non-'=' in the padding of one of the record's strings; the
+// image is written anyway, within its own slot), d_images, the grid and the read bounds around a
+// string are b64_decode_instances'. 16-byte stores when the image's base is 16-byte aligned, one
+// float per lane otherwise; both contiguous over a wave.
+// hipErrorInvalidValue, before any launch: non-positive HS / WS, C != 3, a null pointer, an
+// unknown format, an nchw prep, more than 65535 images, an image of more than 2^30 floats.
+// images == 0 launches nothing.
+hipError_t b64_packed_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                int WS, int C, float* out, int* status, hipStream_t stream,
+                                const int* d_images, const InputPrep* prep, int format);
 
 // ---- input resize (resize_crop.hip) ---------------------------------------------------------
 // Bilinear resize (half-pixel centres, no antialiasing) + centre crop of fp32 NHWC images:

@@ -984,10 +984,12 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   try {
     if (b64)
       // (a YUV frame's string is that of an (HS / 2) x WS x 3 byte image to the ingest's plan,
-      // which checks it against its record; there is no arena, so nothing is decoded)
+      // which checks it against its record; a packed-pixel string is that of an HS x WS x P one;
+      // there is no arena, so nothing is decoded)
       ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
-                      cfg_.yuv_format ? cfg_.rec_h() / 2 : cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io,
-                      arena, arena_bytes);
+                      cfg_.yuv_format ? cfg_.rec_h() / 2 : cfg_.rec_h(), cfg_.rec_w(),
+                      cfg_.packed_format ? packed_bpp(cfg_.packed_format) : cfg_.C, io, arena,
+                      arena_bytes);
     else
       ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
                   cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
@@ -998,6 +1000,7 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   }
   b64_records_ += b64_accepted;  // (as the host path: records the scan accepted)
   if (cfg_.yuv_format) yuv_records_ += b64_accepted;
+  if (cfg_.packed_format) packed_records_ += b64_accepted;
   std::vector<char> corrupt(n, 0);
   for (size_t b = 0; b < f.batches.size(); ++b)
     if (!io.batch_ok[b])
@@ -1137,6 +1140,7 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       if (b64 && r.status == codec::OK) {
         ++b64_records_;
         if (cfg_.yuv_format) ++yuv_records_;
+        if (cfg_.packed_format) ++packed_records_;
       }
     }
     if (r.status == codec::OK && r.images > cfg_.max_batch) {
@@ -1815,6 +1819,7 @@ std::map<std::string, double> Engine::stats() const {
   s["split_records"] = (double)split_records_;
   s["b64_records"] = (double)b64_records_;
   s["yuv_records"] = (double)yuv_records_;
+  s["packed_records"] = (double)packed_records_;
   s["sparse_fetches"] = (double)sparse_fetches_;
   s["restored_fetches"] = (double)restored_fetches_;
   {

@@ -163,9 +163,15 @@ struct EngineConfig {
   // in its CRC-only form (ingest_parse off): the step decodes from the resident mirror
   int yuv_format = 0;
   YuvCoeffs yuv;
+  // PACKED_BGR24 / PACKED_RGBA / PACKED_BGRA / PACKED_GRAY (csrc/codec/pixfmt.h): every string
+  // is rec_h() x rec_w() pixels of packed_bpp bytes, unpacked to RGB where the strings are
+  // decoded (C == 3, no nchw, not with yuv_format). The GPU ingest rule is the YUV one: CRC-only
+  int packed_format = 0;
   // bytes one b64 string carries
   int64_t rec_bytes() const {
-    return yuv_format ? yuv420_bytes(rec_h(), rec_w()) : (int64_t)rec_h() * rec_w() * C;
+    return packed_format ? packed_bytes(rec_h(), rec_w(), packed_format)
+           : yuv_format  ? yuv420_bytes(rec_h(), rec_w())
+                         : (int64_t)rec_h() * rec_w() * C;
   }
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
@@ -448,6 +454,7 @@ class Engine {
   std::atomic<int64_t> split_records_{0}, split_fragments_{0};
   std::atomic<int64_t> b64_records_{0};  // records the b64 scan accepted (handed to a decoder)
   std::atomic<int64_t> yuv_records_{0};  // those of them that carry YUV 4:2:0 frames
+  std::atomic<int64_t> packed_records_{0};  // those that carry bgr24 / rgba / bgra / gray pixels
   std::atomic<int64_t> sparse_fetches_{0}, restored_fetches_{0};  // bounce receive (pack_tap.h)
   Histogram h_queue_us_, h_device_us_, h_engine_e2e_us_, h_record_e2e_ms_, h_batch_images_;
   Histogram h_slo_win_us_;  // e2e latency of the SLO controller's current window

@@ -450,7 +450,14 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
     c = hipMemcpyAsync(s.d_meta + m.off, s.h_meta + m.off, m.bytes, hipMemcpyHostToDevice, st);
     if (c != hipSuccess) return {c, "H2D step metadata"};
   }
-  if (parse && b64_ && yuv_format_) {
+  if (parse && b64_ && packed_format_) {
+    // packed pixels: the same table, status words and output as the RGB decode below
+    c = b64_packed_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
+                             s.d_bytes, recH_, recW_, C_, parsed,
+                             status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
+                             dev ? hdr + kHdrB64 : nullptr, &prep_, packed_format_);
+    if (c != hipSuccess) return {c, "b64_packed_instances"};
+  } else if (parse && b64_ && yuv_format_) {
     // YUV 4:2:0 frames: the same table, status words and output as the RGB decode below
     c = b64_yuv_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table), s.d_bytes,
                           recH_, recW_, C_, parsed,

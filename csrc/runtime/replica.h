@@ -137,6 +137,10 @@ class StubReplica : public Replica {
   // b64 records that carry YUV 4:2:0 frames (EngineConfig::yuv_format, csrc/codec/yuv.h): decoded
   // and converted by the host twin (codec::parse_instances_yuv_host); with set_input_b64
   void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
+  // b64 records that carry packed pixels (EngineConfig::packed_format, csrc/codec/pixfmt.h):
+  // decoded and unpacked by the host twin (codec::parse_instances_packed_host); with
+  // set_input_b64
+  void set_input_packed(int format) { packed_format_ = format; }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images, parsed
   // and preprocessed at that size into a source buffer and resized into the model-size images by
   // the form's host twin (InputResize::apply_host); the logits stay the function of the
@@ -149,6 +153,7 @@ class StubReplica : public Replica {
   bool b64_ = false;
   int yuv_format_ = 0;
   YuvCoeffs yuv_;
+  int packed_format_ = 0;
   std::optional<InputResize> resize_;
   std::vector<float> src_;  // resize_: the batch's images at the source size
   std::atomic<int64_t> resized_{0};
@@ -219,6 +224,11 @@ class GpuReplica : public Replica {
   // be 3 and the prep not nchw (the launcher refuses otherwise). With set_input_b64, before
   // submit()
   void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
+  // b64 records that carry packed pixels (EngineConfig::packed_format, csrc/codec/pixfmt.h): the
+  // step runs b64_packed_instances there - same descriptor table, status words and output
+  // tensor, strings of packed_bytes(recH_, recW_, format) bytes; C must be 3 and the prep not
+  // nchw (the launcher refuses otherwise). With set_input_b64, before submit()
+  void set_input_packed(int format) { packed_format_ = format; }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images. The
   // tables' device image (pack) is uploaded once and every slot gets a source tensor of
   // max_batch * HS * WS * C floats that never moves (captured steps stay valid); the step's
@@ -285,9 +295,12 @@ class GpuReplica : public Replica {
   bool b64_ = false;
   int yuv_format_ = 0;  // YuvFormat of the b64 strings (0: RGB bytes)
   YuvCoeffs yuv_;
+  int packed_format_ = 0;  // PackedFormat of the b64 strings (0: none)
   // bytes one b64 string carries
   int64_t rec_bytes() const {
-    return yuv_format_ ? yuv420_bytes(recH_, recW_) : (int64_t)recH_ * recW_ * C_;
+    return packed_format_ ? packed_bytes(recH_, recW_, packed_format_)
+           : yuv_format_  ? yuv420_bytes(recH_, recW_)
+                          : (int64_t)recH_ * recW_ * C_;
   }
   // input resize: the tables' device image (one allocation; null = off, the records carry
   // model-size images, recH_ / recW_ == H_ / W_) and the kernel plan bound to it

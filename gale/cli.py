@@ -13,8 +13,9 @@
         [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
         [--encoding json|b64]                         b64: base64 uint8 records (--pixels byte)
         [--size H,W]                                  images of that size (--input-size H,W)
-        [--pixel-format rgb|i420|nv12]                YUV 4:2:0 frames (--encoding b64;
-                                                      --input-pixel-format)
+        [--pixel-format rgb|i420|nv12|bgr24|rgba|bgra|gray]
+                                                      YUV 4:2:0 frames / packed pixels
+                                                      (--encoding b64; --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
 
 ``--profile DIR`` re-runs the topology under ``rocprofv3 --kernel-trace --marker-trace --stats``
@@ -209,10 +210,12 @@ def produce_shape(input_shape, size: str):
 
 
 def cmd_produce(argv: List[str]) -> int:
+    import numpy as np
+
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
-                           encode_records_yuv, synthetic_images, synthetic_pixels,
-                           synthetic_yuv_planes)
+                           encode_records_packed, encode_records_yuv, synthetic_images,
+                           synthetic_pixels, synthetic_yuv_planes)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -237,13 +240,19 @@ def cmd_produce(argv: List[str]) -> int:
     ap.add_argument("--pixel-format", default="rgb", choices=CHOICES["input_pixel_format"],
                     help="i420 / nv12: synthetic YUV 4:2:0 frames of HS*WS*3/2 bytes (serve them "
                          "with --input-pixel-format); needs --encoding b64, the nhwc layout, a "
-                         "3-channel model and even sizes")
+                         "3-channel model and even sizes; bgr24 / rgba / bgra / gray: the "
+                         "synthetic pixels of rgb in that byte order (alpha random; gray: their "
+                         "first channel alone); needs --encoding b64, the nhwc layout and a "
+                         "3-channel model")
     a = ap.parse_args(argv)
-    yuv = a.pixel_format != "rgb"
-    if yuv and a.encoding != "b64":
+    packed = a.pixel_format in ("bgr24", "rgba", "bgra", "gray")
+    yuv = a.pixel_format != "rgb" and not packed
+    if (yuv or packed) and a.encoding != "b64":
         ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64")
     if yuv and a.layout != "nhwc":
         ap.error(f"--pixel-format {a.pixel_format} has its own plane order: no --layout nchw")
+    if packed and a.layout != "nhwc":
+        ap.error(f"--pixel-format {a.pixel_format} has its own byte order: no --layout nchw")
     if a.encoding == "b64" and a.pixels != "byte" and not yuv:
         ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
@@ -257,6 +266,17 @@ def cmd_produce(argv: List[str]) -> int:
                      f"{shape}")
         recs = encode_records_yuv(*synthetic_yuv_planes(a.images, shape[0], shape[1], a.seed),
                                   a.pixel_format, a.images_per_record)
+    elif packed:
+        if shape[2] != 3:
+            ap.error(f"--pixel-format {a.pixel_format} needs a 3-channel model, got {shape}")
+        px = synthetic_pixels(a.images, shape, a.seed)  # (what --pixel-format rgb sends)
+        alpha = None
+        if a.pixel_format == "gray":
+            px = np.repeat(px[..., :1], 3, axis=-1)
+        elif a.pixel_format != "bgr24":
+            alpha = np.random.default_rng(a.seed + 1).integers(0, 256, px.shape[:3],
+                                                               dtype=np.uint8)
+        recs = encode_records_packed(px, a.pixel_format, a.images_per_record, alpha)
     elif a.encoding == "b64":
         recs = encode_records_b64(synthetic_pixels(a.images, shape, a.seed),
                                   a.images_per_record, a.layout)

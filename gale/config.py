@@ -42,8 +42,10 @@ CHOICES = {
     "input_format": ("json", "b64"),
     # what a b64 record's bytes are: interleaved RGB, or a YUV 4:2:0 video frame (I420: three
     # planes; NV12: a Y plane and an interleaved UV plane) converted to RGB on the GPU
-    # (gale/models/preprocess.py YuvConvert)
-    "input_pixel_format": ("rgb", "i420", "nv12"),
+    # (gale/models/preprocess.py YuvConvert), or packed pixels (bgr24 / rgba / bgra: the named
+    # byte order, alpha ignored; gray: one byte a pixel, replicated) unpacked to RGB on the GPU
+    # (PixelUnpack). The names are ffmpeg's pix_fmts
+    "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray"),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -65,8 +67,12 @@ HELP = {
                     "resize, no crop); HR >= H and WR >= W (no padding)",
     "input_pixel_format": "i420 / nv12: every b64 string is a YUV 4:2:0 frame of HS*WS*3/2 bytes "
                           "(HS,WS even; the model must have 3 channels), converted to RGB on the "
-                          "GPU; needs --input-format b64 and the nhwc layout; rgb (default): "
-                          "interleaved RGB bytes",
+                          "GPU; bgr24 / rgba / bgra / gray: every b64 string is HS*WS pixels of "
+                          "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
+                          "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
+                          "--input-mean / --input-std stay in R,G,B order; all of them need "
+                          "--input-format b64 and the nhwc layout; rgb (default): interleaved RGB "
+                          "bytes",
     "input_yuv_matrix": "bt601 (default) or bt709; only with a YUV --input-pixel-format",
     "input_yuv_range": "limited (default: Y 16..235, chroma 16..240) or full; only with a YUV "
                        "--input-pixel-format",
@@ -198,7 +204,8 @@ class GaleConfig:
     input_antialias: bool = False      # the antialiased tap filter on both axes (downscale <= 8x)
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
                                        # ingest only with b64_ingest)
-    input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames
+    input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames;
+                                       # bgr24 | rgba | bgra | gray: packed pixels
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
@@ -309,26 +316,31 @@ class GaleConfig:
         return self
 
     def _validate_pixel_format(self, rs) -> None:
-        """ValueError naming the option for a YUV pixel format that cannot be served."""
-        if self.input_pixel_format == "rgb":
+        """ValueError naming the option for a YUV or packed pixel format that cannot be served."""
+        fmt = self.input_pixel_format
+        yuv = fmt in ("i420", "nv12")
+        if not yuv:
             for k in ("input_yuv_matrix", "input_yuv_range"):
                 if getattr(self, k):
                     raise ValueError(f"--{k.replace('_', '-')} applies to the YUV formats only: "
                                      "it needs --input-pixel-format i420 or nv12")
+        if fmt == "rgb":
             return
         from gale.models import get_model
 
-        fmt = self.input_pixel_format
         if self.input_format != "b64":
             raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64")
         if self.input_layout != "nhwc":
-            raise ValueError(f"--input-pixel-format {fmt} has its own plane order: "
+            raise ValueError(f"--input-pixel-format {fmt} has its own "
+                             f"{'plane' if yuv else 'byte'} order: "
                              "--input-layout nchw does not apply")
         C = get_model(self.model).input_shape[2]
         if C != 3:
+            hint = ("; --input-pixel-format rgb already carries one byte per pixel for a "
+                    "1-channel model" if fmt == "gray" and C == 1 else "")
             raise ValueError(f"--input-pixel-format {fmt} gives 3-channel RGB; {self.model} "
-                             f"takes C = {C}")
-        if rs.HS % 2 or rs.WS % 2:
+                             f"takes C = {C}{hint}")
+        if yuv and (rs.HS % 2 or rs.WS % 2):
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
@@ -338,6 +350,12 @@ class GaleConfig:
         from gale.models.preprocess import YuvConvert
 
         return YuvConvert.from_config(self)
+
+    def input_unpack(self):
+        """The ``PixelUnpack`` of this configuration, None for rgb and the YUV formats."""
+        from gale.models.preprocess import PixelUnpack
+
+        return PixelUnpack.from_config(self)
 
     def input_prep(self, C: Optional[int] = None):
         """The ``InputPrep`` of this configuration (C: the model's input channels)."""
@@ -415,7 +433,8 @@ class GaleConfig:
             trace=self.trace, input_format=self.input_format, b64_ingest=self.b64_ingest,
             **self.input_prep(C).engine_entries(),
             **self.input_resize_plan(H, W).engine_entries(),
-            **(self.input_yuv().engine_entries() if self.input_yuv() else {}))
+            **(self.input_yuv().engine_entries() if self.input_yuv() else {}),
+            **(self.input_unpack().engine_entries() if self.input_unpack() else {}))
 
 
 def _pack_fast() -> bool:

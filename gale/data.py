@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import base64
 import json
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -115,6 +115,51 @@ def synthetic_yuv_planes(n: int, HS: int, WS: int, seed: int = 0):
     return (rng.integers(0, 256, (n, HS, WS), dtype=np.uint8),
             rng.integers(0, 256, (n, HS // 2, WS // 2), dtype=np.uint8),
             rng.integers(0, 256, (n, HS // 2, WS // 2), dtype=np.uint8))
+
+
+def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
+                alpha: Optional[np.ndarray] = None) -> np.ndarray:
+    """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of
+    ``gale.models.preprocess.PixelUnpack.apply``): ``bgr24`` / ``rgba`` / ``bgra`` reorder the
+    bytes, with ``alpha`` [N, HS, WS] (default 255) as the fourth byte; ``gray`` needs
+    R == G == B and keeps one byte."""
+    from gale.models.preprocess import PixelUnpack
+
+    un = PixelUnpack(pixel_format)
+    x = np.asarray(rgb_u8)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3] != 3:
+        raise ValueError("pack_pixels: uint8 [N, HS, WS, 3] images")
+    N, HS, WS, _ = x.shape
+    P = un.bytes_per_pixel
+    if alpha is not None and P != 4:
+        raise ValueError(f"pack_pixels: {pixel_format} has no alpha byte")
+    if P == 1:
+        if not (np.array_equal(x[..., 0], x[..., 1]) and np.array_equal(x[..., 0], x[..., 2])):
+            raise ValueError("pack_pixels: gray needs R == G == B")
+        return np.ascontiguousarray(x[..., 0].reshape(N, -1))
+    out = np.full((N, HS, WS, P), 255, np.uint8)
+    if alpha is not None:
+        a = np.asarray(alpha)
+        if a.dtype != np.uint8 or a.shape != (N, HS, WS):
+            raise ValueError(f"pack_pixels: alpha must be uint8 {(N, HS, WS)}, got {a.shape}")
+        out[..., 3] = a
+    for c, off in enumerate(un.offsets):
+        out[..., off] = x[..., c]
+    return out.reshape(N, -1)
+
+
+def encode_records_packed(rgb_u8: np.ndarray, pixel_format: str, images_per_record: int = 1,
+                          alpha: Optional[np.ndarray] = None) -> List[bytes]:
+    """uint8 RGB images (``pack_pixels``) -> ``{"instances":[{"b64":"..."},...]}`` records of
+    packed pixels (--input-format b64 --input-pixel-format bgr24 | rgba | bgra | gray): each
+    image's HS*WS*P bytes in standard base64, '=' padded."""
+    packed = pack_pixels(rgb_u8, pixel_format, alpha)
+    out = []
+    for i in range(0, packed.shape[0], images_per_record):
+        elems = [b'{"b64":"' + base64.b64encode(im.tobytes()) + b'"}'
+                 for im in packed[i:i + images_per_record]]
+        out.append(b'{"instances":[' + b",".join(elems) + b"]}")
+    return out
 
 
 def encode_batches(records: Sequence[bytes], records_per_batch: int = 64) -> List[bytes]:

@@ -94,7 +94,7 @@ class Engine:
                      "image arena and the table step address model-size images); the batch step "
                      "parses from the resident mirror and resizes", resize.HS, resize.WS,
                      resize.HR, resize.WR, H, W)
-        yuv = cfg.input_pixel_format != "rgb"
+        yuv = cfg.input_pixel_format != "rgb"  # (a YUV or a packed format: the same rule)
         if yuv and ingest and cfg.ingest_parse and not resize.active:  # (one line for the rule)
             log.info("input pixel format %s: the GPU ingest does not decode (its b64 decode and "
                      "image arena hold RGB strings' images): CRC-only; the batch step decodes "

@@ -18,6 +18,9 @@ the model's tensors stay NHWC.
 frames (``--input-pixel-format i420 | nv12``) are converted to 0..255 RGB in integers before the
 fma above.
 
+``PixelUnpack`` (below) is the other thing that may come first: ``b64`` records whose pixels are
+packed as ``bgr24``, ``rgba``, ``bgra`` or ``gray`` are unpacked to interleaved RGB bytes.
+
 ``InputResize`` (below) defines the step that may follow: records that carry images of another
 size are resized (bilinear, or with ``antialias`` the support-scaled triangle filter) and
 centre-cropped to the model's on the preprocessed values.
@@ -446,7 +449,7 @@ class YuvConvert:
     def from_config(cls, cfg) -> Optional["YuvConvert"]:
         """The conversion of a configuration, None for ``rgb``. (GaleConfig.validate refuses the
         combinations that have none.)"""
-        if cfg.input_pixel_format == "rgb":
+        if cfg.input_pixel_format not in PIXEL_FORMATS[1:]:  # (rgb, or a PixelUnpack format)
             return None
         return cls(cfg.input_pixel_format, cfg.input_yuv_matrix or "bt601",
                    cfg.input_yuv_range or "limited")
@@ -505,6 +508,74 @@ class YuvConvert:
         acc = self.accumulators(Y, up(U), up(V))
         assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
         return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
+
+
+# the packed formats: name -> (bytes per pixel, byte offset in a pixel of R, G, B)
+PACKED_FORMATS = {"bgr24": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)),
+                  "gray": (1, (0, 0, 0))}
+
+
+@dataclass(frozen=True)
+class PixelUnpack:
+    """Packed pixels (``--input-pixel-format bgr24 | rgba | bgra | gray``) to interleaved RGB.
+
+    An image of HS x WS pixels (any positive sizes) is ``B = HS*WS*P`` bytes, pixels in
+    ``[HS][WS]`` order, P bytes per pixel::
+
+        bgr24  P = 3   B, G, R       RGB = (byte 2, byte 1, byte 0)
+        rgba   P = 4   R, G, B, A    RGB = (byte 0, byte 1, byte 2)
+        bgra   P = 4   B, G, R, A    RGB = (byte 2, byte 1, byte 0)
+        gray   P = 1   Y             RGB = (byte 0, byte 0, byte 0)
+
+    Alpha is ignored: not composited, not un-premultiplied (PIL's ``convert("RGB")``). The names
+    are ffmpeg's ``pix_fmt``s. ``codec::packed_to_rgb_host`` (csrc/codec/pixfmt.h) and the
+    ``b64_packed_instances`` kernel give the same bytes; the ``InputPrep`` coefficients that
+    follow are indexed by model channel (R, G, B), whatever the order on the wire."""
+
+    format: str = "bgr24"
+
+    def __post_init__(self):
+        if self.format not in PACKED_FORMATS:
+            raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
+                             f"{tuple(PACKED_FORMATS)} for a packed format")
+
+    @classmethod
+    def from_config(cls, cfg) -> Optional["PixelUnpack"]:
+        """The unpack of a configuration, None for ``rgb`` and the YUV formats. (GaleConfig.validate
+        refuses the combinations that have none.)"""
+        if cfg.input_pixel_format not in PACKED_FORMATS:
+            return None
+        return cls(cfg.input_pixel_format)
+
+    @property
+    def bytes_per_pixel(self) -> int:
+        return PACKED_FORMATS[self.format][0]
+
+    @property
+    def offsets(self) -> Tuple[int, int, int]:
+        """Byte offset in a pixel of model channels R, G, B."""
+        return PACKED_FORMATS[self.format][1]
+
+    def frame_bytes(self, HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0:
+            raise ValueError(f"an image needs positive sizes, got {HS},{WS}")
+        return HS * WS * self.bytes_per_pixel
+
+    def engine_entries(self) -> Dict[str, Any]:
+        return dict(pixel_format=self.format)
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``b64_packed_instances`` binding."""
+        return dict(format=self.format)
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] images -> uint8 [..., HS, WS, 3] RGB."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        px = f.reshape(*f.shape[:-1], HS, WS, self.bytes_per_pixel)
+        return np.ascontiguousarray(px[..., list(self.offsets)])
 
 
 def prep_or_none(prep: Optional[InputPrep]) -> Optional[InputPrep]:
