@@ -616,6 +616,23 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_patch_supported", [](py::dict desc, int batch, bool has_res) {
     return gale::conv_patch_supported(desc_from_dict(desc), batch, has_res);
   });
+  // the launch of the MFMA conv kernel for this layer and batch (host only, no HIP call)
+  m.def("conv_mfma_plan", [](py::dict desc, int batch, bool has_res) {
+    const gale::ConvMfmaPlan p = gale::conv_mfma_plan(desc_from_dict(desc), batch, has_res);
+    static const char* const kModes[] = {"fast", "gather", "1x1"};
+    py::dict r;
+    r["ok"] = p.ok;
+    r["mode"] = kModes[p.mode];
+    r["nt"] = p.nt;
+    r["pr"] = p.pr;
+    r["n_blocks"] = p.n_blocks;
+    r["bk"] = p.bk;
+    r["nkc"] = p.nkc;
+    r["m_tiles"] = p.m_tiles;
+    r["grid_m"] = p.grid_m;
+    r["lds_bytes"] = p.lds_bytes;
+    return r;
+  }, py::arg("desc"), py::arg("batch"), py::arg("has_res"));
   m.def("device_pci_bus_id", [](int device) {
     char buf[64] = {0};
     chk(hipDeviceGetPCIBusId(buf, (int)sizeof(buf), device), "hipDeviceGetPCIBusId");

@@ -56,6 +56,30 @@ hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, co
 hipError_t conv2d_f32(const ConvDesc& d, int batch, const void* x, const void* w,
                       const float* bias, const void* res, void* y, hipStream_t stream);
 
+// Everything conv2d() decides for a launch of the MFMA kernel (conv_mfma.hip), i.e. once the
+// fp32 / packed-stem / patch / GEMM branches have passed: the template instantiation (mode, nt,
+// pr) and the grid depend on the batch, not only on the layer. Host only, no HIP call; conv2d()
+// launches from this struct and from nothing else. has_res: the launch reads a residual
+// (d.has_res and a non-null pointer).
+// ok == false (conv2d() returns hipErrorInvalidValue): Cout % 4, Kpad % 32, Npad % (16 nt),
+// out_f32 outside 1x1 mode, a K chunk below 32, or a launch the kernel's 32-bit offsets cannot
+// index: batch*Ho*Wo (rounded up to whole pixel tiles), batch*H*W*Cin or, with a residual,
+// batch*res_H*res_W*res_C at 2^31 or more.
+enum ConvMfmaMode : int { CONV_MFMA_FAST = 0, CONV_MFMA_GATHER = 1, CONV_MFMA_1X1 = 2 };
+struct ConvMfmaPlan {
+  bool ok = false;
+  int mode = CONV_MFMA_FAST;  // ConvMfmaMode
+  int nt = 0;                 // channel tiles (16 channels each) per workgroup n-block
+  int pr = 0;                 // pixel tiles (16 pixels each) per wave: the tile is 64 pr pixels
+  int n_blocks = 0;           // grid.y
+  int bk = 0;                 // K chunk staged in LDS
+  int nkc = 0;                // K chunks; 1 = the weights stay resident and tiles are walked
+  int m_tiles = 0;            // pixel tiles of the launch
+  int grid_m = 0;             // grid.x; < m_tiles: workgroups walk the tiles grid-stride
+  size_t lds_bytes = 0;
+};
+ConvMfmaPlan conv_mfma_plan(const ConvDesc& d, int batch, bool has_res);
+
 // Activation element types of the pooling / head kernels (their `et` argument; 1 was the old
 // fp8 flag, so fp8 callers are unchanged)
 enum ElemType : int { ET_BF16 = 0, ET_FP8 = 1, ET_F32 = 2 };

@@ -26,6 +26,13 @@
 // The epilogue dequantises acc * wscale[c] * in_scale, adds bias and the (dequantised) residual,
 // applies ReLU and requantises with 1/out_scale (saturating at +-448), so fp8 halves every
 // activation byte moved; the network input stays fp32 and is quantised while it is loaded.
+//
+// Launch plan: which instantiation (mode, NT, PR) and which grid a launch gets depends on its
+// batch; conv_mfma_plan() below decides all of it on the host and conv2d() launches from its
+// result alone. The pixel index m and the input / residual element offsets (pbase, roff) are
+// 32-bit ints, so the plan refuses a launch whose batch*Ho*Wo (in whole tiles), batch*H*W*Cin or
+// batch*res_H*res_W*res_C reaches 2^31 (conv2d() returns hipErrorInvalidValue). The offsets are
+// deliberately not widened here: that would put 64-bit address arithmetic into the hot loop.
 #include "common.cuh"
 #include "gale/kernels.h"
 
@@ -35,7 +42,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kLdsBudget = 80 * 1024;  // 2 workgroups per CU by LDS
 
-enum { MODE_FAST = 0, MODE_GATHER = 1, MODE_1X1 = 2 };
+enum { MODE_FAST = CONV_MFMA_FAST, MODE_GATHER = CONV_MFMA_GATHER, MODE_1X1 = CONV_MFMA_1X1 };
 
 struct ConvArgs {
   const void* x;
@@ -406,6 +413,56 @@ int conv_n_tiles(int Cout) {
   return 8;
 }
 
+ConvMfmaPlan conv_mfma_plan(const ConvDesc& d, int batch, bool has_res) {
+  ConvMfmaPlan p;
+  if (batch <= 0) return p;
+  if (d.KH == 1 && d.KW == 1 && d.pad == 0 && d.Cin % 8 == 0) p.mode = CONV_MFMA_1X1;
+  else if (d.Cin % 8 == 0 && ilog2_exact(d.Cin) >= 0) p.mode = CONV_MFMA_FAST;
+  else p.mode = CONV_MFMA_GATHER;
+  if (d.out_f32 && p.mode != CONV_MFMA_1X1) return p;
+  if (d.Cout % 4 != 0 || d.Kpad % 32 != 0) return p;
+
+  // the kernel's pixel index, input offsets and residual offsets are 32-bit
+  const long long lim = 1ll << 31;
+  const long long M = (long long)batch * d.Ho * d.Wo;
+  if (M >= lim || (long long)batch * d.H * d.W * d.Cin >= lim) return p;
+  if (has_res && (long long)batch * d.res_H * d.res_W * d.res_C >= lim) return p;
+
+  p.nt = conv_n_tiles(d.Cout);
+  const int BN = p.nt * 16;
+  if (d.Npad % BN != 0) return p;
+  p.n_blocks = (d.Cout + BN - 1) / BN;
+  // pixel tiles per wave: the largest of {4 (2 for 8 channel tiles), 2, 1} that still gives the
+  // chip >= 4 workgroups per CU; small layers (late stages, small batches) trade B-fragment reuse
+  // for occupancy, which is what bounds them
+  p.pr = (p.nt >= 8) ? 2 : 4;
+  while (p.pr > 1 && (M + 64 * p.pr - 1) / (64 * p.pr) * p.n_blocks < 1024) p.pr >>= 1;
+  const int BM = 4 * p.pr * 16;
+  // (pixels past M in the last tile are indexed too, then masked)
+  if ((M + BM - 1) / BM * BM >= lim) return p;
+  p.m_tiles = (int)((M + BM - 1) / BM);
+
+  // K chunk: whole K if it fits the LDS budget (weight-stationary), else the largest multiple of
+  // 32 that does.
+  const int eb = d.fp8 ? 1 : 2;
+  p.bk = d.Kpad;
+  if ((size_t)BN * (p.bk + 16) * eb > (size_t)kLdsBudget) {
+    p.bk = (kLdsBudget / (BN * eb) - 16) & ~31;
+    if (p.bk < 32) return p;
+  }
+  p.nkc = (d.Kpad + p.bk - 1) / p.bk;
+  p.lds_bytes = (size_t)BN * (p.bk + 16) * eb;
+
+  p.grid_m = p.m_tiles;
+  if (p.nkc == 1) {
+    // weight-stationary: enough workgroups to fill 256 CUs x 8, each walks several tiles
+    const int cap = 2048 / p.n_blocks > 0 ? 2048 / p.n_blocks : 1;
+    p.grid_m = p.m_tiles < cap ? p.m_tiles : cap;
+  }
+  p.ok = true;
+  return p;
+}
+
 hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, const float* bias,
                   const float* wscale, const void* res, void* y, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
@@ -424,6 +481,8 @@ hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, co
     return conv2d_gemm(d, batch, x, w, bias, d.has_res ? res : nullptr, y, stream);
   if (f8 && (wscale == nullptr || !(d.in_scale > 0.f) || !(d.out_scale > 0.f)))
     return hipErrorInvalidValue;
+  const ConvMfmaPlan p = conv_mfma_plan(d, batch, d.has_res && res != nullptr);
+  if (!p.ok) return hipErrorInvalidValue;
   ConvArgs a;
   a.x = x;
   a.w = w;
@@ -442,51 +501,15 @@ hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, co
   a.in_qinv = f8 ? 1.f / d.in_scale : 1.f;
   a.out_qinv = f8 ? 1.f / d.out_scale : 1.f;
   a.res_scale = f8 ? d.res_scale : 1.f;
-
-  int mode;
   const int cs = ilog2_exact(d.Cin);
-  if (d.KH == 1 && d.KW == 1 && d.pad == 0 && d.Cin % 8 == 0) mode = MODE_1X1;
-  else if (d.Cin % 8 == 0 && cs >= 0) mode = MODE_FAST;
-  else mode = MODE_GATHER;
   a.cin_shift = cs < 0 ? 0 : cs;
-  if (d.out_f32 && mode != MODE_1X1) return hipErrorInvalidValue;
-  if (d.Cout % 4 != 0 || d.Kpad % 32 != 0) return hipErrorInvalidValue;
+  a.BK = p.bk;
+  a.nkc = p.nkc;
+  a.m_tiles = p.m_tiles;
 
-  const int nt = conv_n_tiles(d.Cout);
-  const int BN = nt * 16;
-  if (d.Npad % BN != 0) return hipErrorInvalidValue;
-  const int n_blocks = (d.Cout + BN - 1) / BN;
-  // pixel tiles per wave: the largest of {4 (2 for 8 channel tiles), 2, 1} that still gives the
-  // chip >= 4 workgroups per CU; small layers (late stages, small batches) trade B-fragment reuse
-  // for occupancy, which is what bounds them
-  const int pr_max = (nt >= 8) ? 2 : 4;
-  int PR = pr_max;
-  while (PR > 1 && (long long)((a.M + 64 * PR - 1) / (64 * PR)) * n_blocks < 1024) PR >>= 1;
-  const int BM = 4 * PR * 16;
-
-  // K chunk: whole K if it fits the LDS budget (weight-stationary), else the largest multiple of
-  // 32 that does.
-  const int eb = f8 ? 1 : 2;
-  int bk = d.Kpad;
-  if ((size_t)BN * (bk + 16) * eb > (size_t)kLdsBudget) {
-    bk = (kLdsBudget / (BN * eb) - 16) & ~31;
-    if (bk < 32) return hipErrorInvalidValue;
-  }
-  a.BK = bk;
-  a.nkc = (d.Kpad + bk - 1) / bk;
-  a.m_tiles = (a.M + BM - 1) / BM;
-  const size_t lds = (size_t)BN * (bk + 16) * eb;
-
-  int grid_m = a.m_tiles;
-  if (a.nkc == 1) {
-    // weight-stationary: enough workgroups to fill 256 CUs x 8, each walks several tiles
-    const int cap = 2048 / n_blocks > 0 ? 2048 / n_blocks : 1;
-    grid_m = a.m_tiles < cap ? a.m_tiles : cap;
-  }
-
-  const ConvKernelFn fn = f8 ? pick_kernel<true>(mode, d.in_f32, d.out_f32, nt, PR)
-                             : pick_kernel<false>(mode, d.in_f32, d.out_f32, nt, PR);
-  hipLaunchKernelGGL(fn, dim3(grid_m, n_blocks), dim3(kThreads), lds, stream, a);
+  const ConvKernelFn fn = f8 ? pick_kernel<true>(p.mode, d.in_f32, d.out_f32, p.nt, p.pr)
+                             : pick_kernel<false>(p.mode, d.in_f32, d.out_f32, p.nt, p.pr);
+  hipLaunchKernelGGL(fn, dim3(p.grid_m, p.n_blocks), dim3(kThreads), p.lds_bytes, stream, a);
   return hipGetLastError();
 }
 
