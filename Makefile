@@ -95,6 +95,16 @@ build/asan/pixfmt_check: csrc/tests/pixfmt_check.cpp csrc/codec/json_codec.cpp \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/pixfmt_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
+# PixelSource (csrc/tests/pixel_source_check.cpp): the names, the bytes of a string, the refusals,
+# the ingest's dimensions and the host dispatch against the three decoders on mutated and
+# truncated records, for all seven pixel formats; codec only, no engine, no HIP call
+build/asan/pixel_source_check: csrc/tests/pixel_source_check.cpp csrc/codec/json_codec.cpp \
+                               csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/pixel_source_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
 # the b64 ingest's host plan behind the scanner, on mutated records and mutated scan results
 # (csrc/tests/b64_plan_check.cpp): codec + plan, no engine, no HIP call
 build/asan/b64_plan_check: csrc/tests/b64_plan_check.cpp csrc/runtime/ingest_plan.cpp \

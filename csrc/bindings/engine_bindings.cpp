@@ -108,24 +108,15 @@ EngineConfig config_from_dict(const py::dict& d) {
   opt(d, "b64_ingest", c.b64_ingest);
   if (c.b64_ingest && !c.input_b64)
     throw std::invalid_argument("b64_ingest needs input_format b64");
-  // YUV 4:2:0 frames in the b64 strings (gale/models/preprocess.py YuvConvert.engine_entries;
-  // absent = RGB bytes)
+  // what the b64 strings carry (gale/models/preprocess.py YuvConvert / PixelUnpack
+  // .engine_entries; absent = RGB bytes)
   {
     std::string pf = "rgb", ym = "bt601", yr = "limited";
     opt(d, "pixel_format", pf);
     opt(d, "yuv_matrix", ym);
     opt(d, "yuv_range", yr);
-    // (the packed formats of csrc/codec/pixfmt.h: bgr24, rgba, bgra, gray)
-    c.packed_format = packed_format_of(pf.c_str());
-    if (pf == "i420" || pf == "nv12")
-      c.yuv_format = pf == "i420" ? (int)YUV_I420 : (int)YUV_NV12;
-    else if (pf != "rgb" && !c.packed_format)
-      throw std::invalid_argument("pixel_format: rgb, i420, nv12, bgr24, rgba, bgra or gray");
-    if (c.packed_format && (d.contains("yuv_matrix") || d.contains("yuv_range")))
-      throw std::invalid_argument("yuv_matrix / yuv_range need pixel_format i420 or nv12");
-    if (!yuv_coeffs(ym == "bt601" ? 0 : ym == "bt709" ? 1 : -1,
-                    yr == "limited" ? 0 : yr == "full" ? 1 : -1, &c.yuv))
-      throw std::invalid_argument("yuv_matrix: bt601 or bt709; yuv_range: limited or full");
+    c.pixels = PixelSource::from_names(pf, d.contains("yuv_matrix") ? &ym : nullptr,
+                                       d.contains("yuv_range") ? &yr : nullptr);
   }
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
@@ -147,22 +138,8 @@ EngineConfig config_from_dict(const py::dict& d) {
   } else if (c.resize_antialias) {
     throw std::invalid_argument("resize_antialias: no input resize is active");
   }
-  if (c.yuv_format) {
-    if (!c.input_b64) throw std::invalid_argument("pixel_format i420 / nv12 needs input_format b64");
-    if (c.prep.nchw) throw std::invalid_argument("pixel_format i420 / nv12: no nchw layout");
-    if (c.C != 3) throw std::invalid_argument("pixel_format i420 / nv12 needs a 3-channel model");
-    if ((c.rec_h() | c.rec_w()) & 1)
-      throw std::invalid_argument("pixel_format i420 / nv12 needs even record-side H, W");
-    // the ingest's b64 decode and its arena hold RGB strings' images: CRC-only
-    c.ingest_parse = false;
-  }
-  if (c.packed_format) {
-    const std::string what = "pixel_format bgr24 / rgba / bgra / gray";
-    if (!c.input_b64) throw std::invalid_argument(what + " needs input_format b64");
-    if (c.prep.nchw) throw std::invalid_argument(what + ": no nchw layout");
-    if (c.C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
-    c.ingest_parse = false;  // (as for YUV)
-  }
+  c.pixels.check(c.C, c.prep.nchw != 0, c.rec_h(), c.rec_w(), c.input_b64);
+  if (!c.pixels.wants_ingest_decode()) c.ingest_parse = false;
   return c;
 }
 
@@ -183,9 +160,7 @@ void bind_engine(py::module_& m) {
              auto rep = std::make_shared<StubReplica>(c.H, c.W, c.C, c.classes, max_images,
                                                       delay_us, compute, locality);
              rep->set_input_prep(c.prep);
-             rep->set_input_b64(c.input_b64);
-             rep->set_input_yuv(c.yuv_format, c.yuv);
-             rep->set_input_packed(c.packed_format);
+             rep->set_input_b64(c.input_b64, c.pixels);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },
@@ -201,9 +176,7 @@ void bind_engine(py::module_& m) {
                                                      locality, step_graph, high_priority,
                                                      step_direct, c.top_k);
              rep->set_input_prep(c.prep);
-             rep->set_input_b64(c.input_b64);
-             rep->set_input_yuv(c.yuv_format, c.yuv);
-             rep->set_input_packed(c.packed_format);
+             rep->set_input_b64(c.input_b64, c.pixels);
              set_resize(*rep, c);
              e.add_replica(std::move(rep));
            },

@@ -67,6 +67,23 @@ inline void* P(uintptr_t p) { return reinterpret_cast<void*>(p); }
 
 void chk(hipError_t e, const char* what) { gale::check_hip(e, what); }
 
+// The InputPrep of a parse / decode binding `name`: a / b (four coefficients each) or nchw given
+// means one is passed (identity ones too); none of them, no prep (nullopt).
+std::optional<gale::InputPrep> prep_from(const char* name,
+                                         const std::optional<std::vector<float>>& a,
+                                         const std::optional<std::vector<float>>& b, bool nchw) {
+  if ((a && a->size() != 4) || (b && b->size() != 4))
+    throw std::invalid_argument(std::string(name) + ": a / b take four coefficients");
+  if (!a && !b && !nchw) return std::nullopt;
+  gale::InputPrep prep;
+  for (int i = 0; i < 4; ++i) {
+    if (a) prep.a[i] = (*a)[i];
+    if (b) prep.b[i] = (*b)[i];
+  }
+  prep.nchw = nchw ? 1 : 0;
+  return prep;
+}
+
 gale::PlanOp op_from_dict(const py::dict& d) {
   gale::PlanOp op;
   op.kind = d["kind"].cast<int>();
@@ -237,15 +254,7 @@ PYBIND11_MODULE(_C, m) {
            std::optional<std::vector<float>> b, bool nchw, uintptr_t d_ntiles, uintptr_t status,
            uintptr_t tile_bad) {
           // a / b (four coefficients each) or nchw: an InputPrep is passed (identity ones too)
-          gale::InputPrep prep;
-          const bool with_prep = a || b || nchw;
-          if ((a && a->size() != 4) || (b && b->size() != 4))
-            throw std::invalid_argument("json_parse_instances: a / b take four coefficients");
-          for (int i = 0; i < 4; ++i) {
-            if (a) prep.a[i] = (*a)[i];
-            if (b) prep.b[i] = (*b)[i];
-          }
-          prep.nchw = nchw ? 1 : 0;
+          const auto prep = prep_from("json_parse_instances", a, b, nchw);
           chk(gale::json_parse_instances(nrec, ntiles, static_cast<gale::JsonRecord*>(P(recs)),
                                          static_cast<const int*>(P(tile_rec)),
                                          static_cast<const uint8_t*>(P(bytes)), H, W, C,
@@ -254,7 +263,7 @@ PYBIND11_MODULE(_C, m) {
                                          static_cast<const int*>(P(d_ntiles)),
                                          static_cast<int*>(P(status)),
                                          static_cast<int*>(P(tile_bad)),
-                                         with_prep ? &prep : nullptr),
+                                         prep ? &*prep : nullptr),
               "json_parse_instances");
         },
         py::arg("nrec"), py::arg("ntiles"), py::arg("recs"), py::arg("tile_rec"),
@@ -270,21 +279,13 @@ PYBIND11_MODULE(_C, m) {
           // imgs: B64_IMAGE_BYTES-byte descriptors (int64 off, int32 slot, int32 rec); d_images
           // non-zero: the image count is read there on the device (images = the launch size).
           // a / b (four coefficients each) or nchw: an InputPrep is passed (identity ones too)
-          gale::InputPrep prep;
-          const bool with_prep = a || b || nchw;
-          if ((a && a->size() != 4) || (b && b->size() != 4))
-            throw std::invalid_argument("b64_decode_instances: a / b take four coefficients");
-          for (int i = 0; i < 4; ++i) {
-            if (a) prep.a[i] = (*a)[i];
-            if (b) prep.b[i] = (*b)[i];
-          }
-          prep.nchw = nchw ? 1 : 0;
+          const auto prep = prep_from("b64_decode_instances", a, b, nchw);
           chk(gale::b64_decode_instances(images, static_cast<const gale::B64Image*>(P(imgs)),
                                          static_cast<const uint8_t*>(P(bytes)), H, W, C,
                                          static_cast<float*>(P(out)),
                                          static_cast<int*>(P(status)), S(stream),
                                          static_cast<const int*>(P(d_images)),
-                                         with_prep ? &prep : nullptr),
+                                         prep ? &*prep : nullptr),
               "b64_decode_instances");
         },
         py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("H"), py::arg("W"),
@@ -300,18 +301,10 @@ PYBIND11_MODULE(_C, m) {
           // (anything else reaches the launcher as an unknown format); coeffs: (cy, crv, cgu,
           // cgv, cbu, yo). Returns the launcher's hipError_t as an int (0 = launched): its
           // refusals are part of the contract, so they do not throw
-          gale::InputPrep prep;
-          const bool with_prep = a || b || nchw;
-          if ((a && a->size() != 4) || (b && b->size() != 4))
-            throw std::invalid_argument("b64_yuv_instances: a / b take four coefficients");
+          const auto prep = prep_from("b64_yuv_instances", a, b, nchw);
           if (coeffs.size() != 6)
             throw std::invalid_argument("b64_yuv_instances: coeffs takes (cy, crv, cgu, cgv, "
                                         "cbu, yo)");
-          for (int i = 0; i < 4; ++i) {
-            if (a) prep.a[i] = (*a)[i];
-            if (b) prep.b[i] = (*b)[i];
-          }
-          prep.nchw = nchw ? 1 : 0;
           gale::YuvCoeffs k;
           k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
           k.cbu = coeffs[4], k.yo = coeffs[5];
@@ -322,7 +315,7 @@ PYBIND11_MODULE(_C, m) {
               images, static_cast<const gale::B64Image*>(P(imgs)),
               static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
               static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
-              with_prep ? &prep : nullptr, fmt, k, pairs);
+              prep ? &*prep : nullptr, fmt, k, pairs);
         },
         py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
         py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
@@ -338,20 +331,12 @@ PYBIND11_MODULE(_C, m) {
           // "bgra" | "gray" (anything else reaches the launcher as an unknown format). Returns
           // the launcher's hipError_t as an int (0 = launched): its refusals are part of the
           // contract, so they do not throw
-          gale::InputPrep prep;
-          const bool with_prep = a || b || nchw;
-          if ((a && a->size() != 4) || (b && b->size() != 4))
-            throw std::invalid_argument("b64_packed_instances: a / b take four coefficients");
-          for (int i = 0; i < 4; ++i) {
-            if (a) prep.a[i] = (*a)[i];
-            if (b) prep.b[i] = (*b)[i];
-          }
-          prep.nchw = nchw ? 1 : 0;
+          const auto prep = prep_from("b64_packed_instances", a, b, nchw);
           return (int)gale::b64_packed_instances(
               images, static_cast<const gale::B64Image*>(P(imgs)),
               static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
               static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
-              with_prep ? &prep : nullptr, gale::packed_format_of(format.c_str()));
+              prep ? &*prep : nullptr, gale::packed_format_of(format.c_str()));
         },
         py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
         py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
@@ -433,22 +418,14 @@ PYBIND11_MODULE(_C, m) {
            std::optional<std::vector<float>> b, bool nchw) {
           // imgs: B64_IMAGE_BYTES-byte descriptors; wg_bad: one int per decode workgroup
           // (images * ceil(L / B64_CHUNK_CHARS)). a / b / nchw: as b64_decode_instances
-          gale::InputPrep prep;
-          const bool with_prep = a || b || nchw;
-          if ((a && a->size() != 4) || (b && b->size() != 4))
-            throw std::invalid_argument("ingest_crc_b64: a / b take four coefficients");
-          for (int i = 0; i < 4; ++i) {
-            if (a) prep.a[i] = (*a)[i];
-            if (b) prep.b[i] = (*b)[i];
-          }
-          prep.nchw = nchw ? 1 : 0;
+          const auto prep = prep_from("ingest_crc_b64", a, b, nchw);
           chk(gale::ingest_crc_b64(static_cast<const uint8_t*>(P(bytes)),
                                    static_cast<const gale::CrcChunk*>(P(chunks)), nchunks,
                                    static_cast<const uint32_t*>(P(tables)),
                                    static_cast<uint32_t*>(P(crc_out)), images,
                                    static_cast<const gale::B64Image*>(P(imgs)), H, W, C,
                                    static_cast<float*>(P(arena)), static_cast<int*>(P(wg_bad)),
-                                   S(stream), with_prep ? &prep : nullptr),
+                                   S(stream), prep ? &*prep : nullptr),
               "ingest_crc_b64");
         },
         py::arg("bytes"), py::arg("chunks"), py::arg("nchunks"), py::arg("tables"),

@@ -489,118 +489,90 @@ bool split_instances_b64_bytes(const uint8_t* arr, size_t len, int64_t nbytes,
   return true;
 }
 
-int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
-                             int max_images, int* images) {
+// One string of nbytes bytes at q (L = b64_chars_bytes(nbytes) characters) into dst[L / 4 * 3]
+// (null: judged only, every character all the same). BAD_NUMBER for a character outside the
+// alphabet in the data part or a non-'=' among the last (3 - nbytes % 3) % 3 characters.
+static int decode_b64_string(const uint8_t* q, size_t nbytes, uint8_t* dst) {
   static const B64Table table;
-  *images = 0;
-  const Scan s = scan_instances_b64(p, n, H, W, C);
+  const size_t L = (size_t)b64_chars_bytes((int64_t)nbytes), pad = (3 - nbytes % 3) % 3;
+  for (size_t g = 0; g < L; g += 4) {
+    uint32_t v = 0;
+    for (size_t j = 0; j < 4; ++j) {
+      uint8_t x = table.v[q[g + j]];
+      if (g + j >= L - pad) {
+        if (q[g + j] != '=') return BAD_NUMBER;
+        x = 0;
+      } else if (x == 0xFF) {
+        return BAD_NUMBER;
+      }
+      v = (v << 6) | x;
+    }
+    if (!dst) continue;
+    const size_t o = g / 4 * 3;
+    dst[o] = (uint8_t)(v >> 16);
+    dst[o + 1] = (uint8_t)(v >> 8);
+    dst[o + 2] = (uint8_t)v;
+  }
+  return OK;
+}
+
+// The host decoders' common procedure for records whose strings carry B bytes: scan, TOO_LARGE,
+// walk, then per element the string's bytes and convert(bytes, image index) - called only when
+// the caller wants the floats (out non-null); the characters are judged either way.
+template <typename Convert>
+static int parse_b64_records(const uint8_t* p, size_t n, int64_t B, bool out, int max_images,
+                             int* images, Convert convert) {
+  const Scan s = scan_instances_b64_bytes(p, n, B);
   if (s.status != OK) return s.status;
   if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
   std::vector<B64Elem> elems;
-  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, image_bytes(H, W, C), elems);
+  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, B, elems);
   if (st != OK) return st;
-  const size_t per = (size_t)H * W * C, L = (size_t)b64_chars(H, W, C);
-  const size_t pad = (3 - per % 3) % 3;
+  std::vector<uint8_t> image(out ? (size_t)b64_chars_bytes(B) / 4 * 3 : 0);
   for (size_t e = 0; e < elems.size(); ++e) {
-    const uint8_t* q = p + s.arr_off + elems[e].str;
-    float* dst = out ? out + e * per : nullptr;
-    for (size_t g = 0; g < L; g += 4) {
-      uint32_t v = 0;
-      for (size_t j = 0; j < 4; ++j) {
-        uint8_t x = table.v[q[g + j]];
-        if (g + j >= L - pad) {
-          if (q[g + j] != '=') return BAD_NUMBER;
-          x = 0;
-        } else if (x == 0xFF) {
-          return BAD_NUMBER;
-        }
-        v = (v << 6) | x;
-      }
-      if (!dst) continue;
-      const size_t o = g / 4 * 3;
-      for (size_t j = 0; j < 3 && o + j < per; ++j)
-        dst[o + j] = (float)((v >> (16 - 8 * j)) & 0xFF);
-    }
+    const int d = decode_b64_string(p + s.arr_off + elems[e].str, (size_t)B,
+                                    out ? image.data() : nullptr);
+    if (d != OK) return d;
+    if (out) convert(image.data(), e);
   }
   *images = s.images;
   return OK;
+}
+
+int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, float* out,
+                             int max_images, int* images) {
+  *images = 0;
+  const size_t per = (size_t)image_bytes(H, W, C);
+  return parse_b64_records(p, n, (int64_t)per, out != nullptr, max_images, images,
+                           [&](const uint8_t* img, size_t e) {
+                             for (size_t i = 0; i < per; ++i) out[e * per + i] = (float)img[i];
+                           });
 }
 
 int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                              const YuvCoeffs& k, float* out, int max_images, int* images) {
-  static const B64Table table;
   *images = 0;
   if (HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1) ||
       (format != YUV_I420 && format != YUV_NV12))
     return BAD_SHAPE;
-  const int64_t B = yuv420_bytes(HS, WS);
-  const Scan s = scan_instances_b64_bytes(p, n, B);
-  if (s.status != OK) return s.status;
-  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
-  std::vector<B64Elem> elems;
-  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, B, elems);
-  if (st != OK) return st;
   // (B is a multiple of 3: every character of the L = 4 B / 3 is a data character)
-  std::vector<uint8_t> frame((size_t)B);
   const size_t per = (size_t)HS * WS * 3;
-  for (size_t e = 0; e < elems.size(); ++e) {
-    const uint8_t* q = p + s.arr_off + elems[e].str;
-    for (size_t g = 0; g < (size_t)B / 3; ++g) {
-      uint32_t v = 0;
-      for (size_t j = 0; j < 4; ++j) {
-        const uint8_t x = table.v[q[4 * g + j]];
-        if (x == 0xFF) return BAD_NUMBER;
-        v = (v << 6) | x;
-      }
-      frame[3 * g] = (uint8_t)(v >> 16);
-      frame[3 * g + 1] = (uint8_t)(v >> 8);
-      frame[3 * g + 2] = (uint8_t)v;
-    }
-    if (out) yuv420_to_rgb_host(frame.data(), HS, WS, format, k, nullptr, out + e * per);
-  }
-  *images = s.images;
-  return OK;
+  return parse_b64_records(p, n, yuv420_bytes(HS, WS), out != nullptr, max_images, images,
+                           [&](const uint8_t* frame, size_t e) {
+                             yuv420_to_rgb_host(frame, HS, WS, format, k, nullptr, out + e * per);
+                           });
 }
 
 int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                 float* out, int max_images, int* images) {
-  static const B64Table table;
   *images = 0;
   const int64_t B = packed_bytes(HS, WS, format);
   if (B <= 0) return BAD_SHAPE;
-  const Scan s = scan_instances_b64_bytes(p, n, B);
-  if (s.status != OK) return s.status;
-  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
-  std::vector<B64Elem> elems;
-  const int st = walk_b64_array(p + s.arr_off, (size_t)s.arr_len, B, elems);
-  if (st != OK) return st;
-  // (padding judged as parse_instances_b64_host judges it)
-  const size_t L = (size_t)b64_chars_bytes(B), pad = (3 - (size_t)B % 3) % 3;
-  std::vector<uint8_t> image(L / 4 * 3);
   const size_t per = (size_t)HS * WS * 3;
-  for (size_t e = 0; e < elems.size(); ++e) {
-    const uint8_t* q = p + s.arr_off + elems[e].str;
-    for (size_t g = 0; g < L; g += 4) {
-      uint32_t v = 0;
-      for (size_t j = 0; j < 4; ++j) {
-        uint8_t x = table.v[q[g + j]];
-        if (g + j >= L - pad) {
-          if (q[g + j] != '=') return BAD_NUMBER;
-          x = 0;
-        } else if (x == 0xFF) {
-          return BAD_NUMBER;
-        }
-        v = (v << 6) | x;
-      }
-      const size_t o = g / 4 * 3;
-      image[o] = (uint8_t)(v >> 16);
-      image[o + 1] = (uint8_t)(v >> 8);
-      image[o + 2] = (uint8_t)v;
-    }
-    if (out) packed_to_rgb_host(image.data(), HS, WS, format, nullptr, out + e * per);
-  }
-  *images = s.images;
-  return OK;
+  return parse_b64_records(p, n, B, out != nullptr, max_images, images,
+                           [&](const uint8_t* img, size_t e) {
+                             packed_to_rgb_host(img, HS, WS, format, nullptr, out + e * per);
+                           });
 }
 
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,

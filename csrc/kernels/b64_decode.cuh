@@ -2,6 +2,11 @@
 // the fetch ingest (b64_ingest.hip). See b64_decode.hip for the work split, the alignment scheme
 // and the verdict rules; the callers differ only in how a workgroup finds its (image, chunk) and
 // in where the verdict goes.
+//
+// It stands on the lane's window (load_window, window_bad): the one place that reads a string's
+// characters, aligns them, turns them into 24-bit groups and judges them for b64_decode_body and
+// the YUV decoder (b64_yuv.hip); each keeps only how a lane finds its window and what it does
+// with the 12 bytes. (The packed-pixel decoder, b64_packed.hip, has a copy: see its header.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,12 +58,81 @@ __device__ __forceinline__ uint32_t first_bytes(int n) {
   return n <= 0 ? 0u : n >= 4 ? 0xFFFFFFFFu : (1u << (8 * n)) - 1u;
 }
 
+// ---- a lane's window ----------------------------------------------------------------------------
+// The 16 characters at bytes + off + c (off: the string's first character, c: the window's first
+// character in the string, a multiple of 4), of which the first nch (4, 8, 12 or 16) lie in the string:
+// x[t] the characters of quad t (first in byte 0), v[t] its 24-bit group (byte 0 of the group in
+// bits 16 .. 23; garbage where a character is outside the alphabet), inv[t] a non-zero byte for
+// each character outside the alphabet.
+struct Window {
+  uint32_t x[4], v[4], inv[4];
+};
+
+// Read bound: the aligned 16-byte word under the window's first character and, only when the
+// nch characters reach into it, the next one - at most 15 bytes before a string and fewer than 16
+// past it are read, whatever the string's start phase.
+// off and c come apart so that the phase of a window at c = 16 k is visibly the string's
+// (off & 15, the same for every lane of an image): the alignment switch below is then a scalar
+// branch. Taken from the sum off + c, the phase is a per-lane value to the compiler and the
+// switch an exec-masked one (measured: 1-2 % on the packed decoders). Where a wave's lanes do
+// differ in phase - b64_yuv_kernel, whose waves can span two byte ranges - it diverges, rightly.
+__device__ __forceinline__ Window load_window(const uint8_t* bytes, int64_t off, int c, int nch) {
+  const int ph = (int)((off + (c & 15)) & 15);
+  const uint8_t* base = bytes + (off + c - ph);
+  const uint4 lo = *reinterpret_cast<const uint4*>(base);
+  const uint4 hi = ph + nch > 16 ? *reinterpret_cast<const uint4*>(base + 16)
+                                 : make_uint4(0, 0, 0, 0);
+  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  const uint32_t sh = (uint32_t)(ph & 3);
+  Window win;
+  switch (ph >> 2) {  // (wave-uniform where the lanes of a wave share the phase: see above)
+#define GALE_ALIGN_WORDS(D)                                    \
+  _Pragma("unroll") for (int t = 0; t < 4; ++t) win.x[t] =     \
+      __builtin_amdgcn_alignbyte(w[t + (D) + 1], w[t + (D)], sh);
+    case 0: GALE_ALIGN_WORDS(0) break;
+    case 1: GALE_ALIGN_WORDS(1) break;
+    case 2: GALE_ALIGN_WORDS(2) break;
+    default: GALE_ALIGN_WORDS(3) break;
+#undef GALE_ALIGN_WORDS
+  }
+  // 4 characters -> 4 sextets -> 24 bits
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t sx = b64_sextets4(win.x[t], &win.inv[t]) & 0x3F3F3F3Fu;
+    // halves: (s0 << 6 | s1), (s2 << 6 | s3); then s0 << 18 | s1 << 12 | s2 << 6 | s3
+    const uint32_t h = ((sx & 0x003F003Fu) << 6) | ((sx >> 8) & 0x003F003Fu);
+    win.v[t] = ((h & 0xFFFu) << 12) | (h >> 16);
+  }
+  return win;
+}
+
+// Whether the window holds a character outside the alphabet among its data characters or a
+// non-'=' in the padding. nd: data characters of the string from the window's start on.
+__device__ __forceinline__ bool window_bad(const Window& win, int nd, int nch) {
+  if (nd >= 16)  // every character of the window is a data character
+    return (win.inv[0] | win.inv[1] | win.inv[2] | win.inv[3]) != 0;
+  // the string's last lane: data characters, then '=', then not judged
+  uint32_t j = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const uint32_t dm = first_bytes(nd - 4 * t);
+    j |= (win.inv[t] & dm) | ((win.x[t] ^ 0x3D3D3D3Du) & first_bytes(nch - 4 * t) & ~dm);
+  }
+  return j != 0;
+}
+
 // (selects on the by-value coefficients: a dynamic index would spill them to scratch)
 __device__ __forceinline__ float prep_a(const InputPrep& p, int ch) {
   return ch == 0 ? p.a[0] : ch == 1 ? p.a[1] : ch == 2 ? p.a[2] : p.a[3];
 }
 __device__ __forceinline__ float prep_b(const InputPrep& p, int ch) {
   return ch == 0 ? p.b[0] : ch == 1 ? p.b[1] : ch == 2 ? p.b[2] : p.b[3];
+}
+// (float)v of channel ch, through fmaf(v, a[ch], b[ch]) with PREP
+template <bool PREP, typename T>
+__device__ __forceinline__ float prepped(T v, int ch, const InputPrep& prep) {
+  const float f = (float)v;
+  return PREP ? __builtin_fmaf(f, prep_a(prep, ch), prep_b(prep, ch)) : f;
 }
 
 // Chunk `chunk` (kB64ChunkChars characters) of the string at bytes + d.off, by the 256 threads of
@@ -91,49 +165,15 @@ __device__ __forceinline__ bool b64_decode_body(const B64Image& d, int chunk, in
   if (c0 < L) {
     const int nch = min(16, L - c0);     // characters of the string in the window (4, 8, 12, 16)
     const int nd = L - pad - c0;         // data characters from the window's start on
-    const int64_t addr = d.off + c0;
-    const int ph = (int)(addr & 15);
-    const uint8_t* base = bytes + (addr - ph);
-    const uint4 lo = *reinterpret_cast<const uint4*>(base);
-    // the second word only when the string reaches into it: it ends < 16 bytes past the string
-    const uint4 hi = ph + nch > 16 ? *reinterpret_cast<const uint4*>(base + 16)
-                                   : make_uint4(0, 0, 0, 0);
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t sh = (uint32_t)(ph & 3);
-    uint32_t x[4];
-    switch (ph >> 2) {  // (wave-uniform: every lane of an image has the string's phase)
-#define GALE_ALIGN_WORDS(D)                                \
-  _Pragma("unroll") for (int t = 0; t < 4; ++t) x[t] =     \
-      __builtin_amdgcn_alignbyte(w[t + (D) + 1], w[t + (D)], sh);
-      case 0: GALE_ALIGN_WORDS(0) break;
-      case 1: GALE_ALIGN_WORDS(1) break;
-      case 2: GALE_ALIGN_WORDS(2) break;
-      default: GALE_ALIGN_WORDS(3) break;
-#undef GALE_ALIGN_WORDS
-    }
-    // 4 characters -> 4 sextets -> 24 bits -> 3 values
-    uint32_t inv[4];
-    float f[12];
+    // (every lane of an image has the string's phase)
+    const Window win = load_window(bytes, d.off, c0, nch);
+    bad = window_bad(win, nd, nch);
+    float f[12];  // 24 bits -> 3 values
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const uint32_t sx = b64_sextets4(x[t], &inv[t]) & 0x3F3F3F3Fu;
-      // halves: (s0 << 6 | s1), (s2 << 6 | s3); then s0 << 18 | s1 << 12 | s2 << 6 | s3
-      const uint32_t h = ((sx & 0x003F003Fu) << 6) | ((sx >> 8) & 0x003F003Fu);
-      const uint32_t v = ((h & 0xFFFu) << 12) | (h >> 16);
-      f[3 * t] = (float)((v >> 16) & 0xFFu);
-      f[3 * t + 1] = (float)((v >> 8) & 0xFFu);
-      f[3 * t + 2] = (float)(v & 0xFFu);
-    }
-    if (nd >= 16) {  // every character of the window is a data character
-      bad = (inv[0] | inv[1] | inv[2] | inv[3]) != 0;
-    } else {         // the string's last lane: data characters, then '=', then not judged
-      uint32_t w = 0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const uint32_t dm = first_bytes(nd - 4 * t);
-        w |= (inv[t] & dm) | ((x[t] ^ 0x3D3D3D3Du) & first_bytes(nch - 4 * t) & ~dm);
-      }
-      bad = w != 0;
+      f[3 * t] = (float)((win.v[t] >> 16) & 0xFFu);
+      f[3 * t + 1] = (float)((win.v[t] >> 8) & 0xFFu);
+      f[3 * t + 2] = (float)(win.v[t] & 0xFFu);
     }
     const int v0 = 12 * k;               // first value of this lane (< per, see the launchers)
     const int nv = min(12, per - v0);    // values of the image in this lane

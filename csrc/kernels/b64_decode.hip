@@ -14,18 +14,19 @@
 // NCHW-ordered strings transpose at the store, straight to global memory.
 //
 // Alignment: a string starts at an arbitrary phase modulo 16 of the staged buffer (the replica's
-// span copy preserves the phase the record had in the fetch buffer). A lane loads the aligned
-// 16-byte word holding its window's first character and, only when the window crosses into it,
-// the next one, then byte-aligns them in registers (v_alignbyte_b32 behind a wave-uniform switch
-// on the dword phase, as the JSON parser aligns its windows). No unaligned 16-byte load is
-// issued, and nothing is read from 16 bytes past a string's end on.
+// span copy preserves the phase the record had in the fetch buffer). A lane reads its 16
+// characters through b64::load_window (b64_decode.cuh, which states the read bound): aligned
+// 16-byte words, byte-aligned in registers (v_alignbyte_b32 behind a wave-uniform switch on the
+// dword phase, as the JSON parser aligns its windows). No unaligned 16-byte load is issued.
 //
-// Verdict: validity accumulates per lane, branch-free; a wave with a bad lane stores the
-// constant 2 into its record's status once (every wave of a bad record stores the same value,
-// so a plain store is enough). Images of a bad record are still written, inside their own slot.
+// Verdict: b64::window_bad per lane, branch-free but for the string's last lane; a wave with a
+// bad lane stores the constant 2 into its record's status once (every wave of a bad record
+// stores the same value, so a plain store is enough). Images of a bad record are still written,
+// inside their own slot.
 //
 // The decode of one chunk is b64::b64_decode_body (b64_decode.cuh), shared with the fetch ingest
-// (b64_ingest.hip); the kernels here map the 2-D grid onto it and raise the record status.
+// (b64_ingest.hip); the window under it is shared with the YUV decoder as well. The kernels
+// here map the 2-D grid onto the body and raise the record status.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

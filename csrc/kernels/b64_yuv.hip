@@ -10,10 +10,10 @@
 // Work split: a workgroup owns `pairs` whole row pairs of one frame: 2 * pairs luma rows and
 // pairs chroma rows. Those are two (NV12) or three (I420) contiguous byte ranges of the frame,
 // hence contiguous runs of base64 quads. Phase 1 decodes the quads of each range into LDS as
-// bytes - a lane takes 16 characters (4 quads, 12 bytes), loaded and byte-aligned exactly as
-// b64::b64_decode_body does: the aligned 16-byte word under its first character and, only when
-// its characters reach into it, the next one, so at most 15 bytes before a string and fewer than
-// 16 past it are read. A quad that straddles two ranges (or two workgroups' ranges) is decoded by
+// bytes - a lane takes 16 characters (4 quads, 12 bytes) through the shared window of
+// b64_decode.cuh (b64::load_window, which states the read bound); a range's last lane judges
+// only its own characters.
+// A quad that straddles two ranges (or two workgroups' ranges) is decoded by
 // every owner, so each character of the string is judged by at least one workgroup. One barrier;
 // phase 2 converts and stores the workgroup's 6 * pairs * WS floats, which are contiguous in the
 // NHWC image: thread t of an iteration stores floats [4 q, 4 q + 4), q = 256 i + t, so a wave's
@@ -54,11 +54,7 @@ __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
 
 __device__ __forceinline__ int clamp8(int acc) { return min(max(acc >> 20, 0), 255); }
 
-template <bool PREP>
-__device__ __forceinline__ float prepped(int v, int ch, const InputPrep& prep) {
-  const float f = (float)v;
-  return PREP ? __builtin_fmaf(f, b64::prep_a(prep, ch), b64::prep_b(prep, ch)) : f;
-}
+using b64::prepped;
 
 template <bool PREP>
 __global__ __launch_bounds__(kThreads) void b64_yuv_kernel(const B64Image* imgs, int images,
@@ -95,37 +91,16 @@ __global__ __launch_bounds__(kThreads) void b64_yuv_kernel(const B64Image* imgs,
     const int nq = in_y ? ry.nq : in_u ? ru.nq : rv.nq;
     const int lds = in_y ? ry.lds : in_u ? ru.lds : rv.lds;
     const int nch = min(16, 4 * nq - 16 * j);  // characters of the range in the window (4 .. 16)
-    const int64_t addr = d.off + 4 * (int64_t)q0 + 16 * j;
-    const int ph = (int)(addr & 15);
-    const uint8_t* base = bytes + (addr - ph);
-    const uint4 lo = *reinterpret_cast<const uint4*>(base);
-    // the second word only when the window reaches into it: it ends < 16 bytes past the window,
-    // and the window ends inside the string
-    const uint4 hi = ph + nch > 16 ? *reinterpret_cast<const uint4*>(base + 16)
-                                   : make_uint4(0, 0, 0, 0);
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t sh = (uint32_t)(ph & 3);
-    uint32_t x[4];
-    switch (ph >> 2) {  // (uniform over the lanes of one range)
-#define GALE_ALIGN_WORDS(D)                                \
-  _Pragma("unroll") for (int t = 0; t < 4; ++t) x[t] =     \
-      __builtin_amdgcn_alignbyte(w[t + (D) + 1], w[t + (D)], sh);
-      case 0: GALE_ALIGN_WORDS(0) break;
-      case 1: GALE_ALIGN_WORDS(1) break;
-      case 2: GALE_ALIGN_WORDS(2) break;
-      default: GALE_ALIGN_WORDS(3) break;
-#undef GALE_ALIGN_WORDS
-    }
-    // 4 characters -> 24 bits -> 3 bytes in memory order (byte 0 first)
+    // (the window ends inside the string: a range's quads are the string's; the phase is
+    // uniform over the lanes of one range; 4 q0 + 16 j < L <= 2^30)
+    const b64::Window win = b64::load_window(bytes, d.off, 4 * q0 + 16 * j, nch);
+    // 24 bits -> 3 bytes in memory order (byte 0 first)
     uint32_t r[4], judged = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      uint32_t inv;
-      const uint32_t sx = b64::b64_sextets4(x[t], &inv) & 0x3F3F3F3Fu;
-      const uint32_t h = ((sx & 0x003F003Fu) << 6) | ((sx >> 8) & 0x003F003Fu);
-      const uint32_t v = ((h & 0xFFFu) << 12) | (h >> 16);
-      r[t] = __builtin_bswap32(v) >> 8;
-      judged |= inv & b64::first_bytes(nch - 4 * t);  // (no padding: B is a multiple of 3)
+      r[t] = __builtin_bswap32(win.v[t]) >> 8;
+      // (no padding: B is a multiple of 3)
+      judged |= win.inv[t] & b64::first_bytes(nch - 4 * t);
     }
     bad |= judged != 0;
     // 12 bytes = 3 dwords at a 12-byte lane stride (conflict-free); the range's last lane only

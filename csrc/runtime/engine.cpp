@@ -982,15 +982,11 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   float* arena =
       arena_bytes ? reinterpret_cast<float*>(dev + pool.mirror_extra_offset()) : nullptr;
   try {
-    if (b64)
-      // (a YUV frame's string is that of an (HS / 2) x WS x 3 byte image to the ingest's plan,
-      // which checks it against its record; a packed-pixel string is that of an HS x WS x P one;
-      // there is no arena, so nothing is decoded)
-      ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
-                      cfg_.yuv_format ? cfg_.rec_h() / 2 : cfg_.rec_h(), cfg_.rec_w(),
-                      cfg_.packed_format ? packed_bpp(cfg_.packed_format) : cfg_.C, io, arena,
-                      arena_bytes);
-    else
+    if (b64) {
+      const PixelSource::Dims sd = cfg_.pixels.ingest_dims(cfg_.rec_h(), cfg_.rec_w(), cfg_.C);
+      ingest->run_b64(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked, sd.H,
+                      sd.W, sd.C, io, arena, arena_bytes);
+    } else
       ingest->run(lane, f, dev, pool.chunk_bytes(), cfg_.check_crcs && !f.crc_checked,
                   cfg_.rec_h(), cfg_.rec_w(), cfg_.C, io, arena, arena_bytes);
   } catch (const std::exception& e) {
@@ -999,8 +995,8 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
     return false;
   }
   b64_records_ += b64_accepted;  // (as the host path: records the scan accepted)
-  if (cfg_.yuv_format) yuv_records_ += b64_accepted;
-  if (cfg_.packed_format) packed_records_ += b64_accepted;
+  if (cfg_.pixels.kind() == PixelSource::YUV) yuv_records_ += b64_accepted;
+  if (cfg_.pixels.kind() == PixelSource::PACKED) packed_records_ += b64_accepted;
   std::vector<char> corrupt(n, 0);
   for (size_t b = 0; b < f.batches.size(); ++b)
     if (!io.batch_ok[b])
@@ -1139,8 +1135,8 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       if (r.status == codec::OK && fault_hit(parse_error_p_)) r.status = codec::BAD_ENVELOPE;
       if (b64 && r.status == codec::OK) {
         ++b64_records_;
-        if (cfg_.yuv_format) ++yuv_records_;
-        if (cfg_.packed_format) ++packed_records_;
+        if (cfg_.pixels.kind() == PixelSource::YUV) ++yuv_records_;
+        if (cfg_.pixels.kind() == PixelSource::PACKED) ++packed_records_;
       }
     }
     if (r.status == codec::OK && r.images > cfg_.max_batch) {

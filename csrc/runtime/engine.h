@@ -157,22 +157,13 @@ struct EngineConfig {
   // input_b64 with a GPU ingest attached (Ingest::run_b64): batch CRCs on the device and, with
   // ingest_parse, every string decoded into the fetch's image arena - the table step
   bool b64_ingest = false;
-  // input pixel format of b64 records (csrc/codec/yuv.h): YUV_NONE = interleaved RGB bytes;
-  // YUV_I420 / YUV_NV12 = every string is a YUV 4:2:0 frame of rec_h() x rec_w() (both even,
-  // C == 3, no nchw), converted with `yuv` where the strings are decoded. A GPU ingest then runs
-  // in its CRC-only form (ingest_parse off): the step decodes from the resident mirror
-  int yuv_format = 0;
-  YuvCoeffs yuv;
-  // PACKED_BGR24 / PACKED_RGBA / PACKED_BGRA / PACKED_GRAY (csrc/codec/pixfmt.h): every string
-  // is rec_h() x rec_w() pixels of packed_bpp bytes, unpacked to RGB where the strings are
-  // decoded (C == 3, no nchw, not with yuv_format). The GPU ingest rule is the YUV one: CRC-only
-  int packed_format = 0;
+  // what the b64 strings carry (csrc/codec/pixel_source.h): interleaved RGB bytes, a YUV 4:2:0
+  // frame of rec_h() x rec_w() or packed pixels, converted to RGB where the strings are decoded.
+  // For anything but RGB a GPU ingest runs in its CRC-only form (ingest_parse off): the step
+  // decodes from the resident mirror
+  PixelSource pixels;
   // bytes one b64 string carries
-  int64_t rec_bytes() const {
-    return packed_format ? packed_bytes(rec_h(), rec_w(), packed_format)
-           : yuv_format  ? yuv420_bytes(rec_h(), rec_w())
-                         : (int64_t)rec_h() * rec_w() * C;
-  }
+  int64_t rec_bytes() const { return pixels.bytes(rec_h(), rec_w(), C); }
   // batching (P7)
   int max_batch = 256;             // images per micro-batch (<= every replica's max)
   int max_wait_us = 2000;          // latency bound on batch formation

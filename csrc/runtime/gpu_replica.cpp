@@ -14,6 +14,7 @@
 #include <stdexcept>
 
 #include "../codec/json_codec.h"
+#include "b64_source.h"
 #include "metrics.h"
 #include "replica.h"
 
@@ -275,7 +276,7 @@ void GpuReplica::describe(const Batch& b, Slot& s) {
     if (b64_ && !p.preparsed) {
       p.b64_first = (int32_t)s.b64_offs.size();
       p.b64_n = codec::b64_image_offsets_bytes(r.value + r.arr_off, (size_t)r.arr_len,
-                                               rec_bytes(), s.b64_scan)
+                                               pixels_.bytes(recH_, recW_, C_), s.b64_scan)
                     ? (int32_t)s.b64_scan.size()
                     : -1;
       s.b64_offs.insert(s.b64_offs.end(), s.b64_scan.begin(), s.b64_scan.end());
@@ -450,26 +451,15 @@ GpuReplica::StepError GpuReplica::emit_step(Slot& s, int slot, hipStream_t st, c
     c = hipMemcpyAsync(s.d_meta + m.off, s.h_meta + m.off, m.bytes, hipMemcpyHostToDevice, st);
     if (c != hipSuccess) return {c, "H2D step metadata"};
   }
-  if (parse && b64_ && packed_format_) {
-    // packed pixels: the same table, status words and output as the RGB decode below
-    c = b64_packed_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
+  if (parse && b64_) {
+    // one decode launch, chosen by what the strings carry: the same table, status words and
+    // output for every source
+    const char* which = nullptr;
+    c = b64_source_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
                              s.d_bytes, recH_, recW_, C_, parsed,
                              status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
-                             dev ? hdr + kHdrB64 : nullptr, &prep_, packed_format_);
-    if (c != hipSuccess) return {c, "b64_packed_instances"};
-  } else if (parse && b64_ && yuv_format_) {
-    // YUV 4:2:0 frames: the same table, status words and output as the RGB decode below
-    c = b64_yuv_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table), s.d_bytes,
-                          recH_, recW_, C_, parsed,
-                          status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
-                          dev ? hdr + kHdrB64 : nullptr, &prep_, yuv_format_, yuv_);
-    if (c != hipSuccess) return {c, "b64_yuv_instances"};
-  } else if (parse && b64_) {
-    c = b64_decode_instances(dev ? mb : p.b64n, meta_at<B64Image>(s.d_meta, L.b64_table),
-                             s.d_bytes, recH_, recW_, C_, parsed,
-                             status ? status : meta_at<int>(s.d_meta, L.b64_status), st,
-                             dev ? hdr + kHdrB64 : nullptr, &prep_);
-    if (c != hipSuccess) return {c, "b64_decode_instances"};
+                             dev ? hdr + kHdrB64 : nullptr, &prep_, pixels_, &which);
+    if (c != hipSuccess) return {c, which};
   } else if (parse) {
     c = json_parse_instances(dev ? mb : p.nrec, dev ? L.tiles_cap : p.ntiles,
                              meta_at<JsonRecord>(s.d_meta, L.recs), meta_at<int>(s.d_meta, L.tiles),

@@ -55,19 +55,9 @@ void StubReplica::submit(Batch& b) {
     // an NCHW record is a rectangular array of dims (C, H, W) to the dims-agnostic decoder
     const bool nchw = prep_.nchw != 0;
     // (a b64 string's bytes are in record order too: [C][H][W] with nchw)
-    const int st = b64_ && packed_format_
-                       ? codec::parse_instances_packed_host(r.value, (size_t)r.len, RH, RW,
-                                                            packed_format_,
-                                                            parsed + (size_t)slot * rper,
-                                                            max_images_ - slot, &n)
-                   : b64_ && yuv_format_
-                       ? codec::parse_instances_yuv_host(r.value, (size_t)r.len, RH, RW,
-                                                         yuv_format_, yuv_,
-                                                         parsed + (size_t)slot * rper,
-                                                         max_images_ - slot, &n)
-                   : b64_ ? codec::parse_instances_b64_host(r.value, (size_t)r.len, RH, RW, C_,
-                                                            parsed + (size_t)slot * rper,
-                                                            max_images_ - slot, &n)
+    const int st = b64_ ? pixels_.parse_host(r.value, (size_t)r.len, RH, RW, C_,
+                                             parsed + (size_t)slot * rper, max_images_ - slot,
+                                             &n)
                         : codec::parse_instances_host(r.value, (size_t)r.len, nchw ? C_ : RH,
                                                       nchw ? RH : RW, nchw ? RW : C_,
                                                       parsed + (size_t)slot * rper,

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../codec/json_codec.h"
+#include "../codec/pixel_source.h"
 #include "batch_plan.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
@@ -132,15 +133,12 @@ class StubReplica : public Replica {
   void wait(Batch& b) override;
   // input preprocessing (InputPrep, gale/kernels.h) on the host-parsed images; before submit()
   void set_input_prep(const InputPrep& p) { prep_ = p; }
-  // base64 uint8 image records (EngineConfig::input_b64): decoded by the host decoder
-  void set_input_b64(bool on) { b64_ = on; }
-  // b64 records that carry YUV 4:2:0 frames (EngineConfig::yuv_format, csrc/codec/yuv.h): decoded
-  // and converted by the host twin (codec::parse_instances_yuv_host); with set_input_b64
-  void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
-  // b64 records that carry packed pixels (EngineConfig::packed_format, csrc/codec/pixfmt.h):
-  // decoded and unpacked by the host twin (codec::parse_instances_packed_host); with
-  // set_input_b64
-  void set_input_packed(int format) { packed_format_ = format; }
+  // base64 image records (EngineConfig::input_b64) whose strings carry `src`
+  // (EngineConfig::pixels): decoded, and converted to RGB, by the source's host parser
+  // (PixelSource::parse_host); before submit()
+  void set_input_b64(bool on, const PixelSource& src = PixelSource()) {
+    b64_ = on, pixels_ = src;
+  }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images, parsed
   // and preprocessed at that size into a source buffer and resized into the model-size images by
   // the form's host twin (InputResize::apply_host); the logits stay the function of the
@@ -151,9 +149,7 @@ class StubReplica : public Replica {
  private:
   InputPrep prep_;
   bool b64_ = false;
-  int yuv_format_ = 0;
-  YuvCoeffs yuv_;
-  int packed_format_ = 0;
+  PixelSource pixels_;
   std::optional<InputResize> resize_;
   std::vector<float> src_;  // resize_: the batch's images at the source size
   std::atomic<int64_t> resized_{0};
@@ -216,19 +212,14 @@ class GpuReplica : public Replica {
   // where it runs json_parse_instances otherwise. The batch's image descriptor table and (for
   // the steps that copy verdicts back) its status words take the place of the JsonRecord table
   // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
-  // map, no count pass. Before submit()
-  void set_input_b64(bool on) { b64_ = on; }
-  // b64 records that carry YUV 4:2:0 frames (EngineConfig::yuv_format, csrc/codec/yuv.h): the
-  // step runs b64_yuv_instances where it runs b64_decode_instances otherwise - same descriptor
-  // table, status words and output tensor, strings of yuv420_bytes(recH_, recW_) bytes; C must
-  // be 3 and the prep not nchw (the launcher refuses otherwise). With set_input_b64, before
-  // submit()
-  void set_input_yuv(int format, const YuvCoeffs& k) { yuv_format_ = format, yuv_ = k; }
-  // b64 records that carry packed pixels (EngineConfig::packed_format, csrc/codec/pixfmt.h): the
-  // step runs b64_packed_instances there - same descriptor table, status words and output
-  // tensor, strings of packed_bytes(recH_, recW_, format) bytes; C must be 3 and the prep not
-  // nchw (the launcher refuses otherwise). With set_input_b64, before submit()
-  void set_input_packed(int format) { packed_format_ = format; }
+  // map, no count pass. The strings carry `src` (EngineConfig::pixels): the one decode launch is
+  // the source's (b64_source_instances: b64_yuv_instances or b64_packed_instances for YUV frames
+  // or packed pixels) - same descriptor table, status words and output tensor, strings of
+  // src.bytes(recH_, recW_, C_) bytes; for those two C must be 3 and the prep not nchw (the
+  // launchers refuse otherwise). Before submit()
+  void set_input_b64(bool on, const PixelSource& src = PixelSource()) {
+    b64_ = on, pixels_ = src;
+  }
   // input resize (resize_plan.h, either form): the records carry r.HS() x r.WS() images. The
   // tables' device image (pack) is uploaded once and every slot gets a source tensor of
   // max_batch * HS * WS * C floats that never moves (captured steps stay valid); the step's
@@ -293,15 +284,7 @@ class GpuReplica : public Replica {
   std::shared_ptr<Executor> exec_;
   InputPrep prep_;
   bool b64_ = false;
-  int yuv_format_ = 0;  // YuvFormat of the b64 strings (0: RGB bytes)
-  YuvCoeffs yuv_;
-  int packed_format_ = 0;  // PackedFormat of the b64 strings (0: none)
-  // bytes one b64 string carries
-  int64_t rec_bytes() const {
-    return packed_format_ ? packed_bytes(recH_, recW_, packed_format_)
-           : yuv_format_  ? yuv420_bytes(recH_, recW_)
-                          : (int64_t)recH_ * recW_ * C_;
-  }
+  PixelSource pixels_;  // what the b64 strings carry
   // input resize: the tables' device image (one allocation; null = off, the records carry
   // model-size images, recH_ / recW_ == H_ / W_) and the kernel plan bound to it
   uint8_t* d_resize_ = nullptr;
