@@ -22,6 +22,7 @@
 #include "../runtime/ingest_plan.h"
 #include "../runtime/pack_tap.h"
 #include "../runtime/resize_plan.h"
+#include "plan_dict.h"
 #include "../kafka/protocol.h"
 #include "../kafka/wire.h"
 
@@ -653,6 +654,18 @@ void bind_host(py::module_& m) {
         py::arg("d_bytes") = (uint64_t)0, py::arg("input_base") = (uint64_t)0,
         "The host plan of a GPU replica's batch, laid out and filled "
         "(csrc/runtime/batch_plan.h)");
+  m.def("validate_plan",
+        [](py::list ops, std::vector<long long> buf_bytes, int max_batch, int slots, int chunk_ops,
+           int chunk_images) {
+          const PlanSpec spec = plan_spec_from_py(ops, std::move(buf_bytes), max_batch, slots, {},
+                                                  chunk_ops, chunk_images);
+          validate_plan(spec);
+          return plan_ops_to_py(spec);
+        },
+        py::arg("ops"), py::arg("buf_bytes"), py::arg("max_batch") = 256, py::arg("slots") = 2,
+        py::arg("chunk_ops") = 0, py::arg("chunk_images") = 0,
+        "What Executor(...) checks before its first HIP call (gale/forward_plan.h), without a "
+        "GPU: ValueError for a plan it would refuse, else the ops with every key written out");
   m.attr("BATCH_ATTR_OFFSET") = (int)kafka::kBatchAttrOffset;
   m.def("split_instances_b64", [](py::bytes arr, int H, int W, int C) -> py::object {
     const std::string_view s = view(arr);

@@ -14,6 +14,7 @@
 #include "../comm/rccl.h"
 #include "gale/executor.h"
 #include "gale/kernels.h"
+#include "plan_dict.h"
 
 namespace py = pybind11;
 
@@ -24,43 +25,7 @@ void bind_host(py::module_& m);  // codec / kafka / engine bindings (host_bindin
 namespace {
 
 using gale::ConvDesc;
-
-template <typename T>
-T get_or(const py::dict& d, const char* k, T dflt) {
-  return d.contains(k) ? d[k].cast<T>() : dflt;
-}
-
-ConvDesc desc_from_dict(const py::dict& d) {
-  ConvDesc c{};
-  c.H = d["H"].cast<int>();
-  c.W = d["W"].cast<int>();
-  c.Cin = d["Cin"].cast<int>();
-  c.Ho = d["Ho"].cast<int>();
-  c.Wo = d["Wo"].cast<int>();
-  c.Cout = d["Cout"].cast<int>();
-  c.KH = d["KH"].cast<int>();
-  c.KW = d["KW"].cast<int>();
-  c.stride = d["stride"].cast<int>();
-  c.pad = d["pad"].cast<int>();
-  c.K = d["K"].cast<int>();
-  c.Kpad = d["Kpad"].cast<int>();
-  c.Npad = d["Npad"].cast<int>();
-  c.relu = get_or<int>(d, "relu", 0);
-  c.has_res = get_or<int>(d, "has_res", 0);
-  c.res_H = get_or<int>(d, "res_H", c.Ho);
-  c.res_W = get_or<int>(d, "res_W", c.Wo);
-  c.res_C = get_or<int>(d, "res_C", c.Cout);
-  c.res_stride = get_or<int>(d, "res_stride", 1);
-  c.in_f32 = get_or<int>(d, "in_f32", 0);
-  c.out_f32 = get_or<int>(d, "out_f32", 0);
-  c.fp8 = get_or<int>(d, "fp8", 0);
-  c.in_scale = get_or<float>(d, "in_scale", 1.0f);
-  c.out_scale = get_or<float>(d, "out_scale", 1.0f);
-  c.res_scale = get_or<float>(d, "res_scale", 1.0f);
-  c.stem = get_or<int>(d, "stem", 0);
-  c.f32 = get_or<int>(d, "f32", 0);
-  return c;
-}
+using gale::desc_from_dict;
 
 inline hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline void* P(uintptr_t p) { return reinterpret_cast<void*>(p); }
@@ -82,32 +47,6 @@ std::optional<gale::InputPrep> prep_from(const char* name,
   }
   prep.nchw = nchw ? 1 : 0;
   return prep;
-}
-
-gale::PlanOp op_from_dict(const py::dict& d) {
-  gale::PlanOp op;
-  op.kind = d["kind"].cast<int>();
-  if (d.contains("conv")) op.conv = desc_from_dict(d["conv"].cast<py::dict>());
-  if (d.contains("p")) {
-    auto v = d["p"].cast<std::vector<int>>();
-    for (size_t i = 0; i < v.size() && i < 8; ++i) op.p[i] = v[i];
-  }
-  op.in = d["in"].cast<int>();
-  op.out = d["out"].cast<int>();
-  op.res = get_or<int>(d, "res", -1);
-  op.w = P(get_or<uintptr_t>(d, "w", 0));
-  op.bias = static_cast<const float*>(P(get_or<uintptr_t>(d, "bias", 0)));
-  op.wscale = static_cast<const float*>(P(get_or<uintptr_t>(d, "wscale", 0)));
-  if (d.contains("ptrs"))
-    for (auto v : d["ptrs"].cast<std::vector<uintptr_t>>()) op.ptrs.push_back(P(v));
-  if (d.contains("scales")) op.scales = d["scales"].cast<std::vector<float>>();
-  op.fp8 = get_or<int>(d, "et", get_or<int>(d, "fp8", 0));  // pool/head activation ElemType
-  op.scale = get_or<float>(d, "scale", 1.0f);
-  if (d.contains("bpi")) {
-    auto v = d["bpi"].cast<std::vector<long long>>();
-    for (size_t i = 0; i < v.size() && i < 3; ++i) op.bpi[i] = v[i];
-  }
-  return op;
 }
 
 }  // namespace
@@ -630,15 +569,10 @@ PYBIND11_MODULE(_C, m) {
   py::class_<gale::Executor, std::shared_ptr<gale::Executor>>(m, "Executor")
       .def(py::init([](int device, py::list ops, std::vector<long long> buf_bytes, int max_batch,
                        int slots, std::vector<int> buckets, int chunk_ops, int chunk_images) {
-             gale::PlanSpec spec;
-             for (auto o : ops) spec.ops.push_back(op_from_dict(o.cast<py::dict>()));
-             spec.buf_bytes_per_image = std::move(buf_bytes);
-             spec.max_batch = max_batch;
-             spec.slots = slots;
-             spec.buckets = std::move(buckets);
-             spec.chunk_ops = chunk_ops;
-             spec.chunk_images = chunk_images;
-             return std::make_shared<gale::Executor>(device, std::move(spec));
+             // a plan that does not parse or validate is a ValueError before any HIP call
+             return std::make_shared<gale::Executor>(
+                 device, gale::plan_spec_from_py(ops, std::move(buf_bytes), max_batch, slots,
+                                                 std::move(buckets), chunk_ops, chunk_images));
            }),
            py::arg("device"), py::arg("ops"), py::arg("buf_bytes"), py::arg("max_batch"),
            py::arg("slots") = 2, py::arg("buckets") = std::vector<int>{}, py::arg("chunk_ops") = 0,

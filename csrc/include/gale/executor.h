@@ -14,67 +14,15 @@
 #include <utility>
 #include <vector>
 
+#include "gale/forward_plan.h"
 #include "gale/kernels.h"
 
 namespace gale {
 
-enum OpKind : int {
-  OP_CONV = 0,      // conv2d (also dense layers as 1x1 convs)
-  OP_MAXPOOL = 1,   // p[0..6] = H, W, C, k, s, pad, Ho ; p[7] = Wo
-  OP_AVGPOOL = 2,   // p[0] = HW, p[1] = C
-  OP_HEAD = 3,      // p[0] = HW, p[1] = C, p[2] = N   (pool + dense(fp32 w) + softmax)
-  OP_SOFTMAX = 4,   // p[0] = N, p[1] = ld
-  OP_RESNET20 = 5,  // whole-network fused CIFAR ResNet-20; ptrs = 19 w, 19 b, fc_w, fc_b
-                    // (+ 19 wscale for fp8), scales = 19 s_in, 19 s_out, 19 s_res (fp8)
-  OP_STEM_PACK = 6, // p[0..4] = H, W, C, Wp, lp  (fp32 input -> packed-stem bf16 image)
-  OP_BN_ACT = 7,    // p[0..7] = HW, Wo, C, relu, res_H, res_W, res_C, res_stride; w = BN scale,
-                    // bias = BN shift (unfolded-BN plan: standalone BatchNorm + add + ReLU)
-  OP_LENET5 = 8,    // whole-network fused MNIST LeNet-5; ptrs = w1 b1 w2 b2 w3 b3 w4 b4 w5 b5
-  OP_BOTTLENECK = 9,  // one whole ResNet-50 56x56 bottleneck (bottleneck56); ptrs = w1 b1 w2 b2
-                      // w3 b3 [wd bd]; p[0] = cin, p[1] = down (projection shortcut)
-  OP_STEM_POOL = 10,  // ResNet-50 stem conv + max-pool (stem_pool); conv = the stem's desc,
-                      // w / bias = its weights; p[0..7] = the max-pool's H W C k s pad Ho Wo
-  OP_CONV_PROJ = 11,  // bottleneck conv3 + projection shortcut as one GEMM (conv2d_gemm_proj):
-                      // conv = conv3's desc, in = its input, res = the block input (the
-                      // projection's source); ptrs = w3 b3 wd bd; p[0..4] = H2 W2 Cin2 stride2 Kpad2
-};
-
-// Buffer ids: 0 = network input (fp32 NHWC), 1 = network output (fp32 [B, classes]),
-// >= 2 = activation workspace.
-struct PlanOp {
-  int kind = 0;
-  ConvDesc conv{};
-  int p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int in = 0, out = 0, res = -1;
-  const void* w = nullptr;
-  const float* bias = nullptr;
-  const float* wscale = nullptr;
-  std::vector<const void*> ptrs;  // OP_RESNET20 parameter pointers
-  std::vector<float> scales;      // OP_RESNET20 fp8 activation scales
-  int fp8 = 0;        // pool / head ops: activation ElemType (0 bf16, 1 e4m3, 2 fp32)
-  float scale = 1.f;  // head: input activation scale (fp8)
-  long long bpi[3] = {0, 0, 0};  // bytes per image of the in / out / res tensors (chunking)
-};
-
-struct PlanSpec {
-  std::vector<PlanOp> ops;
-  std::vector<long long> buf_bytes_per_image;  // indexed by buffer id (ids 0 and 1 included)
-  int max_batch = 256;
-  int slots = 2;                               // independent I/O buffer sets (pipelining depth)
-  std::vector<int> buckets;                    // graph batch buckets (ascending); empty = powers of 2
-  // Batch chunking of the leading ops: ops [0, chunk_ops) run once per chunk of chunk_images
-  // images (operands offset by the first image of the chunk times their PlanOp::bpi; activations
-  // are batch-major), the
-  // rest once over the whole batch. Keeps the wide early tensors (ResNet-50 56x56x256 at batch
-  // 256: 411 MB each) small enough to stay in the 256 MB Infinity Cache between producer and
-  // consumer. 0 = off. The plan must keep every tensor that outlives the prefix in a buffer no
-  // other prefix tensor uses (a later chunk would overwrite it): build_plan(chunk_layers=...).
-  int chunk_ops = 0;
-  int chunk_images = 0;
-};
-
 class Executor {
  public:
+  // validate_plan(spec) and the stem_pool geometry check come first: a refused plan throws
+  // std::invalid_argument before any HIP call
   Executor(int device, PlanSpec spec);
   ~Executor();
   Executor(const Executor&) = delete;

@@ -13,19 +13,17 @@ void check_hip(hipError_t e, const char* what) {
 }
 
 Executor::Executor(int device, PlanSpec spec) : device_(device), spec_(std::move(spec)) {
-  if (spec_.buf_bytes_per_image.size() < 2) throw std::invalid_argument("plan needs >= 2 buffers");
-  if (spec_.max_batch <= 0 || spec_.slots <= 0) throw std::invalid_argument("bad max_batch/slots");
+  validate_plan(spec_);
+  for (size_t i = 0; i < spec_.ops.size(); ++i)
+    if (const StemPoolOp* o = std::get_if<StemPoolOp>(&spec_.ops[i].params))
+      if (!stem_pool_supported(o->conv, o->g.H, o->g.W, o->g.C, o->g.k, o->g.s, o->g.pad, o->g.Ho,
+                               o->g.Wo))
+        throw std::invalid_argument("plan op " + std::to_string(i) +
+                                    " (stem_pool): unsupported geometry");
   buckets_ = spec_.buckets;
   if (buckets_.empty()) {
     for (int b = 1; b < spec_.max_batch; b *= 2) buckets_.push_back(b);
     buckets_.push_back(spec_.max_batch);
-  }
-  if (spec_.chunk_ops < 0 || spec_.chunk_ops > (int)spec_.ops.size() || spec_.chunk_images < 0)
-    throw std::invalid_argument("bad chunk_ops / chunk_images");
-  for (int i = 0; spec_.chunk_images > 0 && i < spec_.chunk_ops; ++i) {
-    const PlanOp& op = spec_.ops[i];
-    if (op.bpi[0] <= 0 || op.bpi[1] <= 0 || (op.res >= 0 && op.bpi[2] <= 0))
-      throw std::invalid_argument("chunked plan op without per-image operand bytes");
   }
   std::sort(buckets_.begin(), buckets_.end());
   buckets_.erase(std::unique(buckets_.begin(), buckets_.end()), buckets_.end());
@@ -87,7 +85,7 @@ void Executor::launch_all(int batch, void* const* bufs, hipStream_t stream, cons
 bool Executor::device_batch_ok() const {
   if (spec_.ops.empty() || spec_.chunk_ops > 0) return false;
   for (const PlanOp& op : spec_.ops)
-    if (op.kind != OP_RESNET20 && op.kind != OP_LENET5) return false;
+    if (op.kind() != OP_RESNET20 && op.kind() != OP_LENET5) return false;
   return true;
 }
 
@@ -109,6 +107,76 @@ void Executor::launch_table(int slot, int batch, const InputTable& tab, hipStrea
   launch_ops(0, 1, batch, bufs_[slot].data(), stream, 0, nullptr, so, nullptr, &tab);
 }
 
+namespace {
+
+// One op's launch: the operands of this launch, and per kind the launcher with the op's fields.
+struct Launch {
+  int batch;
+  const void* in;
+  void* out;
+  const void* res;
+  hipStream_t stream;
+  const int* d_batch;
+  const StepOut* so;
+  const float* const* xs;
+  const InputTable* tab;
+
+  hipError_t operator()(const ConvOp& o) const {
+    return conv2d(o.conv, batch, in, o.w, o.bias, o.wscale, res, out, stream);
+  }
+  hipError_t operator()(const MaxPoolOp& o) const {
+    const PoolGeom& g = o.g;
+    return maxpool2d(batch, g.H, g.W, g.C, g.k, g.s, g.pad, g.Ho, g.Wo, in, out, o.et, stream);
+  }
+  hipError_t operator()(const AvgPoolOp& o) const {
+    return avgpool_global(batch, o.HW, o.C, in, out, o.et, stream);
+  }
+  hipError_t operator()(const HeadOp& o) const {
+    return head_pool_dense_softmax(batch, o.HW, o.C, o.N, in, o.et, o.in_scale, o.w, o.bias,
+                                   static_cast<float*>(out), stream);
+  }
+  hipError_t operator()(const SoftmaxOp& o) const {
+    return softmax_rows(batch, o.N, o.ld, static_cast<const float*>(in),
+                        static_cast<float*>(out), stream);
+  }
+  hipError_t operator()(const StemPackOp& o) const {
+    return stem_pack(batch, o.H, o.W, o.C, o.Wp, o.lp, static_cast<const float*>(in), out, stream);
+  }
+  hipError_t operator()(const BnActOp& o) const {
+    return bn_act(batch, o.HW, o.Wo, o.C, in, o.scale, o.shift, res, o.res_H, o.res_W, o.res_C,
+                  o.res_stride, o.relu, out, stream, o.et);
+  }
+  // the whole-network kernels: the plan's struct with this launch's members set on a copy
+  template <typename Params>
+  Params per_launch(Params p) const {
+    p.batch_dev = d_batch;
+    p.xs = xs;
+    if (so) p.so = *so;
+    return p;
+  }
+  hipError_t operator()(const ResNet20Params& p) const {
+    return resnet20_fused_forward(per_launch(p), batch, static_cast<const float*>(in),
+                                  static_cast<float*>(out), stream, tab);
+  }
+  hipError_t operator()(const LeNet5Params& p) const {
+    return lenet5_fused_forward(per_launch(p), batch, static_cast<const float*>(in),
+                                static_cast<float*>(out), stream, tab);
+  }
+  hipError_t operator()(const BottleneckParams& p) const {
+    return bottleneck56(p, batch, in, out, stream);
+  }
+  hipError_t operator()(const StemPoolOp& o) const {
+    return stem_pool(batch, in, o.w, o.bias, out, stream);
+  }
+  hipError_t operator()(const ConvProjOp& o) const {
+    return conv2d_gemm_proj(o.conv, batch, in, o.w, o.bias, res, o.H2, o.W2, o.Cin2, o.stride2,
+                            o.Kpad2, o.wd, o.bd, out, stream);
+  }
+};
+
+}  // namespace
+
+// Every id and field was checked when the executor was built (validate_plan).
 void Executor::launch_ops(size_t begin, size_t end, int batch, void* const* bufs,
                           hipStream_t stream, int c0, const int* d_batch, const StepOut* so,
                           const float* const* xs, const InputTable* tab) {
@@ -117,122 +185,10 @@ void Executor::launch_ops(size_t begin, size_t end, int batch, void* const* bufs
   };
   for (size_t oi = begin; oi < end; ++oi) {
     const PlanOp& op = spec_.ops[oi];
-    const void* in = at(op.in, op.bpi[0]);
-    void* out = at(op.out, op.bpi[1]);
-    void* res = op.res >= 0 ? at(op.res, op.bpi[2]) : nullptr;
-    hipError_t e = hipSuccess;
-    switch (op.kind) {
-      case OP_CONV:
-        e = conv2d(op.conv, batch, in, op.w, op.bias, op.wscale, res, out, stream);
-        break;
-      case OP_MAXPOOL:
-        e = maxpool2d(batch, op.p[0], op.p[1], op.p[2], op.p[3], op.p[4], op.p[5], op.p[6], op.p[7],
-                      in, out, op.fp8, stream);
-        break;
-      case OP_AVGPOOL:
-        e = avgpool_global(batch, op.p[0], op.p[1], in, out, op.fp8, stream);
-        break;
-      case OP_HEAD:
-        e = head_pool_dense_softmax(batch, op.p[0], op.p[1], op.p[2], in, op.fp8, op.scale,
-                                    static_cast<const float*>(op.w), op.bias,
-                                    static_cast<float*>(out), stream);
-        break;
-      case OP_STEM_PACK:
-        e = stem_pack(batch, op.p[0], op.p[1], op.p[2], op.p[3], op.p[4],
-                      static_cast<const float*>(in), out, stream);
-        break;
-      case OP_SOFTMAX:
-        e = softmax_rows(batch, op.p[0], op.p[1], static_cast<const float*>(in),
-                         static_cast<float*>(out), stream);
-        break;
-      case OP_BN_ACT:
-        e = bn_act(batch, op.p[0], op.p[1], op.p[2], in, static_cast<const float*>(op.w), op.bias,
-                   res, op.p[4], op.p[5], op.p[6], op.p[7],
-                   op.p[3], out, stream, (int)op.fp8);
-        break;
-      case OP_RESNET20: {
-        const bool f8 = op.fp8 != 0;
-        if (op.ptrs.size() != (f8 ? 59u : 40u) || (f8 && op.scales.size() != 57))
-          throw std::invalid_argument("resnet20 op: bad pointer / scale count");
-        ResNet20Params rp{};
-        for (int i = 0; i < 19; ++i) {
-          rp.w[i] = op.ptrs[i];
-          rp.b[i] = static_cast<const float*>(op.ptrs[19 + i]);
-        }
-        rp.fc_w = static_cast<const float*>(op.ptrs[38]);
-        rp.fc_b = static_cast<const float*>(op.ptrs[39]);
-        rp.fp8 = f8 ? 1 : 0;
-        rp.batch_dev = d_batch;
-        rp.xs = xs;
-        if (so) rp.so = *so;
-        if (f8)
-          for (int i = 0; i < 19; ++i) {
-            rp.ws[i] = static_cast<const float*>(op.ptrs[40 + i]);
-            rp.s_in[i] = op.scales[i];
-            rp.s_out[i] = op.scales[19 + i];
-            rp.s_res[i] = op.scales[38 + i];
-          }
-        e = resnet20_fused_forward(rp, batch, static_cast<const float*>(in),
-                                   static_cast<float*>(out), stream, tab);
-        break;
-      }
-      case OP_LENET5: {
-        if (op.ptrs.size() != 10u) throw std::invalid_argument("lenet5 op: bad pointer count");
-        LeNet5Params lp{};
-        lp.w1 = op.ptrs[0];
-        lp.b1 = static_cast<const float*>(op.ptrs[1]);
-        lp.w2 = op.ptrs[2];
-        lp.b2 = static_cast<const float*>(op.ptrs[3]);
-        lp.w3 = op.ptrs[4];
-        lp.b3 = static_cast<const float*>(op.ptrs[5]);
-        lp.w4 = op.ptrs[6];
-        lp.b4 = static_cast<const float*>(op.ptrs[7]);
-        lp.w5 = static_cast<const float*>(op.ptrs[8]);
-        lp.b5 = static_cast<const float*>(op.ptrs[9]);
-        lp.batch_dev = d_batch;
-        lp.xs = xs;
-        if (so) lp.so = *so;
-        e = lenet5_fused_forward(lp, batch, static_cast<const float*>(in),
-                                 static_cast<float*>(out), stream, tab);
-        break;
-      }
-      case OP_BOTTLENECK: {
-        const bool down = op.p[1] != 0;
-        if (op.ptrs.size() != (down ? 8u : 6u))
-          throw std::invalid_argument("bottleneck op: bad pointer count");
-        BottleneckParams bp;
-        bp.w1 = op.ptrs[0];
-        bp.b1 = static_cast<const float*>(op.ptrs[1]);
-        bp.w2 = op.ptrs[2];
-        bp.b2 = static_cast<const float*>(op.ptrs[3]);
-        bp.w3 = op.ptrs[4];
-        bp.b3 = static_cast<const float*>(op.ptrs[5]);
-        if (down) {
-          bp.wd = op.ptrs[6];
-          bp.bd = static_cast<const float*>(op.ptrs[7]);
-        }
-        bp.cin = op.p[0];
-        bp.down = down ? 1 : 0;
-        e = bottleneck56(bp, batch, in, out, stream);
-        break;
-      }
-      case OP_CONV_PROJ:
-        if (op.ptrs.size() != 4u || res == nullptr)
-          throw std::invalid_argument("conv_proj op: bad operands");
-        e = conv2d_gemm_proj(op.conv, batch, in, op.ptrs[0], static_cast<const float*>(op.ptrs[1]),
-                             res, op.p[0], op.p[1], op.p[2], op.p[3], op.p[4], op.ptrs[2],
-                             static_cast<const float*>(op.ptrs[3]), out, stream);
-        break;
-      case OP_STEM_POOL:
-        if (!stem_pool_supported(op.conv, op.p[0], op.p[1], op.p[2], op.p[3], op.p[4], op.p[5],
-                                 op.p[6], op.p[7]))
-          throw std::invalid_argument("stem_pool op: unsupported geometry");
-        e = stem_pool(batch, in, op.w, op.bias, out, stream);
-        break;
-      default:
-        throw std::invalid_argument("unknown plan op kind");
-    }
-    check_hip(e, "plan op launch");
+    const Launch launch{batch, at(op.in, op.bpi[0]), at(op.out, op.bpi[1]),
+                        op.res >= 0 ? at(op.res, op.bpi[2]) : nullptr,
+                        stream, d_batch, so, xs, tab};
+    check_hip(std::visit(launch, op.params), "plan op launch");
   }
 }
 

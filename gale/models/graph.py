@@ -417,11 +417,10 @@ def is_mnist_lenet5(net: Network) -> bool:
 
 def _fused_lenet5_plan(net: Network, base_ptr: int) -> Tuple[List[dict], List[int]]:
     layout, _ = param_layout(net, "bf16")
-    names = ("conv1", "conv2", "fc1", "fc2", "fc3")
-    ptrs = []
-    for nm in names:
-        ptrs += [base_ptr + layout[f"{nm}.w"].offset, base_ptr + layout[f"{nm}.b"].offset]
-    op = dict(kind=OP_LENET5, **{"in": 0}, out=1, ptrs=ptrs)
+    op = _op(OP_LENET5, 0, 1, layer=len(net.layers) - 1)
+    for i, nm in enumerate(("conv1", "conv2", "fc1", "fc2", "fc3"), 1):
+        op[f"w{i}"] = base_ptr + layout[f"{nm}.w"].offset
+        op[f"b{i}"] = base_ptr + layout[f"{nm}.b"].offset
     return [op], [_tensor_bytes(net, "input"), net.classes * 4]
 
 
@@ -430,16 +429,41 @@ def _fused_resnet20_plan(net: Network, base_ptr: int, wdtype: str = "bf16",
                          ) -> Tuple[List[dict], List[int]]:
     layout, _ = param_layout(net, wdtype)
     convs = [L for L in net.layers if isinstance(L, Conv)]
-    ptrs = [base_ptr + layout[f"{L.name}.w"].offset for L in convs]
-    ptrs += [base_ptr + layout[f"{L.name}.b"].offset for L in convs]
-    ptrs += [base_ptr + layout["fc.w"].offset, base_ptr + layout["fc.b"].offset]
-    op = dict(kind=OP_RESNET20, **{"in": 0}, out=1, ptrs=ptrs)
-    if wdtype == "fp8":
-        op["fp8"] = 1
-        op["ptrs"] = ptrs + [base_ptr + layout[f"{L.name}.s"].offset for L in convs]
-        op["scales"] = ([act_scales[L.inp] for L in convs] + [act_scales[L.out] for L in convs]
-                        + [act_scales[L.residual] if L.residual else 1.0 for L in convs])
+    fp8 = wdtype == "fp8"
+    op = _op(OP_RESNET20, 0, 1, layer=len(net.layers) - 1, fp8=int(fp8),
+             w=[base_ptr + layout[f"{L.name}.w"].offset for L in convs],
+             b=[base_ptr + layout[f"{L.name}.b"].offset for L in convs],
+             fc_w=base_ptr + layout["fc.w"].offset, fc_b=base_ptr + layout["fc.b"].offset,
+             # fp8 only: the weight scales and the activation scales of each conv's input /
+             # output / residual
+             ws=[base_ptr + layout[f"{L.name}.s"].offset if fp8 else 0 for L in convs],
+             s_in=[act_scales[L.inp] if fp8 else 0.0 for L in convs],
+             s_out=[act_scales[L.out] if fp8 else 0.0 for L in convs],
+             s_res=[(act_scales[L.residual] if L.residual else 1.0) if fp8 else 0.0
+                    for L in convs])
     return [op], [_tensor_bytes(net, "input"), net.classes * 4]
+
+
+def _op(kind: int, inp: int, out: int, res: int = -1, bpi=(0, 0, 0), *, layer: int,
+        **fields) -> dict:
+    """One plan op: what every op has - the kernel, its buffer ids, the bytes per image of its
+    in / out / res tensors (batch chunking) and the last layer it covers - then the named fields
+    of its kind (csrc/include/gale/forward_plan.h; the keys: csrc/bindings/plan_dict.cpp)."""
+    return {"kind": kind, "in": inp, "out": out, "res": res, "bpi": list(bpi), "layer": layer,
+            **fields}
+
+
+def _conv_desc(d: Dict) -> Dict:
+    """The complete ConvDesc of a conv's geometry and flags: every field the plan leaves out at
+    the value the native parser gives it."""
+    full = dict(relu=0, has_res=0, res_H=d["Ho"], res_W=d["Wo"], res_C=d["Cout"], res_stride=1,
+                in_f32=0, out_f32=0, fp8=0, in_scale=1.0, out_scale=1.0, res_scale=1.0, stem=0,
+                f32=0)
+    full.update(d)
+    return full
+
+
+_POOL_KEYS = ("H", "W", "C", "k", "s", "pad", "Ho", "Wo")
 
 
 def _tensor_bytes(net: Network, name: str, wdtype: str = "bf16") -> int:
@@ -472,12 +496,12 @@ def fuse_stem_pool(ops: List[dict]) -> List[dict]:
         if (i + 1 < len(ops) and c["kind"] == OP_CONV and c["conv"].get("stem")
                 and ops[i + 1]["kind"] == OP_MAXPOOL and ops[i + 1]["in"] == c["out"]):
             m, d = ops[i + 1], c["conv"]
-            H, W, C, k, s_, p, Ho, Wo = m["p"]
+            pool = {k: m[k] for k in _POOL_KEYS}
             if (d["H"] == 224 and d["W"] == 230 and d["Ho"] == 112 and d["Wo"] == 112
                     and d["Cout"] == 64 and d["Npad"] == 64 and d["K"] == 256 and d["relu"]
                     and not d.get("has_res") and not d.get("fp8") and not d.get("f32")
-                    and (H, W, C, k, s_, p, Ho, Wo) == (112, 112, 64, 3, 2, 1, 56, 56)
-                    and m.get("et", 0) == 0):
+                    and pool == dict(H=112, W=112, C=64, k=3, s=2, pad=1, Ho=56, Wo=56)
+                    and m["et"] == 0):
                 live = False
                 for o in ops[i + 2:]:  # the stem output's buffer, read before it is rewritten?
                     if o.get("in") == c["out"] or o.get("res", -1) == c["out"]:
@@ -486,9 +510,9 @@ def fuse_stem_pool(ops: List[dict]) -> List[dict]:
                     if o.get("out") == c["out"]:
                         break
                 if not live:
-                    out.append(dict(kind=OP_STEM_POOL, conv=d, **{"in": c["in"]}, out=m["out"],
-                                    res=-1, w=c["w"], bias=c["bias"], p=list(m["p"]),
-                                    bpi=[c["bpi"][0], m["bpi"][1], 0], layer=m.get("layer", 0)))
+                    out.append(_op(OP_STEM_POOL, c["in"], m["out"],
+                                   bpi=[c["bpi"][0], m["bpi"][1], 0], layer=m["layer"],
+                                   conv=d, w=c["w"], bias=c["bias"], **pool))
                     i += 2
                     continue
         out.append(c)
@@ -529,12 +553,12 @@ def fuse_bottlenecks(ops: List[dict]) -> List[dict]:
                 and not live_after(j + 2, ops[j]["out"]) and not live_after(j + 3, ops[j + 1]["out"])
                 and (down is None or not live_after(j + 3, down["out"]))):
             c1, c2, c3 = ops[j], ops[j + 1], ops[j + 2]
-            ptrs = [c1["w"], c1["bias"], c2["w"], c2["bias"], c3["w"], c3["bias"]]
-            if down is not None:
-                ptrs += [down["w"], down["bias"]]
-            out.append(dict(kind=OP_BOTTLENECK, **{"in": c1["in"]}, out=c3["out"], res=-1,
-                            p=[c1["conv"]["Cin"], int(down is not None)], ptrs=ptrs,
-                            bpi=[c1["bpi"][0], c3["bpi"][1], 0], layer=c3.get("layer", 0)))
+            out.append(_op(OP_BOTTLENECK, c1["in"], c3["out"],
+                           bpi=[c1["bpi"][0], c3["bpi"][1], 0], layer=c3["layer"],
+                           w1=c1["w"], b1=c1["bias"], w2=c2["w"], b2=c2["bias"], w3=c3["w"],
+                           b3=c3["bias"], wd=down["w"] if down else 0,
+                           bd=down["bias"] if down else 0, cin=c1["conv"]["Cin"],
+                           down=int(down is not None)))
             i = j + 3
             continue
         out.append(ops[i])
@@ -580,12 +604,12 @@ def fuse_projections(ops: List[dict], pairs: Dict[int, int]) -> List[dict]:
             dn = ops[pairs[i]]
             dd, cd = dn["conv"], dict(op["conv"])
             for k in ("has_res", "res_H", "res_W", "res_C", "res_stride"):
-                cd.pop(k, None)
-            out.append(dict(kind=OP_CONV_PROJ, conv=cd, **{"in": op["in"]}, out=op["out"],
-                            res=dn["in"], ptrs=[op["w"], op["bias"], dn["w"], dn["bias"]],
-                            p=[dd["H"], dd["W"], dd["Cin"], dd["stride"], dd["Kpad"]],
-                            bpi=[op["bpi"][0], op["bpi"][1], dn["bpi"][0]],
-                            layer=op.get("layer", 0)))
+                del cd[k]  # (conv3 without its residual)
+            out.append(_op(OP_CONV_PROJ, op["in"], op["out"], dn["in"],
+                           bpi=[op["bpi"][0], op["bpi"][1], dn["bpi"][0]], layer=op["layer"],
+                           conv=_conv_desc(cd), w=op["w"], bias=op["bias"], wd=dn["w"],
+                           bd=dn["bias"], H2=dd["H"], W2=dd["W"], Cin2=dd["Cin"],
+                           stride2=dd["stride"], Kpad2=dd["Kpad"]))
             continue
         out.append(op)
     return out
@@ -684,8 +708,8 @@ def build_plan(net: Network, base_ptr: int, wdtype: str = "bf16",
                 h, w, c = net.shapes[L.inp]
                 src = len(buf_bytes)
                 buf_bytes.append(h * gm["W"] * 4 * 2)
-                ops.append(dict(kind=OP_STEM_PACK, p=[h, w, c, gm["W"], 3], **{"in": 0},
-                                out=src, bpi=[tbytes["input"], buf_bytes[src], 0]))
+                ops.append(_op(OP_STEM_PACK, 0, src, bpi=[tbytes["input"], buf_bytes[src], 0],
+                               layer=i, H=h, W=w, C=c, Wp=gm["W"], lp=3))
                 d["in_f32"] = 0
             d["out_f32"] = int(L.out_f32)
             d["fp8"] = int(fp8)
@@ -705,54 +729,50 @@ def build_plan(net: Network, base_ptr: int, wdtype: str = "bf16",
                     d["res_scale"] = act_scales[L.residual]
                 res = buf_of[L.residual]
             in_bpi = buf_bytes[src] if gm.get("stem") else tbytes[L.inp]
-            op = dict(kind=OP_CONV, conv=d, **{"in": src}, out=buf_of[out_name], res=res,
-                      w=base_ptr + layout[f"{L.name}.w"].offset,
-                      bias=base_ptr + layout[f"{L.name}.b"].offset,
-                      bpi=[in_bpi, tbytes[out_name], tbytes[L.residual] if res >= 0 else 0])
-            if wdtype == "fp8":
-                op["wscale"] = base_ptr + layout[f"{L.name}.s"].offset
             conv_op[L.name] = len(ops)
-            ops.append(op)
+            ops.append(_op(OP_CONV, src, buf_of[out_name], res,
+                           bpi=[in_bpi, tbytes[out_name], tbytes[L.residual] if res >= 0 else 0],
+                           layer=i, conv=_conv_desc(d),
+                           w=base_ptr + layout[f"{L.name}.w"].offset,
+                           bias=base_ptr + layout[f"{L.name}.b"].offset,
+                           wscale=base_ptr + layout[f"{L.name}.s"].offset if fp8 else 0))
             if unfold:
                 ho, wo, c = net.shapes[L.out]
-                bn = dict(kind=OP_BN_ACT, **{"in": buf_of[out_name]}, out=buf_of[out_name], res=-1,
-                          w=base_ptr + layout[f"{L.name}.bn_s"].offset,
-                          bias=base_ptr + layout[f"{L.name}.bn_t"].offset,
-                          et=2 if f32 else 0, bpi=[tbytes[out_name], tbytes[out_name], 0])
-                p = [ho * wo, wo, stored_channels(c), int(L.relu), 0, 0, 0, 1]
+                bn = _op(OP_BN_ACT, buf_of[out_name], buf_of[out_name],
+                         bpi=[tbytes[out_name], tbytes[out_name], 0], layer=i,
+                         HW=ho * wo, Wo=wo, C=stored_channels(c), relu=int(L.relu),
+                         res_H=0, res_W=0, res_C=0, res_stride=1, et=2 if f32 else 0,
+                         scale=base_ptr + layout[f"{L.name}.bn_s"].offset,
+                         shift=base_ptr + layout[f"{L.name}.bn_t"].offset)
                 if L.residual is not None:
                     rh, rw, rc = net.shapes[L.residual]
-                    p[4:] = [rh, rw, stored_channels(rc), 2 if L.res_mode == "pad" else 1]
-                    bn["res"] = buf_of[L.residual]
+                    bn.update(res=buf_of[L.residual], res_H=rh, res_W=rw,
+                              res_C=stored_channels(rc),
+                              res_stride=2 if L.res_mode == "pad" else 1)
                     bn["bpi"][2] = tbytes[L.residual]
-                bn["p"] = p
                 ops.append(bn)
         elif isinstance(L, MaxPool):
             h, w, c = net.shapes[L.inp]
             ho, wo, _ = net.shapes[L.out]
-            ops.append(dict(kind=OP_MAXPOOL, p=[h, w, stored_channels(c), L.k, L.s, L.p, ho, wo],
-                            **{"in": buf_of[L.inp]}, out=buf_of[L.out], et=et,
-                            bpi=[tbytes[L.inp], tbytes[L.out], 0]))
+            ops.append(_op(OP_MAXPOOL, buf_of[L.inp], buf_of[L.out],
+                           bpi=[tbytes[L.inp], tbytes[L.out], 0], layer=i, H=h, W=w,
+                           C=stored_channels(c), k=L.k, s=L.s, pad=L.p, Ho=ho, Wo=wo, et=et))
         elif isinstance(L, AvgPool):
             h, w, c = net.shapes[L.inp]
-            ops.append(dict(kind=OP_AVGPOOL, p=[h * w, stored_channels(c)],
-                            **{"in": buf_of[L.inp]}, out=buf_of[L.out], et=et,
-                            bpi=[tbytes[L.inp], tbytes[L.out], 0]))
+            ops.append(_op(OP_AVGPOOL, buf_of[L.inp], buf_of[L.out],
+                           bpi=[tbytes[L.inp], tbytes[L.out], 0], layer=i, HW=h * w,
+                           C=stored_channels(c), et=et))
         elif isinstance(L, Head):
             h, w, c = net.shapes[L.inp]
-            ops.append(dict(kind=OP_HEAD, p=[h * w, stored_channels(c), L.classes],
-                            **{"in": buf_of[L.inp]}, out=1,
-                            w=base_ptr + layout[f"{L.name}.w"].offset,
-                            bias=base_ptr + layout[f"{L.name}.b"].offset,
-                            et=et, scale=act_scales[L.inp] if fp8 else 1.0,
-                            bpi=[tbytes[L.inp], tbytes["output"], 0]))
+            ops.append(_op(OP_HEAD, buf_of[L.inp], 1, bpi=[tbytes[L.inp], tbytes["output"], 0],
+                           layer=i, HW=h * w, C=stored_channels(c), N=L.classes, et=et,
+                           in_scale=act_scales[L.inp] if fp8 else 1.0,
+                           w=base_ptr + layout[f"{L.name}.w"].offset,
+                           bias=base_ptr + layout[f"{L.name}.b"].offset))
         elif isinstance(L, Softmax):
             h, w, c = net.shapes[L.inp]
-            ops.append(dict(kind=OP_SOFTMAX, p=[L.classes, stored_channels(c)],
-                            **{"in": buf_of[L.inp]}, out=1,
-                            bpi=[tbytes[L.inp], tbytes["output"], 0]))
-        for op in ops:
-            op.setdefault("layer", i)
+            ops.append(_op(OP_SOFTMAX, buf_of[L.inp], 1, bpi=[tbytes[L.inp], tbytes["output"], 0],
+                           layer=i, N=L.classes, ld=stored_channels(c)))
         # release buffers whose tensors die here
         for t, lu in list(last_use.items()):
             if lu == i and t in buf_of and buf_of[t] >= 2:

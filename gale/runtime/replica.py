@@ -33,7 +33,7 @@ class ModelReplica:
         ops, buf_bytes = build_plan(net, packed.data_ptr(), wdtype, self.act_scales, fused=fused,
                                     fold_bn=fold_bn, chunk_layers=cl if ci > 0 else 0,
                                     fuse_blocks=fuse_blocks)
-        co = sum(1 for op in ops if op.get("layer", len(net.layers)) < cl) if ci > 0 else 0
+        co = sum(1 for op in ops if op["layer"] < cl) if ci > 0 else 0
         self.ops = ops
         self.buf_bytes = buf_bytes
         self.executor = native().Executor(packed.device.index or 0, ops, buf_bytes, max_batch,

@@ -133,13 +133,14 @@ def test_stem_pool_matches_layered_stem_and_maxpool():
     g = torch.Generator().manual_seed(3)
     x = torch.rand(B, 224, 224, 3, generator=g).to(DEV)
     s = torch.cuda.current_stream().cuda_stream
-    H, W, Cc, Wp, lp = pk["p"][:5]
+    H, W, Cc, Wp, lp = (pk[k] for k in ("H", "W", "C", "Wp", "lp"))
     xp = torch.empty(B, 224, Wp, 4, device=DEV, dtype=torch.bfloat16)
     C.stem_pack(B, H, W, Cc, Wp, lp, x.data_ptr(), xp.data_ptr(), s)
     s0 = torch.empty(B, 112, 112, 64, device=DEV, dtype=torch.bfloat16)
     C.conv2d(st["conv"], B, xp.data_ptr(), st["w"], st["bias"], 0, 0, s0.data_ptr(), s)
     ref = torch.empty(B, 56, 56, 64, device=DEV, dtype=torch.bfloat16)
-    C.maxpool2d(B, *mp["p"], s0.data_ptr(), ref.data_ptr(), s)
+    C.maxpool2d(B, *(mp[k] for k in ("H", "W", "C", "k", "s", "pad", "Ho", "Wo")), s0.data_ptr(),
+                ref.data_ptr(), s)
     got = torch.full_like(ref, float("nan"))
     C.stem_pool(B, xp.data_ptr(), st["w"], st["bias"], got.data_ptr(), s)
     torch.cuda.synchronize()

@@ -83,12 +83,16 @@ def test_resnet20_plan_is_one_fused_kernel():
     net = get_model("resnet20")
     assert is_cifar_resnet20(net) and not is_cifar_resnet20(get_model("lenet5"))
     ops, buf_bytes = build_plan(net, 1 << 20)
-    assert len(ops) == 1 and ops[0]["kind"] == OP_RESNET20 and len(ops[0]["ptrs"]) == 40
+    assert len(ops) == 1 and ops[0]["kind"] == OP_RESNET20
+    # 40 pointers: 19 weights, 19 biases, the classifier's two; no fp8 weight scale
+    r20 = ops[0]
+    assert len(r20["w"]) == len(r20["b"]) == 19 and all(r20["w"] + r20["b"])
+    assert r20["fc_w"] and r20["fc_b"] and r20["ws"] == [0] * 19 and r20["fp8"] == 0
     assert buf_bytes == [32 * 32 * 3 * 4, 40]
     layered, _ = build_plan(net, 1 << 20, fused=False)
     convs = [op for op in layered if op["kind"] == 0]
-    assert [op["w"] for op in convs] == ops[0]["ptrs"][:19]
-    assert [op["bias"] for op in convs] == ops[0]["ptrs"][19:38]
+    assert [op["w"] for op in convs] == r20["w"]
+    assert [op["bias"] for op in convs] == r20["b"]
 
 
 @pytest.mark.parametrize("name", ["resnet20", "resnet50"])
@@ -107,8 +111,8 @@ def test_unfolded_bn_plan_structure(name):
     for i, L in zip(bn_ops, bn_convs):
         conv, bn = ops[i - 1], ops[i]
         assert conv["kind"] == OP_CONV and conv["conv"]["relu"] == 0 and conv["res"] == -1
-        assert "has_res" not in conv["conv"]
-        assert bn["in"] == bn["out"] == conv["out"] and bn["p"][3] == int(L.relu)
+        assert conv["conv"]["has_res"] == 0
+        assert bn["in"] == bn["out"] == conv["out"] and bn["relu"] == int(L.relu)
         assert (bn["res"] >= 0) == (L.residual is not None) and bn["res"] != bn["out"]
     layout, total = param_layout(net, "bf16", fold_bn=False)
     u = unfolded_params(net, params)
@@ -199,24 +203,29 @@ def test_resnet50_plan_fuses_56x56_bottlenecks(monkeypatch):
     fused, bufs2 = build_plan(net, 1 << 20, fuse_blocks=True)
     assert bufs == bufs2
     bn = [op for op in fused if op["kind"] == OP_BOTTLENECK]
-    assert [op["p"][:2] for op in bn] == [[64, 1], [256, 0], [256, 0]]
+    assert [[op["cin"], op["down"]] for op in bn] == [[64, 1], [256, 0], [256, 0]]
     assert len(fused) == len(layered) - 4 - 3 - 3 + 3 - 1  # (- 1: stem + max-pool fused)
     sp = [op for op in fused if op["kind"] == OP_STEM_POOL]
     assert len(sp) == 1 and fused[1] is sp[0]
     assert sp[0]["in"] == layered[1]["in"] and sp[0]["out"] == layered[2]["out"]
-    assert sp[0]["w"] == layered[1]["w"] and sp[0]["p"] == layered[2]["p"]
+    assert sp[0]["w"] == layered[1]["w"]
+    pool_keys = ("H", "W", "C", "k", "s", "pad", "Ho", "Wo")
+    assert [sp[0][k] for k in pool_keys] == [layered[2][k] for k in pool_keys]
     # block 0 reads the max-pool output and writes what l1.1 reads; each block feeds the next
     assert bn[0]["in"] == layered[2]["out"]  # stem_pack, stem, maxpool -> p0
     assert bn[1]["in"] == bn[0]["out"] and bn[2]["in"] == bn[1]["out"]
     assert all(op["in"] != op["out"] for op in bn)
     nxt = fused[fused.index(bn[2]) + 1]
     assert nxt["kind"] == OP_CONV and nxt["in"] == bn[2]["out"]  # l2.0.down reads l1's output
-    assert len(bn[0]["ptrs"]) == 8 and len(bn[1]["ptrs"]) == 6
+    names = ("w1", "b1", "w2", "b2", "w3", "b3", "wd", "bd")
+    # 8 pointers with the projection, 6 without
+    assert all(bn[0][k] for k in names)
+    assert all(bn[1][k] for k in names[:6]) and bn[1]["wd"] == bn[1]["bd"] == 0
     # pointers are the layered convs' own packed weights / biases
     l1 = [op for op in layered[3:13]]
-    assert bn[0]["ptrs"][:6] == [l1[1]["w"], l1[1]["bias"], l1[2]["w"], l1[2]["bias"],
-                                 l1[3]["w"], l1[3]["bias"]]
-    assert bn[0]["ptrs"][6:] == [l1[0]["w"], l1[0]["bias"]]
+    assert [bn[0][k] for k in names[:6]] == [l1[1]["w"], l1[1]["bias"], l1[2]["w"],
+                                             l1[2]["bias"], l1[3]["w"], l1[3]["bias"]]
+    assert [bn[0]["wd"], bn[0]["bd"]] == [l1[0]["w"], l1[0]["bias"]]
     # other models / dtypes untouched
     r20 = build_plan(get_model("resnet20"), 1 << 20, fused=False, fuse_blocks=True)[0]
     assert not any(op["kind"] == OP_BOTTLENECK for op in r20)
@@ -264,12 +273,12 @@ def test_resnet50_plan_fuses_strided_projections_into_conv3():
         # conv1 reads the block input; neither conv1 nor conv2 overwrites it before conv3
         assert c1["in"] == op["res"] and op["res"] not in (c1["out"], c2["out"])
         assert op["in"] == c2["out"] and op["out"] != op["res"]
-        H2, W2, Cin2, s2, Kpad2 = op["p"]
+        H2, Cin2, s2, Kpad2 = op["H2"], op["Cin2"], op["stride2"], op["Kpad2"]
         d = op["conv"]
         assert s2 == 2 and (H2 - 1) // 2 + 1 == d["Ho"] and Kpad2 == Cin2
         assert d["KH"] == 1 and d["stride"] == 1 and not d.get("has_res")
         assert op["bpi"][2] == c1["bpi"][0]
-        assert len(op["ptrs"]) == 4
+        assert all(k in op for k in ("w", "bias", "wd", "bd", "W2"))
     # no other op reads a projection's (now unwritten) output buffer
     written = {o["out"] for o in ops}
     for o in ops:

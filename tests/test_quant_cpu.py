@@ -92,9 +92,12 @@ def test_fp8_fused_resnet20_plan_carries_scales():
     sc = act_scales_from_packed(net, pack_params(net, f, "fp8"))
     ops, _ = build_plan(net, 4096, "fp8", sc)
     assert len(ops) == 1 and ops[0]["kind"] == OP_RESNET20 and ops[0]["fp8"] == 1
-    assert len(ops[0]["ptrs"]) == 59 and len(ops[0]["scales"]) == 57
+    # 59 pointers (19 weights, 19 biases, the classifier's two, 19 weight scales), 57 scales
+    pointers = ops[0]["w"] + ops[0]["b"] + [ops[0]["fc_w"], ops[0]["fc_b"]] + ops[0]["ws"]
+    assert [len(ops[0][k]) for k in ("w", "b", "ws")] == [19, 19, 19] and all(pointers)
     convs = [L for L in net.layers if isinstance(L, Conv)]
-    s_in, s_out, s_res = (ops[0]["scales"][i * 19:(i + 1) * 19] for i in range(3))
+    s_in, s_out, s_res = (ops[0][k] for k in ("s_in", "s_out", "s_res"))
+    assert len(s_in) == len(s_out) == len(s_res) == 19
     assert s_in[0] == pytest.approx(sc["input"])
     for i, L in enumerate(convs):
         assert s_in[i] == pytest.approx(sc[L.inp]) and s_out[i] == pytest.approx(sc[L.out])

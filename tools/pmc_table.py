@@ -46,7 +46,7 @@ def layer_labels(model: str, batch: int):
             out.append((f"{L.name} {d['KH']}x{d['KW']}/{d['stride']} {d['Cin']}->{d['Cout']} "
                         f"@{d['Ho']}x{d['Wo']}", fl, by))
         elif op["kind"] == 9:  # OP_BOTTLENECK: a whole 56x56 block (bottleneck_fused.hip)
-            cin, down = op["p"][0], op["p"][1]
+            cin, down = op["cin"], op["down"]
             blk = net.layers[op["layer"]].name.rsplit(".", 1)[0]
             m = batch * 56 * 56
             fl = 2.0 * m * (cin * 64 + 576 * 64 + 64 * 256 + (64 * 256 if down else 0))
@@ -60,11 +60,11 @@ def layer_labels(model: str, batch: int):
             out.append(("stem 7x7/2 + maxpool 3x3/2 (fused) @56x56", fl, by))
         elif op["kind"] == 11:  # OP_CONV_PROJ: conv3 + strided projection (conv2d_gemm_proj)
             d = op["conv"]
-            H2, W2, Cin2 = op["p"][:3]
+            Cin2 = op["Cin2"]
             m = batch * d["Ho"] * d["Wo"]
             fl = 2.0 * m * d["Cout"] * (d["K"] + Cin2)
             by = 2.0 * (batch * d["H"] * d["W"] * d["Cin"] + m * Cin2 + m * d["Cout"])
-            by += d["Npad"] * (d["Kpad"] + op["p"][4]) * 2
+            by += d["Npad"] * (d["Kpad"] + op["Kpad2"]) * 2
             blk = net.layers[op["layer"]].name.rsplit(".", 1)[0]
             out.append((f"{blk} conv3 1x1 {d['Cin']}->{d['Cout']} + proj 1x1/2 {Cin2} @"
                         f"{d['Ho']}x{d['Wo']}", fl, by))
