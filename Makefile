@@ -21,6 +21,7 @@ CXX_SRC   := $(wildcard csrc/runtime/*.cpp) $(wildcard csrc/codec/*.cpp) \
 HIP_OBJ   := $(patsubst csrc/%.hip,$(OBJ)/%.o,$(HIP_SRC))
 CXX_OBJ   := $(patsubst csrc/%.cpp,$(OBJ)/%.o,$(CXX_SRC))
 HDRS      := $(wildcard csrc/include/gale/*.h) $(wildcard csrc/kernels/*.cuh) \
+             $(wildcard csrc/kernels/*.h) \
              $(wildcard csrc/runtime/*.h) $(wildcard csrc/codec/*.h) $(wildcard csrc/kafka/*.h) \
              $(wildcard csrc/comm/*.h) $(wildcard csrc/bindings/*.h)
 
@@ -137,14 +138,23 @@ build/asan/batch_plan_check: csrc/tests/batch_plan_check.cpp csrc/runtime/batch_
 	    csrc/tests/batch_plan_check.cpp csrc/runtime/batch_plan.cpp -o $@
 
 # the forward plan's validation on randomly corrupted plans of every op kind
-# (csrc/tests/forward_plan_check.cpp): the plan alone, no executor, no HIP call
+# (csrc/tests/forward_plan_check.cpp): the plan and the conv route, no executor, no HIP call
 build/asan/forward_plan_check: csrc/tests/forward_plan_check.cpp csrc/runtime/forward_plan.cpp \
-                               $(HDRS)
+                               csrc/runtime/conv_route.cpp $(HDRS)
 	@mkdir -p $(dir $@)
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 \
 	    -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include -Icsrc/include \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    csrc/tests/forward_plan_check.cpp csrc/runtime/forward_plan.cpp -o $@
+	    csrc/tests/forward_plan_check.cpp csrc/runtime/forward_plan.cpp \
+	    csrc/runtime/conv_route.cpp -o $@
+
+# the conv route on random and extreme descs (csrc/tests/conv_route_check.cpp): every count a
+# launcher passes as a 32-bit value recomputed in 64 bits; the route alone, no HIP header or call
+build/asan/conv_route_check: csrc/tests/conv_route_check.cpp csrc/runtime/conv_route.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -Icsrc/include \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/conv_route_check.cpp csrc/runtime/conv_route.cpp -o $@
 
 # the two top-k encoders (host selection by the score order rule, slot concatenation) over
 # generated rows (csrc/tests/topk_encode_check.cpp): codec only, no engine

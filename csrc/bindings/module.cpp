@@ -533,8 +533,7 @@ PYBIND11_MODULE(_C, m) {
     return gale::conv_patch_supported(desc_from_dict(desc), batch, has_res);
   });
   // the launch of the MFMA conv kernel for this layer and batch (host only, no HIP call)
-  m.def("conv_mfma_plan", [](py::dict desc, int batch, bool has_res) {
-    const gale::ConvMfmaPlan p = gale::conv_mfma_plan(desc_from_dict(desc), batch, has_res);
+  auto mfma_dict = [](const gale::ConvMfmaPlan& p) {
     static const char* const kModes[] = {"fast", "gather", "1x1"};
     py::dict r;
     r["ok"] = p.ok;
@@ -547,6 +546,44 @@ PYBIND11_MODULE(_C, m) {
     r["m_tiles"] = p.m_tiles;
     r["grid_m"] = p.grid_m;
     r["lds_bytes"] = p.lds_bytes;
+    return r;
+  };
+  m.def("conv_mfma_plan", [mfma_dict](py::dict desc, int batch, bool has_res) {
+    return mfma_dict(gale::conv_mfma_plan(desc_from_dict(desc), batch, has_res));
+  }, py::arg("desc"), py::arg("batch"), py::arg("has_res"));
+  // the launch conv2d() makes for this layer and batch under the process policy: "kernel"
+  // ("none" / "f32" / "gemm" / "patch" / "mfma"), "refusal" (None unless "none") and the chosen
+  // kernel's plan fields (host only, no HIP call)
+  m.def("conv_route", [mfma_dict](py::dict desc, int batch, bool has_res) {
+    const gale::ConvRoute t = gale::conv_route(desc_from_dict(desc), batch, has_res);
+    py::dict r;
+    switch (t.kernel) {
+      case gale::CONV_F32:
+        r["M"] = t.f32.M, r["grid_m"] = t.f32.grid_m, r["grid_n"] = t.f32.grid_n;
+        break;
+      case gale::CONV_GEMM: {
+        const gale::ConvGemmPlan& p = t.gemm;
+        r["bn"] = p.bn, r["stages"] = p.stages, r["stem"] = p.stem, r["M"] = p.M;
+        r["m_tiles"] = p.m_tiles, r["n_tiles"] = p.n_tiles, r["nwg"] = p.nwg;
+        r["nkb"] = p.nkb, r["cin_blocks"] = p.cin_blocks;
+        break;
+      }
+      case gale::CONV_PATCH: {
+        const gale::ConvPatchPlan& p = t.patch;
+        r["bn"] = p.bn, r["prr"] = p.prr, r["TR"] = p.TR, r["IMG"] = p.IMG, r["P"] = p.P;
+        r["PW"] = p.PW, r["PR1"] = p.PR1, r["PR"] = p.PR, r["rblocks"] = p.rblocks;
+        r["nsteps"] = p.nsteps, r["batch"] = p.batch, r["n_tiles"] = p.n_tiles;
+        r["nwg"] = p.nwg;
+        break;
+      }
+      case gale::CONV_MFMA:
+        r = mfma_dict(t.mfma);
+        r["M"] = t.mfma.M, r["cin_shift"] = t.mfma.cin_shift, r["kw_magic"] = t.mfma.kw_magic;
+        break;
+      default: break;
+    }
+    r["kernel"] = gale::conv_kernel_name(t.kernel);
+    r["refusal"] = t.refusal ? py::object(py::str(t.refusal)) : py::object(py::none());
     return r;
   }, py::arg("desc"), py::arg("batch"), py::arg("has_res"));
   m.def("device_pci_bus_id", [](int device) {

@@ -111,7 +111,10 @@ struct PlanSpec {
 // Throws std::invalid_argument ("plan op <index> (<kind>): <field> ...") unless every op can be
 // launched as it stands: in / out / res inside buf_bytes_per_image (a conv_proj has a res), every
 // pointer its kind needs non-null, et an ElemType, bpi within its buffer; and max_batch / slots /
-// chunk_ops / chunk_images sane, every chunked op with the bpi of its operands.
+// chunk_ops / chunk_images sane, every chunked op with the bpi of its operands. Every conv is
+// routed (gale/conv_route.h) at the largest batch the executor launches it with - chunk_images for
+// a chunked op, else max_batch - and refused with the route's refusal when no kernel takes it;
+// a conv_proj, a bottleneck and a stem_pool must have the geometry their kernel is compiled for.
 void validate_plan(const PlanSpec& spec);
 
 }  // namespace gale

@@ -12,131 +12,39 @@
 
 #include "../../codec/pixfmt.h"  // PackedFormat (no HIP: shared with the host codec)
 #include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
+#include "gale/conv_route.h"  // ConvDesc, the conv launch plans, BottleneckParams (no HIP)
 
 namespace gale {
 
-// Geometry of one convolution (or fully connected layer expressed as a 1x1 convolution over a
-// 1x1 image). Independent of the batch size, which is a launch argument so one descriptor serves
-// every hipGraph batch bucket.
-struct ConvDesc {
-  int H, W, Cin;        // input spatial size and channel count (channel stride of the input)
-  int Ho, Wo, Cout;     // output spatial size; Cout = stored output channels (channel stride of y)
-  int KH, KW, stride, pad;
-  int K;                // true reduction length KH*KW*Cin
-  int Kpad;             // K rounded up to 32 (row stride of the packed weights)
-  int Npad;             // rows of the packed weight matrix (multiple of the n-block)
-  int relu;             // apply ReLU in the epilogue
-  // residual added before the ReLU (ResNet shortcut). res_C < Cout zero-pads the extra channels
-  // and res_stride > 1 subsamples: together they are the parameter-free "option A" shortcut.
-  int has_res, res_H, res_W, res_C, res_stride;
-  int in_f32;           // input tensor is fp32 (network input; converted to bf16 while staging)
-  int out_f32;          // output tensor is fp32 (classifier logits)
-  int fp8;              // OCP e4m3 operands (fp8 MFMA path): weights per-channel (wscale),
-                        // activations per tensor (value = code * scale)
-  float in_scale;       // fp8: input scale (in_f32: the input is quantised with this step)
-  float out_scale;      // fp8: output scale (ignored for out_f32)
-  float res_scale;      // fp8: residual scale
-  // 1 = packed-stem layout (ResNet-50 7x7/2 stem, bf16): x is the stem_pack() image
-  // [B][H][W][4] bf16 with W = 2*Wo + 6 (3 zero columns left, the rest right), the packed weights
-  // are [Npad][256] with k = kh*32 + kw*4 + c over an 8x8x4 zero-padded kernel (KH = KW = 8,
-  // K = Kpad = 256), so each kernel row of one output pixel is ONE 64-byte run of x.
-  int stem;
-  // 1 = reference-precision plan (--dtype fp32): x, w, residual and y are all fp32 and the conv
-  // runs on the fp32 matrix core (conv_f32.hip, v_mfma_f32_16x16x4_f32); Kpad % 16 == 0
-  int f32;
-};
-
-// y[B,Ho,Wo,Cout] = act(conv(x, w) + bias (+ residual)).
+// y[B,Ho,Wo,Cout] = act(conv(x, w) + bias (+ residual)), by the kernel conv_route() picks for
+// the launch (gale/conv_route.h; hipErrorInvalidValue where it picks none).
 // w: [Npad][Kpad] (bf16 or e4m3), k = (kh*KW + kw)*Cin + ci, zero padded.
 // bias: [Npad] fp32 (BatchNorm already folded in). wscale: [Npad] fp32 per-output-channel weight
 // dequant scale (fp8 path only; nullptr otherwise). In the fp8 path x / res / y are e4m3 tensors
 // (x fp32 when in_f32, y fp32 when out_f32).
 hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, const float* bias,
                   const float* wscale, const void* res, void* y, hipStream_t stream);
-hipError_t conv2d_f32(const ConvDesc& d, int batch, const void* x, const void* w,
-                      const float* bias, const void* res, void* y, hipStream_t stream);
-
-// Everything conv2d() decides for a launch of the MFMA kernel (conv_mfma.hip), i.e. once the
-// fp32 / packed-stem / patch / GEMM branches have passed: the template instantiation (mode, nt,
-// pr) and the grid depend on the batch, not only on the layer. Host only, no HIP call; conv2d()
-// launches from this struct and from nothing else. has_res: the launch reads a residual
-// (d.has_res and a non-null pointer).
-// ok == false (conv2d() returns hipErrorInvalidValue): Cout % 4, Kpad % 32, Npad % (16 nt),
-// out_f32 outside 1x1 mode, a K chunk below 32, or a launch the kernel's 32-bit offsets cannot
-// index: batch*Ho*Wo (rounded up to whole pixel tiles), batch*H*W*Cin or, with a residual,
-// batch*res_H*res_W*res_C at 2^31 or more.
-enum ConvMfmaMode : int { CONV_MFMA_FAST = 0, CONV_MFMA_GATHER = 1, CONV_MFMA_1X1 = 2 };
-struct ConvMfmaPlan {
-  bool ok = false;
-  int mode = CONV_MFMA_FAST;  // ConvMfmaMode
-  int nt = 0;                 // channel tiles (16 channels each) per workgroup n-block
-  int pr = 0;                 // pixel tiles (16 pixels each) per wave: the tile is 64 pr pixels
-  int n_blocks = 0;           // grid.y
-  int bk = 0;                 // K chunk staged in LDS
-  int nkc = 0;                // K chunks; 1 = the weights stay resident and tiles are walked
-  int m_tiles = 0;            // pixel tiles of the launch
-  int grid_m = 0;             // grid.x; < m_tiles: workgroups walk the tiles grid-stride
-  size_t lds_bytes = 0;
-};
-ConvMfmaPlan conv_mfma_plan(const ConvDesc& d, int batch, bool has_res);
 
 // Activation element types of the pooling / head kernels (their `et` argument; 1 was the old
 // fp8 flag, so fp8 callers are unchanged)
 enum ElemType : int { ET_BF16 = 0, ET_FP8 = 1, ET_F32 = 2 };
 
-// The LDS-pipelined implicit-GEMM path (conv_gemm.hip) for wide bf16 layers; conv2d() routes
-// there by itself when conv_gemm_supported() holds.
-bool conv_gemm_supported(const ConvDesc& d, int batch, bool has_res);
-// conv path selection (tests / A-B benches): 0 auto, 1 never GEMM, 2 GEMM whenever the shape allows
-void set_conv_path(int mode);
-int conv_path();
 // conv3 of a ResNet bottleneck with its projection shortcut as ONE GEMM over the concatenated
-// reduction: y = act(conv1x1(x, w) + bias + conv1x1_stride2(x2, w2) + bias2). d: the 1x1
-// stride-1 conv on x (no residual); x2 [B][H2][W2][Cin2] bf16 sampled at stride2 onto d's output
-// grid, w2 [Npad][Kpad2]. The projection's output tensor never exists.
-bool conv_gemm_proj_supported(const ConvDesc& d, int batch, int H2, int W2, int Cin2,
-                              int stride2, int Kpad2);
+// reduction (conv_gemm.hip): y = act(conv1x1(x, w) + bias + conv1x1_stride2(x2, w2) + bias2),
+// launched from conv_gemm_proj_plan() (gale/conv_route.h). The projection's output tensor never
+// exists.
 hipError_t conv2d_gemm_proj(const ConvDesc& d, int batch, const void* x, const void* w,
                             const float* bias, const void* x2, int H2, int W2, int Cin2,
                             int stride2, int Kpad2, const void* w2, const float* bias2, void* y,
                             hipStream_t stream);
-hipError_t conv2d_gemm(const ConvDesc& d, int batch, const void* x, const void* w,
-                       const float* bias, const void* res, void* y, hipStream_t stream);
 
-// 3x3 stride-1 convs with an LDS-resident input patch per 64-channel block (conv_patch.hip):
-// bf16, Cin % 64 == 0, tiles of whole output rows (<= 128 pixels, >= 96). conv2d() routes there
-// first when conv_patch_supported() holds. set_conv_patch / GALE_CONV_PATCH: 0 off, 1 (default)
-// 128-channel tiles only, 2 also 64-channel tiles.
-bool conv_patch_supported(const ConvDesc& d, int batch, bool has_res);
-void set_conv_patch(int mode);
-hipError_t conv2d_patch(const ConvDesc& d, int batch, const void* x, const void* w,
-                        const float* bias, const void* res, void* y, hipStream_t stream);
-
-// One whole ResNet-50 56x56 bottleneck per launch (bottleneck_fused.hip), bf16 NHWC:
-// y = relu(conv3(relu(conv2(relu(conv1(x))))) + shortcut), shortcut = x (cin 256) or, with
-// down = 1 (block 0, cin 64), the 1x1 projection bf16(wd . x + bd). Packed weights as conv2d's:
-// w1 [64][cin], w2 [64][576], w3 / wd [256][64]; biases fp32 with BatchNorm folded in.
-struct BottleneckParams {
-  const void* w1 = nullptr;
-  const void* w2 = nullptr;
-  const void* w3 = nullptr;
-  const void* wd = nullptr;
-  const float* b1 = nullptr;
-  const float* b2 = nullptr;
-  const float* b3 = nullptr;
-  const float* bd = nullptr;
-  int cin = 256;
-  int down = 0;
-};
-bool bottleneck56_supported(int H, int W, int cin, int cmid, int cout, int down);
+// One whole ResNet-50 56x56 bottleneck per launch (BottleneckParams, gale/conv_route.h).
 hipError_t bottleneck56(const BottleneckParams& p, int batch, const void* x, void* y,
                         hipStream_t stream);
 
 // ResNet-50 ImageNet stem conv (packed-stem ConvDesc, ReLU) + 3x3/2 max-pool in one launch
-// (stem_pool.hip): x = stem_pack() image bf16 [B][224][230][4], w [64][256], y bf16
-// [B][56][56][64]. stem_pool_supported: the conv desc + the maxpool op's geometry.
-bool stem_pool_supported(const ConvDesc& d, int H, int W, int C, int k, int s, int p, int Ho,
-                         int Wo);
+// (stem_pool.hip; stem_pool_supported, gale/conv_route.h): x = stem_pack() image bf16
+// [B][224][230][4], w [64][256], y bf16 [B][56][56][64].
 hipError_t stem_pool(int batch, const void* x, const void* w, const float* bias, void* y,
                      hipStream_t stream);
 

@@ -52,6 +52,8 @@ constexpr int kLdsBytes = kH1Bytes + kW2Bytes;   // 147,968
 constexpr int kT1 = kR1 * kW / 16;               // 35 phase-1 pixel tiles
 constexpr int kStrips = kH / kTR;                // 7
 static_assert(kR1 * kW % 16 == 0 && kTR * kW % (16 * 4) == 0, "tile geometry");
+static_assert(kH == kBneckH && kW == kBneckW && kCM == kBneckMid && kCO == kBneckOut,
+              "bottleneck56_supported (gale/conv_route.h) admits the compiled geometry");
 static_assert(kCO * 128 <= kW2Bytes, "W3 must fit the W2 region");
 static_assert(kCO * 128 + 8 * 4096 <= kW2Bytes, "two-tile output stages must fit past W3");
 
@@ -407,16 +409,11 @@ __global__ __launch_bounds__(512, 1) void bottleneck56_kernel(BneckArgs a) {
 
 }  // namespace
 
-bool bottleneck56_supported(int H, int W, int cin, int cmid, int cout, int down) {
-  return H == kH && W == kW && cmid == kCM && cout == kCO &&
-         ((down && cin == 64) || (!down && cin == kCO));
-}
-
 hipError_t bottleneck56(const BottleneckParams& p, int batch, const void* x, void* y,
                         hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
   if (!p.w1 || !p.w2 || !p.w3 || !p.b1 || !p.b2 || !p.b3 || !x || !y) return hipErrorInvalidValue;
-  if (p.down && (!p.wd || !p.bd || p.cin != 64)) return hipErrorInvalidValue;
+  if (p.down && (!p.wd || !p.bd || p.cin != kBneckDownIn)) return hipErrorInvalidValue;
   if (!p.down && p.cin != kCO) return hipErrorInvalidValue;
   // the kernel's element offsets are 32-bit: launch chunks of <= 2048 images (any max_batch)
   constexpr int kChunk = 2048;

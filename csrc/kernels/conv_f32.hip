@@ -14,7 +14,7 @@
 // [64][16+1] and the im2col tile as [16][64+16]: both padded so the fragment reads of a
 // half-wave hit 32 distinct banks); each chunk is 4 k-steps of 4.
 #include "common.cuh"
-#include "gale/kernels.h"
+#include "conv_launch.h"
 
 namespace gale {
 namespace {
@@ -24,6 +24,7 @@ constexpr int kTN = 64;            // channels per workgroup
 constexpr int kKC = 16;            // K chunk
 constexpr int kAS = kKC + 1;       // LDS row stride of the weight tile (floats)
 constexpr int kBS = kTM + 16;      // LDS row stride of the im2col tile (floats)
+static_assert(kTM == kConvF32Tile && kTN == kConvF32Tile, "ConvF32Plan's grid (gale/conv_route.h)");
 
 struct F32Args {
   const float* x;
@@ -131,28 +132,22 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(F32Args a) {
 
 }  // namespace
 
-hipError_t conv2d_f32(const ConvDesc& d, int batch, const void* x, const void* w,
-                      const float* bias, const void* res, void* y, hipStream_t stream) {
-  if (batch <= 0) return hipSuccess;
-  if (d.Kpad % kKC || d.Cout % 4 || d.K > d.Kpad || d.Npad < d.Cout || d.fp8 || d.stem)
-    return hipErrorInvalidValue;
-  if (d.has_res && res && (d.res_stride < 1 || d.res_C > d.Cout || d.res_C % 4))
-    return hipErrorInvalidValue;
+hipError_t launch_conv_f32(const ConvDesc& d, const ConvF32Plan& p, const void* x, const void* w,
+                           const float* bias, const void* res, void* y, hipStream_t stream) {
   F32Args a;
   a.x = static_cast<const float*>(x);
   a.w = static_cast<const float*>(w);
   a.bias = bias;
   a.res = static_cast<const float*>(res);
   a.y = static_cast<float*>(y);
-  a.M = batch * d.Ho * d.Wo;
+  a.M = p.M;
   a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.Ho = d.Ho; a.Wo = d.Wo; a.HWo = d.Ho * d.Wo;
   a.Cout = d.Cout; a.KW = d.KW; a.stride = d.stride; a.pad = d.pad; a.K = d.K; a.Kpad = d.Kpad;
   a.Npad = d.Npad;
   a.relu = d.relu;
-  a.has_res = d.has_res && res != nullptr;
+  a.has_res = res != nullptr;
   a.res_H = d.res_H; a.res_W = d.res_W; a.res_C = d.res_C; a.res_stride = d.res_stride;
-  const dim3 grid((a.M + kTM - 1) / kTM, (d.Cout + kTN - 1) / kTN);
-  hipLaunchKernelGGL(conv_f32_kernel, grid, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(conv_f32_kernel, dim3(p.grid_m, p.grid_n), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

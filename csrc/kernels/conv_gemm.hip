@@ -20,12 +20,10 @@
 // residual loads and output stores are 16-byte, whole-row accesses.
 // Grid: one workgroup per (pixel tile, channel tile), remapped so the tiles of one XCD are
 // contiguous (T1): the channel tiles of a pixel tile, which re-read the same im2col rows, share an L2.
-#include <stdlib.h>
-
-#include <atomic>
+#include <algorithm>
 
 #include "common.cuh"
-#include "gale/kernels.h"
+#include "conv_launch.h"
 
 namespace gale {
 namespace {
@@ -343,29 +341,11 @@ void conv_gemm_kernel(GemmConvArgs a) {
 
 }  // namespace
 
-// 0 auto, 1 never the GEMM path, 2 GEMM path whenever the shape allows (tests / A-B benches)
-static std::atomic<int> g_conv_path{0};
-void set_conv_path(int mode) { g_conv_path = mode; }
-int conv_path() { return g_conv_path; }
+typedef void (*GemmKernelFn)(GemmConvArgs);
 
-bool conv_gemm_supported(const ConvDesc& d, int batch, bool has_res) {
-  if (g_conv_path == 1) return false;
-  if (d.fp8 || d.in_f32 || d.f32) return false;
-  if (d.Cin % 64 != 0 || d.Cout % 8 != 0 || d.K != d.KH * d.KW * d.Cin || d.Kpad != d.K)
-    return false;
-  // channel tiles cover Npad (zero weight rows past Cout; the epilogue stores c < Cout only)
-  const int bn = (d.Npad % 128 == 0) ? 128 : 64;
-  if (d.Npad % bn != 0 || d.Npad < d.Cout) return false;
-  if (has_res && (d.res_C != d.Cout || d.res_stride != 1 || d.res_H != d.Ho || d.res_W != d.Wo))
-    return false;
-  // 32-bit element offsets inside the kernel. (No minimum size: measured faster than conv_mfma
-  // from ResNet-50 batch 64 up, including the 98-tile stage-4 layers, profiles/archive/r1_resnet50_*.)
-  const long long m = (long long)batch * d.Ho * d.Wo;
-  return m < (1ll << 31) && (long long)batch * d.H * d.W * d.Cin < (1ll << 31);
-}
-
-hipError_t conv2d_gemm(const ConvDesc& d, int batch, const void* x, const void* w,
-                       const float* bias, const void* res, void* y, hipStream_t stream) {
+hipError_t launch_conv_gemm(const ConvDesc& d, const ConvGemmPlan& p, const void* x,
+                            const void* w, const float* bias, const void* res, void* y,
+                            hipStream_t stream) {
   GemmConvArgs a;
   a.x = static_cast<const bf16*>(x);
   a.w = static_cast<const bf16*>(w);
@@ -373,123 +353,65 @@ hipError_t conv2d_gemm(const ConvDesc& d, int batch, const void* x, const void* 
   a.res = static_cast<const bf16*>(res);
   a.y = y;
   a.out_f32 = d.out_f32;
-  a.M = batch * d.Ho * d.Wo;
+  a.M = p.M;
   a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.HWo = d.Ho * d.Wo; a.Wo = d.Wo; a.Cout = d.Cout;
   a.KW = d.KW; a.stride = d.stride; a.pad = d.pad; a.Kpad = d.Kpad;
-  a.nkb = d.K / 64;
-  a.cin_blocks = d.stem ? 1 : d.Cin / 64;
+  a.nkb = p.nkb;
+  a.cin_blocks = p.cin_blocks;
   a.relu = d.relu;
-  a.has_res = d.has_res && res != nullptr;
+  a.has_res = res != nullptr;
   a.x2 = nullptr; a.w2 = nullptr; a.bias2 = nullptr;
   a.H2 = a.W2 = a.Cin2 = a.stride2 = a.Kpad2 = 0;
   a.nkb1 = a.nkb;
-  // 64-channel tiles for the single-k-step (K = 64) 1x1 convs: these are bound by their
-  // epilogue traffic, and half-width tiles (24 KB of LDS, 91 VGPRs) put 5 workgroups on a CU
-  // instead of 4 (ResNet-50 batch 256: 4.87 -> 4.81 ms; at K = 128 / 256 / 512 the same change
-  // costs 0.6 / 1.6 / 2.6 %, profiles/r4_resnet50_layers.txt)
-  // (the single-stage form for the K = 128 1x1 convs, with 64- or 128-channel tiles, measured
-  // 0.4 / 2.2 % slower in round 4; for the 64-channel K = 256 ones, within noise)
-  const int bn = (d.Npad % 128 == 0 && !(d.K == 64 && d.KH == 1 && !d.stem)) ? 128 : 64;
+  a.n_tiles = p.n_tiles;
+  a.nwg = p.nwg;
   constexpr int BM = 128;
-  const int m_tiles = (a.M + BM - 1) / BM;
-  a.n_tiles = d.Npad / bn;
-  a.nwg = m_tiles * a.n_tiles;
-  // per-shape choice: the packed stem; K = 64 (one k-step: 1x1 convs on 64 channels) in the
-  // single-stage form with 64-channel tiles, 5 workgroups per CU; everything else
-  // double-buffered, 128-channel tiles when Npad allows, else 64
-  const bool one = a.nkb == 1;
-  if (d.stem) {
-    if (bn == 128)
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 128, true, 2>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-    else
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 64, true, 2>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-  } else if (bn == 128) {
-    if (one)
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 128, false, 1>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-    else
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 128, false, 2>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-  } else {
-    if (one)
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 64, false, 1>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-    else
-      hipLaunchKernelGGL((conv_gemm_kernel<BM, 64, false, 2>), dim3(a.nwg), dim3(256), 0, stream,
-                         a);
-  }
+  const bool wide = p.bn == 128;
+  GemmKernelFn fn;
+  if (p.stem) fn = wide ? conv_gemm_kernel<BM, 128, true, 2> : conv_gemm_kernel<BM, 64, true, 2>;
+  else if (wide)
+    fn = p.stages == 1 ? conv_gemm_kernel<BM, 128, false, 1> : conv_gemm_kernel<BM, 128, false, 2>;
+  else fn = p.stages == 1 ? conv_gemm_kernel<BM, 64, false, 1> : conv_gemm_kernel<BM, 64, false, 2>;
+  hipLaunchKernelGGL(fn, dim3(p.nwg), dim3(256), 0, stream, a);
   return hipGetLastError();
-}
-
-// images per launch of the fused projection: every element offset of the launch's x, x2 and y
-// (and its pixel count) must stay below 2^31 (max_batch >= ~2675 overflowed the
-// stage-2 projection's input)
-static int proj_chunk_images(const ConvDesc& d, int H2, int W2, int Cin2) {
-  const long long lim = (1ll << 31) - 1;
-  long long per = (long long)d.Ho * d.Wo * std::max(d.Cout, 1);
-  per = std::max(per, (long long)d.H * d.W * d.Cin);
-  per = std::max(per, (long long)H2 * W2 * Cin2);
-  return per > 0 ? (int)std::min<long long>(lim / per, 1 << 20) : 0;
-}
-
-bool conv_gemm_proj_supported(const ConvDesc& d, int batch, int H2, int W2, int Cin2,
-                              int stride2, int Kpad2) {
-  // (no conv_path switch: like the fused block kernels this op has no other implementation)
-  if (d.fp8 || d.in_f32 || d.f32 || d.out_f32 || d.stem || d.has_res) return false;
-  if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad != 0) return false;
-  if (d.Cin % 64 != 0 || d.K != d.Cin || d.Kpad != d.K || d.Ho != d.H || d.Wo != d.W) return false;
-  if (Cin2 % 64 != 0 || Kpad2 != Cin2 || stride2 < 1) return false;
-  if ((H2 - 1) / stride2 + 1 != d.Ho || (W2 - 1) / stride2 + 1 != d.Wo) return false;
-  if (d.Npad % 128 != 0 || d.Npad < d.Cout || d.Cout % 8 != 0) return false;
-  // (any batch: conv2d_gemm_proj launches chunks whose 32-bit element offsets hold)
-  return batch >= 0 && proj_chunk_images(d, H2, W2, Cin2) > 0;
 }
 
 hipError_t conv2d_gemm_proj(const ConvDesc& d, int batch, const void* x, const void* w,
                             const float* bias, const void* x2, int H2, int W2, int Cin2,
                             int stride2, int Kpad2, const void* w2, const float* bias2, void* y,
                             hipStream_t stream) {
-  if (!conv_gemm_proj_supported(d, batch, H2, W2, Cin2, stride2, Kpad2))
-    return hipErrorInvalidValue;
-  const int chunk = proj_chunk_images(d, H2, W2, Cin2);
-  if (batch > chunk) {  // chunks of images, each with 32-bit offsets (bf16 in and out)
-    for (int c0 = 0; c0 < batch; c0 += chunk) {
-      const int nb = std::min(chunk, batch - c0);
-      const hipError_t e = conv2d_gemm_proj(
-          d, nb, static_cast<const bf16*>(x) + (size_t)c0 * d.H * d.W * d.Cin, w, bias,
-          static_cast<const bf16*>(x2) + (size_t)c0 * H2 * W2 * Cin2, H2, W2, Cin2, stride2,
-          Kpad2, w2, bias2, static_cast<bf16*>(y) + (size_t)c0 * d.Ho * d.Wo * d.Cout, stream);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
+  const ConvProjPlan p = conv_gemm_proj_plan(d, batch, H2, W2, Cin2, stride2, Kpad2);
+  if (!p.ok) return hipErrorInvalidValue;
   GemmConvArgs a;
-  a.x = static_cast<const bf16*>(x);
   a.w = static_cast<const bf16*>(w);
   a.bias = bias;
   a.res = nullptr;
-  a.y = y;
   a.out_f32 = 0;
-  a.M = batch * d.Ho * d.Wo;
   a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.HWo = d.Ho * d.Wo; a.Wo = d.Wo; a.Cout = d.Cout;
   a.KW = 1; a.stride = 1; a.pad = 0; a.Kpad = d.Kpad;
-  a.cin_blocks = d.Cin / 64;
-  a.nkb1 = d.Cin / 64;
-  a.nkb = a.nkb1 + Cin2 / 64;
+  a.cin_blocks = p.nkb1;
+  a.nkb1 = p.nkb1;
+  a.nkb = p.nkb;
   a.relu = d.relu;
   a.has_res = 0;
-  a.x2 = static_cast<const bf16*>(x2);
   a.w2 = static_cast<const bf16*>(w2);
   a.bias2 = bias2;
   a.H2 = H2; a.W2 = W2; a.Cin2 = Cin2; a.stride2 = stride2; a.Kpad2 = Kpad2;
-  constexpr int BM = 128;
-  a.n_tiles = d.Npad / 128;
-  a.nwg = (a.M + BM - 1) / BM * a.n_tiles;
-  hipLaunchKernelGGL((conv_gemm_kernel<BM, 128, false, 2, true>), dim3(a.nwg), dim3(256), 0,
-                     stream, a);
-  return hipGetLastError();
+  a.n_tiles = p.n_tiles;
+  // chunks of images, each with 32-bit offsets (bf16 in and out)
+  for (int c0 = 0; c0 < batch; c0 += p.chunk_images) {
+    const int nb = std::min(p.chunk_images, batch - c0);
+    a.x = static_cast<const bf16*>(x) + (size_t)c0 * d.H * d.W * d.Cin;
+    a.x2 = static_cast<const bf16*>(x2) + (size_t)c0 * H2 * W2 * Cin2;
+    a.y = static_cast<bf16*>(y) + (size_t)c0 * d.Ho * d.Wo * d.Cout;
+    a.M = nb * a.HWo;
+    a.nwg = (a.M + 127) / 128 * a.n_tiles;
+    hipLaunchKernelGGL((conv_gemm_kernel<128, 128, false, 2, true>), dim3(a.nwg), dim3(256), 0,
+                       stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 namespace {

@@ -28,19 +28,19 @@
 // activation byte moved; the network input stays fp32 and is quantised while it is loaded.
 //
 // Launch plan: which instantiation (mode, NT, PR) and which grid a launch gets depends on its
-// batch; conv_mfma_plan() below decides all of it on the host and conv2d() launches from its
-// result alone. The pixel index m and the input / residual element offsets (pbase, roff) are
-// 32-bit ints, so the plan refuses a launch whose batch*Ho*Wo (in whole tiles), batch*H*W*Cin or
-// batch*res_H*res_W*res_C reaches 2^31 (conv2d() returns hipErrorInvalidValue). The offsets are
-// deliberately not widened here: that would put 64-bit address arithmetic into the hot loop.
+// batch; conv_mfma_plan() (gale/conv_route.h) decides all of it on the host and the launcher
+// below launches from its result alone. The pixel index m and the input / residual element
+// offsets (pbase, roff) are 32-bit ints, so the plan refuses a launch whose batch*Ho*Wo (in whole
+// tiles), batch*H*W*Cin or batch*res_H*res_W*res_C reaches 2^31 (conv2d() returns
+// hipErrorInvalidValue). The offsets are deliberately not widened here: that would put 64-bit
+// address arithmetic into the hot loop.
 #include "common.cuh"
-#include "gale/kernels.h"
+#include "conv_launch.h"
 
 namespace gale {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kLdsBudget = 80 * 1024;  // 2 workgroups per CU by LDS
 
 enum { MODE_FAST = CONV_MFMA_FAST, MODE_GATHER = CONV_MFMA_GATHER, MODE_1X1 = CONV_MFMA_1X1 };
 
@@ -397,92 +397,12 @@ ConvKernelFn pick_kernel(int mode, bool in_f32, bool out_f32, int nt, int pr) {
                 : pick_nt<MODE_GATHER, false, false, F8>(nt, pr);
 }
 
-int ilog2_exact(int v) {
-  int s = 0;
-  while ((1 << s) < v) ++s;
-  return ((1 << s) == v) ? s : -1;
-}
-
 }  // namespace
 
-int conv_n_tiles(int Cout) {
-  // channel tiles per workgroup n-block: whole Cout for the small-channel CNNs, 128 otherwise
-  if (Cout <= 16) return 1;
-  if (Cout <= 32) return 2;
-  if (Cout <= 64) return 4;
-  return 8;
-}
-
-ConvMfmaPlan conv_mfma_plan(const ConvDesc& d, int batch, bool has_res) {
-  ConvMfmaPlan p;
-  if (batch <= 0) return p;
-  if (d.KH == 1 && d.KW == 1 && d.pad == 0 && d.Cin % 8 == 0) p.mode = CONV_MFMA_1X1;
-  else if (d.Cin % 8 == 0 && ilog2_exact(d.Cin) >= 0) p.mode = CONV_MFMA_FAST;
-  else p.mode = CONV_MFMA_GATHER;
-  if (d.out_f32 && p.mode != CONV_MFMA_1X1) return p;
-  if (d.Cout % 4 != 0 || d.Kpad % 32 != 0) return p;
-
-  // the kernel's pixel index, input offsets and residual offsets are 32-bit
-  const long long lim = 1ll << 31;
-  const long long M = (long long)batch * d.Ho * d.Wo;
-  if (M >= lim || (long long)batch * d.H * d.W * d.Cin >= lim) return p;
-  if (has_res && (long long)batch * d.res_H * d.res_W * d.res_C >= lim) return p;
-
-  p.nt = conv_n_tiles(d.Cout);
-  const int BN = p.nt * 16;
-  if (d.Npad % BN != 0) return p;
-  p.n_blocks = (d.Cout + BN - 1) / BN;
-  // pixel tiles per wave: the largest of {4 (2 for 8 channel tiles), 2, 1} that still gives the
-  // chip >= 4 workgroups per CU; small layers (late stages, small batches) trade B-fragment reuse
-  // for occupancy, which is what bounds them
-  p.pr = (p.nt >= 8) ? 2 : 4;
-  while (p.pr > 1 && (M + 64 * p.pr - 1) / (64 * p.pr) * p.n_blocks < 1024) p.pr >>= 1;
-  const int BM = 4 * p.pr * 16;
-  // (pixels past M in the last tile are indexed too, then masked)
-  if ((M + BM - 1) / BM * BM >= lim) return p;
-  p.m_tiles = (int)((M + BM - 1) / BM);
-
-  // K chunk: whole K if it fits the LDS budget (weight-stationary), else the largest multiple of
-  // 32 that does.
-  const int eb = d.fp8 ? 1 : 2;
-  p.bk = d.Kpad;
-  if ((size_t)BN * (p.bk + 16) * eb > (size_t)kLdsBudget) {
-    p.bk = (kLdsBudget / (BN * eb) - 16) & ~31;
-    if (p.bk < 32) return p;
-  }
-  p.nkc = (d.Kpad + p.bk - 1) / p.bk;
-  p.lds_bytes = (size_t)BN * (p.bk + 16) * eb;
-
-  p.grid_m = p.m_tiles;
-  if (p.nkc == 1) {
-    // weight-stationary: enough workgroups to fill 256 CUs x 8, each walks several tiles
-    const int cap = 2048 / p.n_blocks > 0 ? 2048 / p.n_blocks : 1;
-    p.grid_m = p.m_tiles < cap ? p.m_tiles : cap;
-  }
-  p.ok = true;
-  return p;
-}
-
-hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, const float* bias,
-                  const float* wscale, const void* res, void* y, hipStream_t stream) {
-  if (batch <= 0) return hipSuccess;
-  if (d.f32) return conv2d_f32(d, batch, x, w, bias, d.has_res ? res : nullptr, y, stream);
+hipError_t launch_conv_mfma(const ConvDesc& d, const ConvMfmaPlan& p, const void* x,
+                            const void* w, const float* bias, const float* wscale,
+                            const void* res, void* y, hipStream_t stream) {
   const bool f8 = d.fp8 != 0;
-  if (d.stem) {
-    if (f8 || d.in_f32 || d.out_f32 || d.Cin != 4 || d.KH != 8 || d.KW != 8 || d.K != 256 ||
-        d.Kpad != 256 || d.stride != 2 || d.pad != 3 || d.W != 2 * d.Wo + 6 ||
-        d.Cout % 64 != 0 || d.Npad % 64 != 0 || (d.has_res && res != nullptr))
-      return hipErrorInvalidValue;
-    return conv2d_gemm(d, batch, x, w, bias, nullptr, y, stream);
-  }
-  if (!f8 && conv_patch_supported(d, batch, d.has_res && res != nullptr))
-    return conv2d_patch(d, batch, x, w, bias, d.has_res ? res : nullptr, y, stream);
-  if (!f8 && conv_gemm_supported(d, batch, d.has_res && res != nullptr))
-    return conv2d_gemm(d, batch, x, w, bias, d.has_res ? res : nullptr, y, stream);
-  if (f8 && (wscale == nullptr || !(d.in_scale > 0.f) || !(d.out_scale > 0.f)))
-    return hipErrorInvalidValue;
-  const ConvMfmaPlan p = conv_mfma_plan(d, batch, d.has_res && res != nullptr);
-  if (!p.ok) return hipErrorInvalidValue;
   ConvArgs a;
   a.x = x;
   a.w = w;
@@ -490,19 +410,18 @@ hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, co
   a.wscale = wscale;
   a.res = res;
   a.y = y;
-  a.M = batch * d.Ho * d.Wo;
+  a.M = p.M;
   a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.Ho = d.Ho; a.Wo = d.Wo; a.HWo = d.Ho * d.Wo;
   a.Cout = d.Cout; a.KW = d.KW; a.stride = d.stride; a.pad = d.pad; a.K = d.K; a.Kpad = d.Kpad;
-  a.kw_magic = (65536 + d.KW - 1) / d.KW;
+  a.kw_magic = p.kw_magic;
   a.relu = d.relu;
-  a.has_res = d.has_res && res != nullptr;
+  a.has_res = res != nullptr;
   a.res_H = d.res_H; a.res_W = d.res_W; a.res_C = d.res_C; a.res_stride = d.res_stride;
   a.in_scale = f8 ? d.in_scale : 1.f;
   a.in_qinv = f8 ? 1.f / d.in_scale : 1.f;
   a.out_qinv = f8 ? 1.f / d.out_scale : 1.f;
   a.res_scale = f8 ? d.res_scale : 1.f;
-  const int cs = ilog2_exact(d.Cin);
-  a.cin_shift = cs < 0 ? 0 : cs;
+  a.cin_shift = p.cin_shift;
   a.BK = p.bk;
   a.nkc = p.nkc;
   a.m_tiles = p.m_tiles;
@@ -511,6 +430,22 @@ hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, co
                              : pick_kernel<false>(p.mode, d.in_f32, d.out_f32, p.nt, p.pr);
   hipLaunchKernelGGL(fn, dim3(p.grid_m, p.n_blocks), dim3(kThreads), p.lds_bytes, stream, a);
   return hipGetLastError();
+}
+
+// The one conv entry point: the route (gale/conv_route.h) decides, the launchers launch.
+hipError_t conv2d(const ConvDesc& d, int batch, const void* x, const void* w, const float* bias,
+                  const float* wscale, const void* res, void* y, hipStream_t stream) {
+  if (batch <= 0) return hipSuccess;
+  if (d.fp8 && wscale == nullptr) return hipErrorInvalidValue;
+  if (!d.has_res) res = nullptr;
+  const ConvRoute r = conv_route(d, batch, res != nullptr);
+  switch (r.kernel) {
+    case CONV_F32: return launch_conv_f32(d, r.f32, x, w, bias, res, y, stream);
+    case CONV_GEMM: return launch_conv_gemm(d, r.gemm, x, w, bias, res, y, stream);
+    case CONV_PATCH: return launch_conv_patch(d, r.patch, x, w, bias, res, y, stream);
+    case CONV_MFMA: return launch_conv_mfma(d, r.mfma, x, w, bias, wscale, res, y, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace gale

@@ -22,11 +22,8 @@
 // LDS row r holds 16-byte chunk s ^ ((r >> 1) & 7)). Fragment rows map pixel p of the tile to
 // patch row (p / W + kh) * (W + 2) + p % W + kw; rows past the tile's pixels read a zero row.
 // The epilogue (bias, residual, ReLU) is the same as conv_gemm's, staged through LDS.
-#include <algorithm>
-#include <atomic>
-
 #include "common.cuh"
-#include "gale/kernels.h"
+#include "conv_launch.h"
 
 namespace gale {
 namespace {
@@ -287,64 +284,11 @@ void conv_patch_kernel(PatchArgs a) {
   }
 }
 
-// the patch-row capacities compiled (2 workgroups per CU at BN = 128 up to 184 rows)
-constexpr int kPrr[3] = {152, 184, 240};
-
-int patch_tile_rows(const ConvDesc& d) {
-  // largest divisor of H whose rows hold <= 128 pixels
-  for (int tr = 128 / d.W; tr >= 1; --tr)
-    if (d.H % tr == 0) return tr;
-  return 0;
-}
-
-// whole images per tile: several when one image's rows fill less than half the tile (7x7: 2 x 49
-// of 128 MFMA rows)
-int patch_images(const ConvDesc& d, int tr) {
-  if (tr != d.H) return 1;
-  return std::max(1, 128 / (d.H * d.W));
-}
-
-int patch_prr(int PR) {
-  for (int c : kPrr)
-    if (PR + 1 <= c) return c;
-  return 0;
-}
-
-int patch_bn(const ConvDesc& d) { return (d.Npad % 128 == 0) ? 128 : 64; }
-
 }  // namespace
 
-// conv_patch mode (set_conv_patch): 0 off, 1 (default) the 128-channel tiles (ResNet-50 28x28
-// and 14x14 conv2: 90 -> 77 us and 86 -> 76 us per layer at batch 256), 2 also the 64-channel
-// tiles (the 56x56 conv2 measured 104-110 -> 125-127 us there: one input block per tile leaves
-// the patch load exposed, so those stay on conv_gemm; profiles/archive/r2_conv_patch.txt)
-static std::atomic<int> g_conv_patch{1};
-
-void set_conv_patch(int mode) { g_conv_patch = mode; }
-
-bool conv_patch_supported(const ConvDesc& d, int batch, bool has_res) {
-  if (!g_conv_patch.load(std::memory_order_relaxed) || conv_path() == 1) return false;
-  if (d.stem || d.fp8 || d.f32 || d.in_f32 || d.out_f32) return false;
-  if (d.KH != 3 || d.KW != 3 || d.stride != 1 || d.pad != 1) return false;
-  if (d.Cin % 64 != 0 || d.K != 9 * d.Cin || d.Kpad != d.K) return false;
-  if (d.Ho != d.H || d.Wo != d.W || d.W > 128 || d.Cout % 8 != 0) return false;
-  const int bn = patch_bn(d);
-  if (d.Npad % bn != 0 || d.Npad < d.Cout) return false;
-  if (bn == 64 && g_conv_patch.load(std::memory_order_relaxed) < 2) return false;
-  if (has_res && (d.res_C != d.Cout || d.res_stride != 1 || d.res_H != d.H || d.res_W != d.W))
-    return false;
-  const int tr = patch_tile_rows(d);
-  const int img = tr >= 1 ? patch_images(d, tr) : 1;
-  // (a tile below 3/4 of its MFMA rows wastes too much)
-  if (tr < 1 || img * tr * d.W * 4 < 128 * 3 - 16) return false;
-  const int prr = patch_prr(img * (tr + 2) * (d.W + 2));
-  if (prr == 0 || (bn == 128 && prr > 184)) return false;
-  return (long long)batch * d.H * d.W * d.Cin < (1ll << 31) &&
-         (long long)batch * d.H * d.W * d.Cout < (1ll << 31);
-}
-
-hipError_t conv2d_patch(const ConvDesc& d, int batch, const void* x, const void* w,
-                        const float* bias, const void* res, void* y, hipStream_t stream) {
+hipError_t launch_conv_patch(const ConvDesc& d, const ConvPatchPlan& p, const void* x,
+                             const void* w, const float* bias, const void* res, void* y,
+                             hipStream_t stream) {
   PatchArgs a;
   a.x = static_cast<const bf16*>(x);
   a.w = static_cast<const bf16*>(w);
@@ -352,37 +296,21 @@ hipError_t conv2d_patch(const ConvDesc& d, int batch, const void* x, const void*
   a.res = static_cast<const bf16*>(res);
   a.y = static_cast<bf16*>(y);
   a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.Cout = d.Cout; a.Kpad = d.Kpad;
-  const int bn = patch_bn(d);
-  a.TR = patch_tile_rows(d);
-  if (a.TR < 1) return hipErrorInvalidValue;
-  a.IMG = patch_images(d, a.TR);
-  a.B = batch;
-  a.P = a.IMG * a.TR * d.W;
-  a.PW = d.W + 2;
-  a.PR1 = (a.TR + 2) * a.PW;
-  a.PR = a.IMG * a.PR1;
-  a.rblocks = d.H / a.TR;
-  a.nsteps = 9 * (d.Cin / 64);  // k-steps: one tap of 64 input channels each
+  a.TR = p.TR; a.P = p.P; a.PW = p.PW; a.PR = p.PR;
+  a.rblocks = p.rblocks;
+  a.IMG = p.IMG; a.PR1 = p.PR1; a.B = p.batch;
+  a.nsteps = p.nsteps;
   a.relu = d.relu;
-  a.has_res = d.has_res && res != nullptr;
-  a.n_tiles = d.Npad / bn;
-  a.nwg = (batch + a.IMG - 1) / a.IMG * a.rblocks * a.n_tiles;
-  const int prr = patch_prr(a.PR);
-  if (a.P > 128 || prr == 0) return hipErrorInvalidValue;
-  if (bn == 128) {
-    if (prr > 184) return hipErrorInvalidValue;
-    if (prr == 152)
-      hipLaunchKernelGGL((conv_patch_kernel<128, 152>), dim3(a.nwg), dim3(256), 0, stream, a);
-    else
-      hipLaunchKernelGGL((conv_patch_kernel<128, 184>), dim3(a.nwg), dim3(256), 0, stream, a);
-  } else {
-    if (prr == 152)
-      hipLaunchKernelGGL((conv_patch_kernel<64, 152>), dim3(a.nwg), dim3(256), 0, stream, a);
-    else if (prr == 184)
-      hipLaunchKernelGGL((conv_patch_kernel<64, 184>), dim3(a.nwg), dim3(256), 0, stream, a);
-    else
-      hipLaunchKernelGGL((conv_patch_kernel<64, 240>), dim3(a.nwg), dim3(256), 0, stream, a);
-  }
+  a.has_res = res != nullptr;
+  a.n_tiles = p.n_tiles;
+  a.nwg = p.nwg;
+  // the (channel tile, patch-row capacity) forms compiled: 128 channels up to 184 rows (2
+  // workgroups per CU), 64 channels up to 240
+  void (*fn)(PatchArgs);
+  if (p.bn == 128) fn = p.prr == 152 ? conv_patch_kernel<128, 152> : conv_patch_kernel<128, 184>;
+  else if (p.prr == 152) fn = conv_patch_kernel<64, 152>;
+  else fn = p.prr == 184 ? conv_patch_kernel<64, 184> : conv_patch_kernel<64, 240>;
+  hipLaunchKernelGGL(fn, dim3(p.nwg), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -42,6 +42,9 @@ constexpr int kWBytes = kK / 64 * kC * 128;  // 32 KB: 4 k-blocks x 64 rows x 12
 constexpr int kTileBytes = kSR * kSO * 128;  // 129,024
 static_assert(kSR * kSO % 16 == 0 && kPO % kPR == 0, "tile geometry");
 static_assert(kWBytes + kTileBytes <= 163840, "LDS");
+static_assert(kIH == kStemInH && kIW == kStemInW && kSO == kStemOut && kPO == kStemPooled &&
+                  kC == kStemC && kK == kStemK,
+              "stem_pool_supported (gale/conv_route.h) admits the compiled geometry");
 
 __device__ __forceinline__ int rkey(int row) { return (row >> 1) & 7; }
 __device__ __forceinline__ int swz(int row, int c) { return row * 128 + ((c ^ rkey(row)) << 4); }
@@ -180,14 +183,6 @@ __global__ __launch_bounds__(512, 1) void stem_pool_kernel(StemPoolArgs a) {
 }
 
 }  // namespace
-
-bool stem_pool_supported(const ConvDesc& d, int H, int W, int C, int k, int s, int p, int Ho,
-                         int Wo) {
-  return d.stem && !d.fp8 && !d.f32 && !d.out_f32 && d.relu && !d.has_res && d.H == kIH &&
-         d.W == kIW && d.Ho == kSO && d.Wo == kSO && d.Cout == kC && d.Npad == kC &&
-         d.K == kK && d.Kpad == kK && H == kSO && W == kSO && C == kC && k == 3 && s == 2 &&
-         p == 1 && Ho == kPO && Wo == kPO;
-}
 
 hipError_t stem_pool(int batch, const void* x, const void* w, const float* bias, void* y,
                      hipStream_t stream) {

@@ -14,12 +14,6 @@ void check_hip(hipError_t e, const char* what) {
 
 Executor::Executor(int device, PlanSpec spec) : device_(device), spec_(std::move(spec)) {
   validate_plan(spec_);
-  for (size_t i = 0; i < spec_.ops.size(); ++i)
-    if (const StemPoolOp* o = std::get_if<StemPoolOp>(&spec_.ops[i].params))
-      if (!stem_pool_supported(o->conv, o->g.H, o->g.W, o->g.C, o->g.k, o->g.s, o->g.pad, o->g.Ho,
-                               o->g.Wo))
-        throw std::invalid_argument("plan op " + std::to_string(i) +
-                                    " (stem_pool): unsupported geometry");
   buckets_ = spec_.buckets;
   if (buckets_.empty()) {
     for (int b = 1; b < spec_.max_batch; b *= 2) buckets_.push_back(b);

@@ -1,6 +1,7 @@
 // Forward-plan validation (see gale/forward_plan.h). Host only.
 #include "gale/forward_plan.h"
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -19,6 +20,8 @@ namespace {
 struct OpCheck {
   size_t index;
   int kind;
+  int batch;     // the largest batch the executor launches this op with
+  bool has_res;  // the op has a residual buffer
 
   [[noreturn]] void fail(const std::string& what) const {
     throw std::invalid_argument("plan op " + std::to_string(index) + " (" + op_kind_name(kind) +
@@ -42,6 +45,8 @@ struct OpCheck {
     ptr(o.w, "w");
     ptr(o.bias, "bias");
     if (o.conv.fp8) ptr(o.wscale, "wscale");
+    const ConvRoute r = conv_route(o.conv, batch, has_res && o.conv.has_res);
+    if (r.kernel == CONV_NONE) fail(std::string("no conv kernel takes it: ") + r.refusal);
   }
   void operator()(const MaxPoolOp& o) const { elem_type(o.et); }
   void operator()(const AvgPoolOp& o) const { elem_type(o.et); }
@@ -85,16 +90,23 @@ struct OpCheck {
       ptr(p.wd, "wd");
       ptr(p.bd, "bd");
     }
+    need(bottleneck56_supported(kBneckH, kBneckW, p.cin, kBneckMid, kBneckOut, p.down),
+         "cin is not the 56x56 bottleneck's (256, or 64 with down)");
   }
   void operator()(const StemPoolOp& o) const {
     ptr(o.w, "w");
     ptr(o.bias, "bias");
+    const PoolGeom& g = o.g;
+    need(stem_pool_supported(o.conv, g.H, g.W, g.C, g.k, g.s, g.pad, g.Ho, g.Wo),
+         "unsupported geometry (not the 224x224 stem + 3x3/2 max-pool)");
   }
   void operator()(const ConvProjOp& o) const {
     ptr(o.w, "w");
     ptr(o.bias, "bias");
     ptr(o.wd, "wd");
     ptr(o.bd, "bd");
+    need(conv_gemm_proj_supported(o.conv, batch, o.H2, o.W2, o.Cin2, o.stride2, o.Kpad2),
+         "unsupported geometry (conv3 + projection as one GEMM)");
   }
 };
 
@@ -109,7 +121,10 @@ void validate_plan(const PlanSpec& spec) {
   const int nb = (int)bytes.size();
   for (size_t i = 0; i < spec.ops.size(); ++i) {
     const PlanOp& op = spec.ops[i];
-    const OpCheck c{i, op.kind()};
+    const bool chunked = spec.chunk_images > 0 && (int)i < spec.chunk_ops;
+    const OpCheck c{i, op.kind(),
+                    chunked ? std::min(spec.chunk_images, spec.max_batch) : spec.max_batch,
+                    op.res >= 0};
     c.need(op.in >= 0 && op.in < nb, "in is outside the buffer table");
     c.need(op.out >= 0 && op.out < nb, "out is outside the buffer table");
     c.need(op.res >= -1 && op.res < nb, "res is outside the buffer table");
@@ -122,7 +137,7 @@ void validate_plan(const PlanSpec& spec) {
       c.need(op.bpi[k] >= 0, "bpi is negative");
       if (ids[k] >= 0) c.need(op.bpi[k] <= bytes[ids[k]], over[k]);
     }
-    if (spec.chunk_images > 0 && (int)i < spec.chunk_ops)
+    if (chunked)
       c.need(op.bpi[0] > 0 && op.bpi[1] > 0 && (op.res < 0 || op.bpi[2] > 0),
              "chunked without per-image operand bytes (bpi)");
     std::visit(c, op.params);

@@ -1,7 +1,7 @@
 // Sanitizer run of the forward plan's validation (gale/forward_plan.h): a fixed seed, plans
 // holding every op kind over a random buffer table, then random corruption - buffer ids in and
-// out of range, null pointers, element types, bytes per image, chunking figures. validate_plan
-// must refuse by std::invalid_argument exactly the plans the second derivation below calls
+// out of range, null pointers, element types, bytes per image, chunking figures, conv and fused-op
+// geometry no kernel takes. validate_plan must refuse by std::invalid_argument exactly the plans the second derivation below calls
 // unlaunchable, so an accepted plan has every id inside the table.
 //   build/asan/forward_plan_check [iterations]
 #include <stdint.h>
@@ -33,11 +33,34 @@ int failures = 0;
 float storage[4];  // (addresses for the plan's pointers; nothing reads through them)
 const float* kPtr = storage;
 
+// The conv geometries of the valid plans: a 3x3 16 -> 16 conv on 8x8 (bf16 or fp8: the MFMA
+// kernel), the ResNet-50 packed stem, and conv3 of its first bottleneck (1x1 64 -> 256 on 56x56).
+ConvDesc conv3x3(int fp8) {
+  ConvDesc d{};
+  d.H = d.W = d.Ho = d.Wo = 8, d.Cin = d.Cout = d.Npad = 16;
+  d.KH = d.KW = 3, d.stride = d.pad = 1, d.K = 144, d.Kpad = 160;
+  d.fp8 = fp8, d.in_scale = d.out_scale = d.res_scale = 0.5f;
+  return d;
+}
+ConvDesc stem_desc() {
+  ConvDesc d{};
+  d.H = 224, d.W = 230, d.Cin = 4, d.Ho = d.Wo = 112, d.Cout = d.Npad = 64;
+  d.KH = d.KW = 8, d.stride = 2, d.pad = 3, d.K = d.Kpad = 256, d.relu = 1, d.stem = 1;
+  return d;
+}
+ConvDesc conv3_desc() {
+  ConvDesc d{};
+  d.H = d.W = d.Ho = d.Wo = 56, d.Cin = d.K = d.Kpad = 64, d.Cout = d.Npad = 256;
+  d.KH = d.KW = d.stride = 1, d.relu = 1;
+  return d;
+}
+const PoolGeom kStemPool = {112, 112, 64, 3, 2, 1, 56, 56};
+
 OpParams valid_params(int kind, std::mt19937& rng) {
   switch (kind) {
     case OP_CONV: {
       ConvOp o;
-      o.conv.fp8 = rng() % 2;
+      o.conv = conv3x3(rng() % 2);
       o.w = o.bias = kPtr;
       if (o.conv.fp8) o.wscale = kPtr;
       return o;
@@ -87,16 +110,21 @@ OpParams valid_params(int kind, std::mt19937& rng) {
       p.w1 = p.w2 = p.w3 = kPtr;
       p.b1 = p.b2 = p.b3 = kPtr;
       p.down = rng() % 2;
+      p.cin = p.down ? 64 : 256;
       if (p.down) p.wd = p.bd = kPtr;
       return p;
     }
     case OP_STEM_POOL: {
       StemPoolOp o;
+      o.conv = stem_desc();
+      o.g = kStemPool;
       o.w = o.bias = kPtr;
       return o;
     }
     default: {
       ConvProjOp o;
+      o.conv = conv3_desc();
+      o.H2 = o.W2 = 56, o.Cin2 = o.Kpad2 = 64, o.stride2 = 1;
       o.w = o.wd = kPtr;
       o.bias = o.bd = kPtr;
       return o;
@@ -145,6 +173,36 @@ void null_a_pointer(OpParams& params, std::mt19937& rng) {
   }
 }
 
+// one field of the op's geometry set to a value no kernel takes (ops without geometry: nothing)
+void break_geometry(OpParams& params, std::mt19937& rng) {
+  const unsigned r = rng();
+  if (auto* o = std::get_if<ConvOp>(&params)) {
+    switch (r % 6) {
+      case 0: o->conv.Cout = 18; break;                   // Cout % 4
+      case 1: o->conv.Kpad = 144; break;                  // Kpad % 32
+      case 2: o->conv.Npad = 24; break;                   // Npad % (16 nt)
+      case 3: o->conv.out_f32 = 1; break;                 // fp32 out outside a 1x1
+      case 4: o->conv.fp8 = 1, o->conv.in_scale = 0.f; break;
+      default: o->conv.H = o->conv.W = 1 << 14; break;    // max_batch*H*W*Cin >= 2^31
+    }
+  } else if (auto* p = std::get_if<BottleneckParams>(&params)) {
+    p->cin = 128;
+  } else if (auto* o = std::get_if<StemPoolOp>(&params)) {
+    if (r % 2) o->g.Ho = 55; else o->conv.Ho = 111;
+  } else if (auto* o = std::get_if<ConvProjOp>(&params)) {
+    if (r % 2) o->Cin2 = 96; else o->conv.has_res = 1;
+  }
+}
+
+// (memberwise: the valid plans' descs against a corrupted one)
+bool same_desc(const ConvDesc& a, const ConvDesc& b) {
+  return a.H == b.H && a.W == b.W && a.Cin == b.Cin && a.Ho == b.Ho && a.Wo == b.Wo &&
+         a.Cout == b.Cout && a.KH == b.KH && a.KW == b.KW && a.stride == b.stride &&
+         a.pad == b.pad && a.K == b.K && a.Kpad == b.Kpad && a.Npad == b.Npad &&
+         a.has_res == b.has_res && a.out_f32 == b.out_f32 && a.stem == b.stem &&
+         a.fp8 == b.fp8 && a.in_scale == b.in_scale;
+}
+
 void set_et(OpParams& params, int et) {
   if (auto* o = std::get_if<MaxPoolOp>(&params)) o->et = et;
   if (auto* o = std::get_if<AvgPoolOp>(&params)) o->et = et;
@@ -176,7 +234,10 @@ bool launchable(const PlanSpec& s) {
     switch (op.kind()) {
       case OP_CONV: {
         const ConvOp& o = std::get<ConvOp>(op.params);
-        have = o.w && o.bias && (!o.conv.fp8 || o.wscale);
+        // (geometry: the valid plans' conv, or one break_geometry broke; 2^14 x 2^14 x 16
+        // elements per image are 2^32, over the kernels' 32-bit offsets at any batch)
+        have = o.w && o.bias && (!o.conv.fp8 || o.wscale) &&
+               same_desc(o.conv, conv3x3(o.conv.fp8));
         break;
       }
       case OP_MAXPOOL: et = std::get<MaxPoolOp>(op.params).et; break;
@@ -207,17 +268,19 @@ bool launchable(const PlanSpec& s) {
       }
       case OP_BOTTLENECK: {
         const BottleneckParams& p = std::get<BottleneckParams>(op.params);
-        have = p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3 && (!p.down || (p.wd && p.bd));
+        have = p.w1 && p.b1 && p.w2 && p.b2 && p.w3 && p.b3 && (!p.down || (p.wd && p.bd)) &&
+               p.cin == (p.down ? 64 : 256);
         break;
       }
       case OP_STEM_POOL: {
         const StemPoolOp& o = std::get<StemPoolOp>(op.params);
-        have = o.w && o.bias;
+        have = o.w && o.bias && same_desc(o.conv, stem_desc()) && o.g.Ho == 56;
         break;
       }
       case OP_CONV_PROJ: {
         const ConvProjOp& o = std::get<ConvProjOp>(op.params);
-        have = o.w && o.bias && o.wd && o.bd && op.res >= 0;
+        have = o.w && o.bias && o.wd && o.bd && op.res >= 0 && o.Cin2 == 64 &&
+               same_desc(o.conv, conv3_desc());
         break;
       }
       default: break;  // softmax, stem_pack: dimensions only
@@ -261,7 +324,7 @@ int main(int argc, char** argv) {
     for (int m = corrupt ? 1 + (int)(rng() % 3) : 0; m > 0; --m) {
       PlanOp& op = s.ops[rng() % s.ops.size()];
       const int wild = (int)(rng() % (nb + 6)) - 3;  // -3 .. nb + 2
-      switch (rng() % 9) {
+      switch (rng() % 10) {
         case 0: op.in = wild; break;
         case 1: op.out = wild; break;
         case 2: op.res = wild; break;
@@ -273,6 +336,7 @@ int main(int argc, char** argv) {
           s.chunk_images = (int)(rng() % 6) - 1;
           break;
         case 7: s.buf_bytes_per_image.resize(rng() % (nb + 1)); break;
+        case 8: break_geometry(op.params, rng); break;
         default: (rng() % 2 ? s.max_batch : s.slots) = (int)(rng() % 3) - 1;
       }
     }

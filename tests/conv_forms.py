@@ -50,6 +50,39 @@ FORMS = [
     # small shape
     Form("k4608_pr1", 2, 7, 7, 512, 512, 3, 1, 1, False, False, None, True,
          "fast", 8, 1, 4, (288, 608), (16, 8), 2, 2, 34),
+    # The remaining (mode, NT, PR) instantiations the zoo plans launch at some batch up to 1024
+    # (tests/golden/conv_routes.json): the PR1 forms of small launches ...
+    Form("c16_pr1", 2, 9, 9, 16, 16, 3, 1, 1, False, False, None, True,
+         "fast", 1, 1, 1, 160, 1, 3, 3, 34),
+    Form("c32_pr1", 2, 9, 9, 16, 32, 3, 1, 1, False, False, "identity", True,
+         "fast", 2, 1, 1, 160, 1, 3, 3, 34),
+    Form("c64_pr1", 2, 9, 9, 32, 64, 3, 1, 1, False, False, None, True,
+         "fast", 4, 1, 1, 288, 1, 3, 3, 34),
+    Form("reduce_pr1", 2, 7, 7, 64, 64, 1, 1, 0, False, False, None, True,
+         "1x1", 4, 1, 1, 64, 1, 2, 2, 34),
+    Form("expand_pr1", 2, 7, 7, 64, 256, 1, 1, 0, False, False, "identity", True,
+         "1x1", 8, 1, 2, 64, 1, 2, 2, 34),
+    Form("fc_out_f32_pr1", 65, 1, 1, 64, 1000, 1, 1, 0, False, True, None, False,
+         "1x1", 8, 1, 8, 64, 1, 2, 2, 1),
+    Form("stem3_pr1", 2, 9, 9, 3, 16, 3, 1, 1, True, False, None, True,
+         "gather", 1, 1, 1, 32, 1, 3, 3, 34),
+    Form("stem7_pr1", 2, 29, 29, 3, 64, 7, 2, 3, True, False, None, True,
+         "gather", 4, 1, 1, 160, 1, 8, 8, 2),
+    # ... and the PR2 / PR4 forms at the smallest batch that selects them
+    Form("c16_pr2", 137, 31, 31, 16, 16, 3, 1, 1, False, False, None, False,
+         "fast", 1, 2, 1, 160, 1, 1029, 1029, 73),
+    Form("c32_s2_pr4", 1164, 29, 29, 16, 32, 3, 2, 1, False, False, None, False,
+         "fast", 2, 4, 1, 160, 1, 1024, 1024, 12),
+    Form("reduce_pr2", 2673, 7, 7, 64, 64, 1, 1, 0, False, False, None, False,
+         "1x1", 4, 2, 1, 64, 1, 1024, 1024, 33),
+    Form("reduce_pr4", 5345, 7, 7, 64, 64, 1, 1, 0, False, False, "identity", True,
+         "1x1", 4, 4, 1, 64, 1, 1024, 1024, 17),
+    Form("stem3_pr2", 137, 31, 31, 3, 16, 3, 1, 1, True, False, None, False,
+         "gather", 1, 2, 1, 32, 1, 1029, 1029, 73),
+    Form("stem7_pr2", 582, 29, 29, 3, 64, 7, 2, 3, True, False, None, True,
+         "gather", 4, 2, 1, 160, 1, 1024, 1024, 6),
+    Form("stem7_pr4", 1164, 29, 29, 3, 64, 7, 2, 3, True, False, None, False,
+         "gather", 4, 4, 1, 160, 1, 1024, 1024, 12),
 ]
 
 PLAN_KEYS = ("mode", "nt", "pr", "n_blocks", "bk", "nkc", "m_tiles", "grid_m")

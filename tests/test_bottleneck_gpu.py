@@ -137,6 +137,8 @@ def test_stem_pool_matches_layered_stem_and_maxpool():
     xp = torch.empty(B, 224, Wp, 4, device=DEV, dtype=torch.bfloat16)
     C.stem_pack(B, H, W, Cc, Wp, lp, x.data_ptr(), xp.data_ptr(), s)
     s0 = torch.empty(B, 112, 112, 64, device=DEV, dtype=torch.bfloat16)
+    route = C.conv_route(st["conv"], B, False)  # conv_gemm's packed-stem form, 64-channel tiles
+    assert (route["kernel"], route["stem"], route["bn"], route["stages"]) == ("gemm", 1, 64, 2)
     C.conv2d(st["conv"], B, xp.data_ptr(), st["w"], st["bias"], 0, 0, s0.data_ptr(), s)
     ref = torch.empty(B, 56, 56, 64, device=DEV, dtype=torch.bfloat16)
     C.maxpool2d(B, *(mp[k] for k in ("H", "W", "C", "k", "s", "pad", "Ho", "Wo")), s0.data_ptr(),

@@ -13,7 +13,8 @@ partial sum is an exact fp32 value (K <= 4608: below 2^24 quanta), so the fp32 C
 the same values is the exact result whatever its summation order and the kernel's only rounding
 is the one to its output type. y is prefilled with a NaN pattern no launch can produce and is one
 256-row tile longer than M: a tile the walk skipped shows up as NaNs inside, a write past M in the
-tail. Each test first asserts, through conv_mfma_plan(), the form it is about to launch.
+tail. Each test first asserts, through conv_mfma_plan() and conv_route(), the kernel and form it
+is about to launch.
 """
 
 import pytest
@@ -77,6 +78,9 @@ def _launch(f, fp8, x, wp, bp, ws, geom, res, out_dtype, out_scale=1.0):
     try:
         if force:
             C.set_conv_path(1)
+        route = C.conv_route(d, f.B, res is not None)
+        assert route["kernel"] == "mfma"
+        conv_forms.check_plan(route, f, fp8)
         C.conv2d(d, f.B, x.data_ptr(), wp.data_ptr(), bp.data_ptr(),
                  ws.data_ptr() if fp8 else 0, res.data_ptr() if res is not None else 0,
                  y.data_ptr(), torch.cuda.current_stream().cuda_stream)

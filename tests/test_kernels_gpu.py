@@ -10,6 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_routes
+from conv_routes import GEMM_CASES, GEMM_FORMS, PATCH_CASES, PATCH_FORMS, TAP_CASES
+
 from gale import ops
 
 pytestmark = pytest.mark.gpu
@@ -250,19 +253,11 @@ def test_pool_and_head_fp8():
     assert (probs - refp).abs().max().item() < 1e-4
 
 
-GEMM_CASES = [
-    # B, H, W, Cin, Cout, k, stride, pad, residual
-    (2, 14, 14, 64, 64, 3, 1, 1, False),      # ResNet-50 stage 1 3x3 (BN = 64), M % 128 != 0
-    (3, 9, 11, 64, 128, 3, 2, 1, True),       # strided 3x3, odd sizes, BN = 128, residual
-    (2, 14, 14, 256, 128, 1, 2, 0, False),    # 1x1 stride-2 projection
-    (4, 7, 7, 128, 512, 1, 1, 0, True),       # 1x1 expand + residual
-    (1, 7, 7, 512, 512, 3, 1, 1, False),      # K = 4608 (72 k-steps)
-]
-
-
 @pytest.mark.parametrize("case", GEMM_CASES)
 def test_conv2d_gemm_path_matches_torch(case):
-    """The LDS-pipelined GEMM conv (conv_gemm.hip), forced on small shapes, vs fp32 torch."""
+    """The LDS-pipelined GEMM conv (conv_gemm.hip), forced on small shapes, vs fp32 torch. A case
+    the patch kernel would take in its default mode (7x7x512) has it switched off for the GEMM
+    half; each half first asserts, through conv_route, the kernel it is about to launch."""
     from gale._native import native
 
     B, H, W, Cin, Cout, k, s, p, with_res = case
@@ -275,15 +270,23 @@ def test_conv2d_gemm_path_matches_torch(case):
     Wo = (W + 2 * p - k) // s + 1
     res = torch.randn(B, Ho, Wo, Cout, generator=g).to(torch.bfloat16) if with_res else None
     C = native()
+    d = conv_routes.gemm_desc(case)
+    assert {k: d[k] for k in geom} == geom
     try:
         C.set_conv_path(2)
+        if C.conv_route(d, B, with_res)["kernel"] == "patch":
+            C.set_conv_patch(0)
+        r = C.conv_route(d, B, with_res)
+        assert (r["kernel"], r["bn"], r["stages"]) == ("gemm",) + GEMM_FORMS[GEMM_CASES.index(case)]
         y = ops.conv2d(x.to(DEV), wp, bp, geom, stride=s, pad=p, relu=True,
                        residual=None if res is None else res.to(DEV))
         C.set_conv_path(1)
+        assert C.conv_route(d, B, with_res)["kernel"] == "mfma"
         y_old = ops.conv2d(x.to(DEV), wp, bp, geom, stride=s, pad=p, relu=True,
                            residual=None if res is None else res.to(DEV))
     finally:
         C.set_conv_path(0)
+        C.set_conv_patch(1)
     ref = _ref_conv(x.float(), w.to(torch.bfloat16).float(), b, s, p, True, res=res)
     got = y.float().cpu()
     err = (got - ref).abs().max().item()
@@ -305,6 +308,8 @@ def test_conv2d_gemm_identity_asymmetric():
     wp, bp, geom = ops.pack_conv(w, torch.zeros(C))
     try:
         native().set_conv_path(2)
+        r = native().conv_route(conv_routes.conv_desc(H, H, C, C, 1, 1, 0, relu=False), B, False)
+        assert (r["kernel"], r["bn"], r["stages"]) == ("gemm", 128, 2)
         y = ops.conv2d(x.to(DEV), wp, bp, geom)
     finally:
         native().set_conv_path(0)
@@ -410,21 +415,15 @@ def test_conv_f32_matches_fp32(B, H, W, Cin, Cout, k, stride, pad, res):
                  res_stride=2 if res == "pad" else 1)
         rd = rd_t.data_ptr()
     xd, bd = x.to(DEV), b.to(DEV)
+    route = native().conv_route(d, B, r is not None)
+    assert (route["kernel"], route["grid_m"], route["grid_n"]) == ("f32", -(-B * Ho * Wo // 64),
+                                                                   -(-Cout // 64))
     native().conv2d(d, B, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), 0, rd, y.data_ptr(),
                     torch.cuda.current_stream().cuda_stream)
     ref = _ref_conv(x, w, b, stride, pad, True, r, res or "identity")
     got = y.cpu()
     scale = ref.abs().max().item()
     assert (got - ref).abs().max().item() < 2e-5 * max(scale, 1.0)
-
-
-PATCH_CASES = [  # B, H, W, Cin, Cout, with_res: the ResNet-50 3x3 stride-1 shapes (+ residual)
-    (2, 56, 56, 64, 64, False),     # 2 rows x 56 per tile, BN = 64, 240-row patch
-    (3, 28, 28, 128, 128, True),    # 4 rows x 28, BN = 128
-    (2, 14, 14, 256, 256, False),   # 7 rows x 14 (98 of 128 MFMA rows), two channel tiles
-    (1, 14, 14, 128, 64, True),     # BN = 64 at 14 x 14
-    (3, 7, 7, 512, 512, True),      # two whole 7 x 7 images per tile, a partial last tile
-]
 
 
 def _patch_desc(geom, B, H, W, has_res):
@@ -451,9 +450,12 @@ def test_conv2d_patch_path_matches_torch(case):
     try:
         C.set_conv_patch(2)  # (2: the 64-channel tiles too)
         assert C.conv_patch_supported(_patch_desc(geom, B, H, W, with_res), B, with_res)
+        r = C.conv_route(_patch_desc(geom, B, H, W, with_res), B, with_res)
+        assert (r["kernel"], r["bn"], r["prr"]) == ("patch",) + PATCH_FORMS[PATCH_CASES.index(case)]
         y = ops.conv2d(x.to(DEV), wp, bp, geom, stride=1, pad=1, relu=True,
                        residual=None if res is None else res.to(DEV))
         C.set_conv_patch(0)
+        assert C.conv_route(_patch_desc(geom, B, H, W, with_res), B, with_res)["kernel"] == "gemm"
         y_gemm = ops.conv2d(x.to(DEV), wp, bp, geom, stride=1, pad=1, relu=True,
                             residual=None if res is None else res.to(DEV))
     finally:
@@ -466,8 +468,7 @@ def test_conv2d_patch_path_matches_torch(case):
     assert (y.float() - y_gemm.float()).abs().max().item() <= 1e-2 * scale + 1e-2
 
 
-@pytest.mark.parametrize("H,C,tap", [(56, 64, 4), (28, 128, 0), (14, 256, 8), (28, 128, 5),
-                                     (7, 128, 0), (7, 128, 8)])
+@pytest.mark.parametrize("H,C,tap", TAP_CASES)
 def test_conv2d_patch_single_tap_shift_is_exact(H, C, tap):
     """One identity tap (kh, kw) and zeros elsewhere: y[n, i, j] = x[n, i + kh - 1, j + kw - 1]
     (zero outside the image), bit exact - pins the patch-row mapping, the halo and the zero
@@ -484,6 +485,7 @@ def test_conv2d_patch_single_tap_shift_is_exact(H, C, tap):
     try:
         native().set_conv_patch(2)
         assert native().conv_patch_supported(_patch_desc(geom, B, H, H, False), B, False)
+        assert native().conv_route(_patch_desc(geom, B, H, H, False), B, False)["kernel"] == "patch"
         y = ops.conv2d(x.to(DEV), wp, bp, geom, stride=1, pad=1).cpu()
     finally:
         native().set_conv_patch(1)
