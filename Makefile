@@ -106,6 +106,16 @@ build/asan/pixel_source_check: csrc/tests/pixel_source_check.cpp csrc/codec/json
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/pixel_source_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
+# typed tensor records (csrc/tests/elemtype_check.cpp): the element codec on every 16-bit pattern
+# and on f32 patterns, PixelSource's fourth arm (names, bytes, refusals, ingest dimensions) and the
+# typed record decoder on planted, mutated and truncated records; codec only, no engine, no HIP call
+build/asan/elemtype_check: csrc/tests/elemtype_check.cpp csrc/codec/json_codec.cpp \
+                           csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/elemtype_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
 # the b64 ingest's host plan behind the scanner, on mutated records and mutated scan results
 # (csrc/tests/b64_plan_check.cpp): codec + plan, no engine, no HIP call
 build/asan/b64_plan_check: csrc/tests/b64_plan_check.cpp csrc/runtime/ingest_plan.cpp \

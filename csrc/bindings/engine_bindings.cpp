@@ -117,6 +117,13 @@ EngineConfig config_from_dict(const py::dict& d) {
     opt(d, "yuv_range", yr);
     c.pixels = PixelSource::from_names(pf, d.contains("yuv_matrix") ? &ym : nullptr,
                                        d.contains("yuv_range") ? &yr : nullptr);
+    // the strings' element type (gale/models/preprocess.py ElemType.engine_entries; absent =
+    // u8): a typed tensor in the rgb layout
+    if (d.contains("input_dtype")) {
+      std::string dt = "u8";
+      opt(d, "input_dtype", dt);
+      c.pixels = c.pixels.with_elem(dt);
+    }
   }
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
@@ -138,7 +145,10 @@ EngineConfig config_from_dict(const py::dict& d) {
   } else if (c.resize_antialias) {
     throw std::invalid_argument("resize_antialias: no input resize is active");
   }
-  c.pixels.check(c.C, c.prep.nchw != 0, c.rec_h(), c.rec_w(), c.input_b64);
+  bool uniform_prep = true;
+  for (int i = 1; i < 4; ++i)
+    uniform_prep = uniform_prep && c.prep.a[i] == c.prep.a[0] && c.prep.b[i] == c.prep.b[0];
+  c.pixels.check(c.C, c.prep.nchw != 0, c.rec_h(), c.rec_w(), c.input_b64, uniform_prep);
   if (!c.pixels.wants_ingest_decode()) c.ingest_parse = false;
   return c;
 }

@@ -798,6 +798,45 @@ void bind_host(py::module_& m) {
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"),
         py::arg("max_images") = -1);
+  // ---- typed tensor records (csrc/codec/elemtype.h) ----
+  m.def("elem_bytes", [](const std::string& dtype) {
+    return elem_bytes(elem_type_of(dtype.c_str()));  // (0 for an unknown name)
+  });
+  m.def("typed_to_float_host",
+        [](py::bytes data, const std::string& dtype) {
+          // (float32 [n]: float32(x) of every element, all finite?)
+          const std::string_view s = view(data);
+          const int t = elem_type_of(dtype.c_str());
+          const int E = elem_bytes(t);
+          if (E == 0 || s.size() % (size_t)E != 0)
+            throw std::invalid_argument("typed_to_float_host: dtype / whole elements");
+          py::array_t<float> out((py::ssize_t)(s.size() / (size_t)E));
+          const bool finite = codec::typed_to_float_host(
+              reinterpret_cast<const uint8_t*>(s.data()), s.size() / (size_t)E, t,
+              out.mutable_data());
+          return py::make_tuple(out, finite);
+        },
+        py::arg("data"), py::arg("dtype"));
+  m.def("parse_instances_typed_host",
+        [](py::bytes b, int HS, int WS, int C, const std::string& dtype, int max_images) {
+          // (status, float32 [N, HS*WS*C]: float32(x) of every element, in string order)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          const int t = elem_type_of(dtype.c_str());
+          int n = 0;
+          int st = codec::parse_instances_typed_host(p, s.size(), HS, WS, C, t, nullptr,
+                                                     max_images, &n);
+          if (st != codec::OK) n = 0;
+          const py::ssize_t per =
+              HS > 0 && WS > 0 && C > 0 ? (py::ssize_t)HS * WS * C : (py::ssize_t)0;
+          py::array_t<float> out({(py::ssize_t)n, per});
+          if (st == codec::OK)
+            st = codec::parse_instances_typed_host(p, s.size(), HS, WS, C, t, out.mutable_data(),
+                                                   max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("C"), py::arg("dtype"),
+        py::arg("max_images") = -1);
   m.def("apply_input_prep",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
            bool nchw, std::vector<float> a, std::vector<float> b) {

@@ -281,6 +281,25 @@ PYBIND11_MODULE(_C, m) {
         py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
         py::arg("d_images") = 0, py::arg("format") = "bgr24", py::arg("a") = py::none(),
         py::arg("b") = py::none(), py::arg("nchw") = false);
+  m.def("b64_typed_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& dtype,
+           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b, bool nchw) {
+          // imgs / d_images / a / b / nchw: as b64_decode_instances. dtype: "u16" | "f16" |
+          // "bf16" | "f32" (anything else, "u8" too, reaches the launcher as an unknown type).
+          // Returns the launcher's hipError_t as an int (0 = launched): its refusals are part of
+          // the contract, so they do not throw
+          const auto prep = prep_from("b64_typed_instances", a, b, nchw);
+          return (int)gale::b64_typed_instances(
+              images, static_cast<const gale::B64Image*>(P(imgs)),
+              static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+              static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+              prep ? &*prep : nullptr, gale::elem_type_of(dtype.c_str()));
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("dtype") = "f32", py::arg("a") = py::none(),
+        py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("b64_yuv_pairs", &gale::b64_yuv_pairs);
   m.def("b64_yuv_lds_bytes", &gale::b64_yuv_lds_bytes);
   m.attr("YUV_LDS_BUDGET") = (int)gale::kYuvLdsBudget;

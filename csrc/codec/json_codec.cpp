@@ -575,6 +575,29 @@ int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int 
                            });
 }
 
+int parse_instances_typed_host(const uint8_t* p, size_t n, int HS, int WS, int C, int type,
+                               float* out, int max_images, int* images) {
+  *images = 0;
+  const int64_t B = typed_bytes(HS, WS, C, type);
+  if (B <= 0) return BAD_SHAPE;
+  const size_t per = (size_t)HS * WS * C;
+  // (the elements are judged with out null too: the strings are then decoded into a scratch
+  // image, so a validating call and a decoding call give the same verdict)
+  std::vector<float> scratch(out ? 0 : per);
+  bool finite = true;
+  const int st = parse_b64_records(p, n, B, true, max_images, images,
+                                   [&](const uint8_t* img, size_t e) {
+                                     finite &= typed_to_float_host(
+                                         img, per, type, out ? out + e * per : scratch.data());
+                                   });
+  if (st != OK) return st;
+  if (!finite) {
+    *images = 0;
+    return BAD_NUMBER;
+  }
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "elemtype.h"
 #include "pixfmt.h"
 #include "yuv.h"
 
@@ -146,6 +147,17 @@ int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int for
 // is BAD_SHAPE. out may be null.
 int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                 float* out, int max_images, int* images);
+
+// Full host decoder of typed tensor records (elemtype.h: u16 / f16 / bf16 / f32; u8 decodes as
+// parse_instances_b64_host): the same envelope, element list and verdicts with strings of
+// typed_bytes(HS, WS, C, type) bytes (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3
+// of them '='; a character outside the alphabet in the data part or a non-'=' in the padding is
+// BAD_NUMBER), every string's little-endian elements converted by typed_to_float_host into
+// out[N][HS*WS*C] in string order, then the non-finite verdict: an f16 / bf16 / f32 element with
+// an all-ones exponent is BAD_NUMBER. An unknown type or a non-positive size is BAD_SHAPE. out
+// may be null (the elements are judged all the same).
+int parse_instances_typed_host(const uint8_t* p, size_t n, int HS, int WS, int C, int type,
+                               float* out, int max_images, int* images);
 
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.

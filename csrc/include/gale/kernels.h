@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../codec/elemtype.h"  // InputElem (no HIP: shared with the host codec)
 #include "../../codec/pixfmt.h"  // PackedFormat (no HIP: shared with the host codec)
 #include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
 #include "gale/conv_route.h"  // ConvDesc, the conv launch plans, BottleneckParams (no HIP)
@@ -290,6 +291,26 @@ hipError_t b64_yuv_instances(int images, const B64Image* imgs, const uint8_t* by
 hipError_t b64_packed_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
                                 int WS, int C, float* out, int* status, hipStream_t stream,
                                 const int* d_images, const InputPrep* prep, int format);
+
+// GPU decoder of base64 typed tensor records (input dtypes "u16" / "f16" / "bf16" / "f32",
+// b64_typed.hip): every image's string - L = 4 ceil(B / 3) characters of standard base64,
+// B = HS*WS*C*E bytes of little-endian elements (csrc/codec/elemtype.h), padded like an RGB
+// string - becomes the HS*WS*C floats fmaf(float32(x), a[c], b[c]) of the fp32 NHWC batch tensor.
+// float32(x) is exact (f16 subnormals too, whatever the denormal mode); without a prep the
+// element's float32 bits are stored untouched (f32: -0 and subnormals as sent). imgs, status,
+// d_images, the grid, the read bounds around a string, prep and its nchw are
+// b64_decode_instances'. status[rec] is also set to 2 when an f16 / bf16 / f32 element of one of
+// the record's strings has an all-ones exponent (Inf, NaN), judged on the element as sent; the
+// image is written anyway, within its own slot. The 16-bit types store 16-byte vectors when the
+// image's base is 16-byte aligned and one float per lane otherwise; f32 stores 12 bytes per lane;
+// all contiguous over a wave.
+// hipErrorInvalidValue, before any launch: non-positive HS / WS / C, a null pointer, a type
+// other than ELEM_U16 / ELEM_F16 / ELEM_BF16 / ELEM_F32 (u8 strings are b64_decode_instances'),
+// more than 65535 images, an image of more than 2^30 floats, C > 4 with non-uniform
+// coefficients. images == 0 launches nothing.
+hipError_t b64_typed_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                               int WS, int C, float* out, int* status, hipStream_t stream,
+                               const int* d_images, const InputPrep* prep, int type);
 
 // ---- input resize (resize_crop.hip) ---------------------------------------------------------
 // Bilinear resize (half-pixel centres, no antialiasing) + centre crop of fp32 NHWC images:

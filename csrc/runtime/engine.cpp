@@ -997,6 +997,7 @@ bool Engine::ingest_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
   b64_records_ += b64_accepted;  // (as the host path: records the scan accepted)
   if (cfg_.pixels.kind() == PixelSource::YUV) yuv_records_ += b64_accepted;
   if (cfg_.pixels.kind() == PixelSource::PACKED) packed_records_ += b64_accepted;
+  if (cfg_.pixels.kind() == PixelSource::TYPED) typed_records_ += b64_accepted;
   std::vector<char> corrupt(n, 0);
   for (size_t b = 0; b < f.batches.size(); ++b)
     if (!io.batch_ok[b])
@@ -1137,6 +1138,7 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
         ++b64_records_;
         if (cfg_.pixels.kind() == PixelSource::YUV) ++yuv_records_;
         if (cfg_.pixels.kind() == PixelSource::PACKED) ++packed_records_;
+        if (cfg_.pixels.kind() == PixelSource::TYPED) ++typed_records_;
       }
     }
     if (r.status == codec::OK && r.images > cfg_.max_batch) {
@@ -1816,6 +1818,7 @@ std::map<std::string, double> Engine::stats() const {
   s["b64_records"] = (double)b64_records_;
   s["yuv_records"] = (double)yuv_records_;
   s["packed_records"] = (double)packed_records_;
+  s["typed_records"] = (double)typed_records_;
   s["sparse_fetches"] = (double)sparse_fetches_;
   s["restored_fetches"] = (double)restored_fetches_;
   {

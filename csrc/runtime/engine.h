@@ -158,7 +158,8 @@ struct EngineConfig {
   // ingest_parse, every string decoded into the fetch's image arena - the table step
   bool b64_ingest = false;
   // what the b64 strings carry (csrc/codec/pixel_source.h): interleaved RGB bytes, a YUV 4:2:0
-  // frame of rec_h() x rec_w() or packed pixels, converted to RGB where the strings are decoded.
+  // frame of rec_h() x rec_w() or packed pixels, converted to RGB where the strings are decoded,
+  // or a typed tensor (input_dtype: 16-bit or float elements in the rgb layout).
   // For anything but RGB a GPU ingest runs in its CRC-only form (ingest_parse off): the step
   // decodes from the resident mirror
   PixelSource pixels;
@@ -446,6 +447,7 @@ class Engine {
   std::atomic<int64_t> b64_records_{0};  // records the b64 scan accepted (handed to a decoder)
   std::atomic<int64_t> yuv_records_{0};  // those of them that carry YUV 4:2:0 frames
   std::atomic<int64_t> packed_records_{0};  // those that carry bgr24 / rgba / bgra / gray pixels
+  std::atomic<int64_t> typed_records_{0};   // those that carry u16 / f16 / bf16 / f32 elements
   std::atomic<int64_t> sparse_fetches_{0}, restored_fetches_{0};  // bounce receive (pack_tap.h)
   Histogram h_queue_us_, h_device_us_, h_engine_e2e_us_, h_record_e2e_ms_, h_batch_images_;
   Histogram h_slo_win_us_;  // e2e latency of the SLO controller's current window

@@ -213,10 +213,10 @@ class GpuReplica : public Replica {
   // the steps that copy verdicts back) its status words take the place of the JsonRecord table
   // in the slot's metadata allocation: [B64Image x max_batch][int status x max_batch]. No tile
   // map, no count pass. The strings carry `src` (EngineConfig::pixels): the one decode launch is
-  // the source's (b64_source_instances: b64_yuv_instances or b64_packed_instances for YUV frames
-  // or packed pixels) - same descriptor table, status words and output tensor, strings of
-  // src.bytes(recH_, recW_, C_) bytes; for those two C must be 3 and the prep not nchw (the
-  // launchers refuse otherwise). Before submit()
+  // the source's (b64_source_instances: b64_yuv_instances, b64_packed_instances or
+  // b64_typed_instances for YUV frames, packed pixels or typed tensors) - same descriptor table,
+  // status words and output tensor, strings of src.bytes(recH_, recW_, C_) bytes; for the first
+  // two C must be 3 and the prep not nchw (the launchers refuse otherwise). Before submit()
   void set_input_b64(bool on, const PixelSource& src = PixelSource()) {
     b64_ = on, pixels_ = src;
   }

@@ -214,8 +214,8 @@ def cmd_produce(argv: List[str]) -> int:
 
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
-                           encode_records_packed, encode_records_yuv, synthetic_images,
-                           synthetic_pixels, synthetic_yuv_planes)
+                           encode_records_packed, encode_records_typed, encode_records_yuv,
+                           synthetic_images, synthetic_pixels, synthetic_yuv_planes)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -244,7 +244,17 @@ def cmd_produce(argv: List[str]) -> int:
                          "synthetic pixels of rgb in that byte order (alpha random; gray: their "
                          "first channel alone); needs --encoding b64, the nhwc layout and a "
                          "3-channel model")
+    ap.add_argument("--input-dtype", default="u8", choices=CHOICES["input_dtype"],
+                    help="u16 / f16 / bf16 / f32: the synthetic pixels (--pixels byte: 0..255; "
+                         "unit: floats in [0, 1), not for u16) rounded to that type, little-endian "
+                         "(serve them with --input-dtype); needs --encoding b64 and --pixel-format "
+                         "rgb")
     a = ap.parse_args(argv)
+    typed = a.input_dtype != "u8"
+    if typed and (a.encoding != "b64" or a.pixel_format != "rgb"):
+        ap.error(f"--input-dtype {a.input_dtype} needs --encoding b64 and --pixel-format rgb")
+    if typed and a.input_dtype == "u16" and a.pixels != "byte":
+        ap.error("--input-dtype u16 carries integers: it needs --pixels byte")
     packed = a.pixel_format in ("bgr24", "rgba", "bgra", "gray")
     yuv = a.pixel_format != "rgb" and not packed
     if (yuv or packed) and a.encoding != "b64":
@@ -253,7 +263,7 @@ def cmd_produce(argv: List[str]) -> int:
         ap.error(f"--pixel-format {a.pixel_format} has its own plane order: no --layout nchw")
     if packed and a.layout != "nhwc":
         ap.error(f"--pixel-format {a.pixel_format} has its own byte order: no --layout nchw")
-    if a.encoding == "b64" and a.pixels != "byte" and not yuv:
+    if a.encoding == "b64" and a.pixels != "byte" and not yuv and not typed:
         ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
     try:
@@ -277,6 +287,10 @@ def cmd_produce(argv: List[str]) -> int:
             alpha = np.random.default_rng(a.seed + 1).integers(0, 256, px.shape[:3],
                                                                dtype=np.uint8)
         recs = encode_records_packed(px, a.pixel_format, a.images_per_record, alpha)
+    elif typed:
+        imgs = (synthetic_pixels if a.pixels == "byte" else synthetic_images)(
+            a.images, shape, a.seed)
+        recs = encode_records_typed(imgs, a.input_dtype, a.images_per_record, a.layout)
     elif a.encoding == "b64":
         recs = encode_records_b64(synthetic_pixels(a.images, shape, a.seed),
                                   a.images_per_record, a.layout)

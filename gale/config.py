@@ -49,6 +49,9 @@ CHOICES = {
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
+    # the element type of an rgb b64 string (gale/models/preprocess.py ElemType): one uint8 a
+    # value, or little-endian 16-bit / float elements converted exactly on the GPU
+    "input_dtype": ("u8", "u16", "f16", "bf16", "f32"),
 }
 
 TOP_K_MAX = 64  # --top-k: one winner per lane of the selection kernel's wave
@@ -76,6 +79,11 @@ HELP = {
     "input_yuv_matrix": "bt601 (default) or bt709; only with a YUV --input-pixel-format",
     "input_yuv_range": "limited (default: Y 16..235, chroma 16..240) or full; only with a YUV "
                        "--input-pixel-format",
+    "input_dtype": "the element type of every b64 string: u8 (default) one byte a value; u16 / f16 "
+                   "/ bf16 / f32: HS*WS*C little-endian elements of 2 / 2 / 2 / 4 bytes, converted "
+                   "exactly to float32 on the GPU before --input-scale / --input-mean / "
+                   "--input-std; an Inf or NaN element makes its record bad_number; anything but "
+                   "u8 needs --input-format b64 and --input-pixel-format rgb",
     "input_antialias": "resample with the antialiased (support-scaled triangle) filter of PIL / "
                        "torchvision antialias=True instead of two-tap bilinear; needs an active "
                        "--input-size / --input-resize and a downscale of at most 8x per axis",
@@ -208,6 +216,8 @@ class GaleConfig:
                                        # bgr24 | rgba | bgra | gray: packed pixels
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
+    input_dtype: str = "u8"            # u16 | f16 | bf16 | f32: rgb b64 strings carry little-endian
+                                       # elements of that type (typed tensor records)
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
                                        # the device, strings decoded into the fetch's image
                                        # arena, the table step); needs gpu_ingest, no effect
@@ -305,6 +315,7 @@ class GaleConfig:
         # (ValueError naming --input-size / --input-resize / --input-antialias)
         rs = self.input_resize_plan()
         self._validate_pixel_format(rs)
+        self._validate_dtype()
         if self.top_k != 0:
             from gale.models import get_model
 
@@ -344,6 +355,24 @@ class GaleConfig:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
+
+    def _validate_dtype(self) -> None:
+        """ValueError naming the option for an element type that cannot be served. (Per-channel
+        coefficients with C > 4 are refused by input_prep(), by --input-mean / --input-std.)"""
+        dt = self.input_dtype
+        if dt == "u8":
+            return
+        if self.input_format != "b64":
+            raise ValueError(f"--input-dtype {dt} needs --input-format b64")
+        if self.input_pixel_format != "rgb":
+            raise ValueError(f"--input-dtype {dt} names the elements of an rgb tensor: it needs "
+                             f"--input-pixel-format rgb, not {self.input_pixel_format}")
+
+    def input_elem(self):
+        """The ``ElemType`` of this configuration, None for u8."""
+        from gale.models.preprocess import ElemType
+
+        return ElemType.from_config(self)
 
     def input_yuv(self):
         """The ``YuvConvert`` of this configuration, None for rgb."""
@@ -434,7 +463,8 @@ class GaleConfig:
             **self.input_prep(C).engine_entries(),
             **self.input_resize_plan(H, W).engine_entries(),
             **(self.input_yuv().engine_entries() if self.input_yuv() else {}),
-            **(self.input_unpack().engine_entries() if self.input_unpack() else {}))
+            **(self.input_unpack().engine_entries() if self.input_unpack() else {}),
+            **(self.input_elem().engine_entries() if self.input_elem() else {}))
 
 
 def _pack_fast() -> bool:

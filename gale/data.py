@@ -162,6 +162,30 @@ def encode_records_packed(rgb_u8: np.ndarray, pixel_format: str, images_per_reco
     return out
 
 
+def encode_records_typed(x: np.ndarray, dtype: str, images_per_record: int = 1,
+                         layout: str = "nhwc") -> List[bytes]:
+    """[N, H, W, C] values -> ``{"instances":[{"b64":"..."},...]}`` records of typed tensors
+    (--input-format b64 --input-dtype u8 | u16 | f16 | bf16 | f32): each image's H*W*C elements
+    rounded to ``dtype`` (``gale.models.preprocess.ElemType.to_wire``), little-endian, in
+    standard base64, ordered [H][W][C], or [C][H][W] with ``layout="nchw"``."""
+    from gale.models.preprocess import ElemType
+
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"layout={layout!r}: expected nhwc or nchw")
+    x = np.asarray(x)
+    if x.ndim != 4:
+        raise ValueError("encode_records_typed: [N, H, W, C] images")
+    if layout == "nchw":
+        x = x.transpose(0, 3, 1, 2)
+    wire = ElemType(dtype).to_wire(np.ascontiguousarray(x)).reshape(x.shape[0], -1)
+    out = []
+    for i in range(0, wire.shape[0], images_per_record):
+        elems = [b'{"b64":"' + base64.b64encode(im.tobytes()) + b'"}'
+                 for im in wire[i:i + images_per_record]]
+        out.append(b'{"instances":[' + b",".join(elems) + b"]}")
+    return out
+
+
 def encode_batches(records: Sequence[bytes], records_per_batch: int = 64) -> List[bytes]:
     """Group records into Kafka RecordBatch v2 blobs (for the broker's shared-append preload)."""
     K = native().kafka

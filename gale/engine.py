@@ -99,6 +99,12 @@ class Engine:
             log.info("input pixel format %s: the GPU ingest does not decode (its b64 decode and "
                      "image arena hold RGB strings' images): CRC-only; the batch step decodes "
                      "and converts from the resident mirror", cfg.input_pixel_format)
+        typed = cfg.input_dtype != "u8"  # (typed tensor records: the YUV and packed rule)
+        if typed and ingest and cfg.ingest_parse and not resize.active:
+            log.info("input dtype %s: the GPU ingest does not decode (its b64 decode and image "
+                     "arena hold uint8 strings' images): CRC-only; the batch step decodes and "
+                     "converts from the resident mirror", cfg.input_dtype)
+        yuv = yuv or typed
         d["ingest_parse"] = bool(
             not resize.active and not yuv and (not b64 or cfg.b64_ingest) and cfg.ingest_parse and cfg.gpu_ingest
             and cfg.use_graph and cfg.graph_step and cfg.gpu_encode and cfg.float_format == "jdk19" and cfg.step_launch == "direct"

@@ -29,7 +29,7 @@ KEYS = ("records_in", "records_out", "images_out", "errors", "produce_failures",
         "generation", "assigned_partitions", "eff_max_batch", "eff_max_wait_us",
         "lag_rebalances", "lag_rebalances_skipped", "capacity_rps", "steals",
         "converted_batches", "poison_batches", "poison_records", "poison_unknown_span",
-        "split_records", "b64_records", "yuv_records", "packed_records",
+        "split_records", "b64_records", "yuv_records", "packed_records", "typed_records",
         "resized_images",
         "graph_step_batches", "sparse_fetches", "restored_fetches", "pinned_chunks",
         "pinned_waits", "pinned_heap_budget")

@@ -578,5 +578,113 @@ class PixelUnpack:
         return np.ascontiguousarray(px[..., list(self.offsets)])
 
 
+# the element types of a typed tensor record: name -> (bytes per element, numpy wire dtype)
+ELEM_TYPES = {"u8": (1, "u1"), "u16": (2, "<u2"), "f16": (2, "<f2"), "bf16": (2, "<u2"),
+              "f32": (4, "<f4")}
+
+
+@dataclass(frozen=True)
+class ElemType:
+    """The element type of ``rgb`` b64 strings (``--input-dtype u8 | u16 | f16 | bf16 | f32``).
+
+    A string is the image's ``HS*WS*C`` elements, little-endian, ``E`` bytes each, in ``[H][W][C]``
+    order (``[C][H][W]`` with ``--input-layout nchw``)::
+
+        u8    E = 1   the plain b64 record
+        u16   E = 2   unsigned
+        f16   E = 2   IEEE binary16
+        bf16  E = 2   the top 16 bits of binary32
+        f32   E = 4   binary32
+
+    The model input of element x at channel c is ``fma(float32(x), a[c], b[c])`` with the
+    ``InputPrep`` coefficients; ``float32(x)`` is exact for every type (f16 subnormals included),
+    and with the identity prep the float32 bits are stored as they are. An f16 / bf16 / f32 element
+    whose exponent field is all ones (Inf, NaN) makes its record ``bad_number``, judged on the
+    element as sent. ``codec::typed_to_float_host`` (csrc/codec/elemtype.h) and the
+    ``b64_typed_instances`` kernel give the same bits."""
+
+    dtype: str = "u8"
+
+    def __post_init__(self):
+        if self.dtype not in ELEM_TYPES:
+            raise ValueError(f"input_dtype={self.dtype!r}: expected one of {tuple(ELEM_TYPES)}")
+
+    @classmethod
+    def from_config(cls, cfg) -> Optional["ElemType"]:
+        """The element type of a configuration, None for ``u8``. (GaleConfig.validate refuses the
+        combinations that have none.)"""
+        if cfg.input_dtype == "u8":
+            return None
+        return cls(cfg.input_dtype)
+
+    @property
+    def bytes_per_element(self) -> int:
+        return ELEM_TYPES[self.dtype][0]
+
+    def frame_bytes(self, HS: int, WS: int, C: int) -> int:
+        if HS <= 0 or WS <= 0 or C <= 0:
+            raise ValueError(f"a tensor needs positive sizes, got {HS},{WS},{C}")
+        return HS * WS * C * self.bytes_per_element
+
+    def engine_entries(self) -> Dict[str, Any]:
+        return dict(input_dtype=self.dtype)
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``b64_typed_instances`` binding."""
+        return dict(dtype=self.dtype)
+
+    def to_float(self, data) -> np.ndarray:
+        """uint8 [..., n * E] wire bytes -> float32 [..., n]: ``float32(x)`` of every element."""
+        raw = np.ascontiguousarray(np.asarray(data, np.uint8))
+        E = self.bytes_per_element
+        if raw.shape[-1] % E:
+            raise ValueError(f"expected whole {self.dtype} elements, got {raw.shape[-1]} bytes")
+        v = raw.view(ELEM_TYPES[self.dtype][1])
+        if self.dtype == "bf16":
+            return (v.astype(np.uint32) << 16).view(np.float32)
+        return v.astype(np.float32)
+
+    def nonfinite(self, data) -> np.ndarray:
+        """bool [..., n]: the elements with an all-ones exponent field (never for u8 / u16)."""
+        x = self.to_float(data)
+        if self.dtype in ("u8", "u16"):
+            return np.zeros(x.shape, bool)
+        return ~np.isfinite(x)
+
+    def to_wire(self, x) -> np.ndarray:
+        """float [...] values -> uint8 [..., E] wire bytes of each, rounded to the type (nearest
+        even; the integer types round and saturate): what a client holding ``x`` sends."""
+        x = np.asarray(x, np.float32)
+        if self.dtype in ("u8", "u16"):
+            hi = 255 if self.dtype == "u8" else 65535
+            v = np.clip(np.rint(x), 0, hi).astype(ELEM_TYPES[self.dtype][1])
+        elif self.dtype == "bf16":
+            b = np.ascontiguousarray(x).view(np.uint32).astype(np.uint64)
+            v = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16).astype("<u2")  # (finite x: no NaN care)
+        else:
+            with np.errstate(over="ignore"):
+                v = x.astype(ELEM_TYPES[self.dtype][1])
+        v = np.ascontiguousarray(v)
+        return v.view(np.uint8).reshape(*v.shape, self.bytes_per_element)
+
+    def apply(self, data, HS: int, WS: int, C: int, prep: Optional[InputPrep] = None) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] strings' bytes -> float32 [..., HS, WS, C] model
+        inputs (NHWC, whatever the prep's layout): the exact conversion, then ``prep.apply``."""
+        B = self.frame_bytes(HS, WS, C)
+        raw = np.asarray(data, np.uint8)
+        if raw.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {raw.shape}")
+        x = self.to_float(raw)
+        lead = x.shape[:-1]
+        if prep is not None and prep.nchw:
+            x = np.moveaxis(x.reshape(*lead, C, HS, WS), -3, -1)
+        else:
+            x = x.reshape(*lead, HS, WS, C)
+        x = np.ascontiguousarray(x)
+        if prep is None or prep.identity:
+            return x
+        return prep.apply(x)
+
+
 def prep_or_none(prep: Optional[InputPrep]) -> Optional[InputPrep]:
     return None if prep is None or prep.identity else prep

@@ -434,6 +434,44 @@ def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: t
     return out
 
 
+def b64_typed_instances(staged: torch.Tensor, table: torch.Tensor, shape, out: torch.Tensor,
+                        status: torch.Tensor, elem, images: Optional[int] = None,
+                        d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Decode base64 typed tensor strings (``--input-dtype u16 | f16 | bf16 | f32``) into the fp32
+    NHWC batch tensor ``out`` [slots, HS, WS, C], in place; returns ``out``.
+
+    ``staged`` / ``table`` / ``status`` / ``images`` / ``d_images`` / ``prep``: as
+    ``b64_decode_instances`` (both launch forms, either layout; a record with a bad character or
+    a non-finite element gets status 2). ``shape``: (HS, WS, C); every string is
+    4 * ceil(HS*WS*C*E / 3) characters. ``elem``: a ``gale.models.preprocess.ElemType``. A shape or
+    argument the launcher refuses raises ``ValueError`` before anything is launched."""
+    HS, WS, C = (int(v) for v in shape)
+    _check(staged, torch.uint8, "staged")
+    _check(table, torch.int32, "table")
+    _check(out, torch.float32, "out")
+    _check(status, torch.int32, "status")
+    if table.dim() != 2 or table.shape[1] != native().B64_IMAGE_BYTES // 4:
+        raise ValueError("gale op: table must be int32 [images, 4]")
+    n = table.shape[0] if images is None else int(images)
+    if n > table.shape[0]:
+        raise ValueError("gale op: more images than descriptors")
+    if HS > 0 and WS > 0 and C > 0 and out.numel() % (HS * WS * C) != 0:
+        raise ValueError("gale op: out must hold whole [HS, WS, C] images")
+    if d_images is not None:
+        _check(d_images, torch.int32, "d_images")
+    kw = prep.kernel_kwargs() if prep is not None else {}
+    err = native().b64_typed_instances(n, table.data_ptr(), staged.data_ptr(), HS, WS, C,
+                                       out.data_ptr(), status.data_ptr(), _stream(),
+                                       d_images.data_ptr() if d_images is not None else 0,
+                                       **elem.kernel_kwargs(), **kw)
+    if err == native().HIP_ERROR_INVALID_VALUE:
+        raise ValueError(f"b64_typed_instances: the launcher refused {HS}x{WS}x{C} "
+                         f"{elem.dtype} (images={n})")
+    if err != 0:
+        raise RuntimeError(f"b64_typed_instances: HIP error {err}")
+    return out
+
+
 def ingest_crc_b64(staged: torch.Tensor, shape, arena: Optional[torch.Tensor] = None,
                    table: Optional[torch.Tensor] = None, wg_bad: Optional[torch.Tensor] = None,
                    windows: Optional[torch.Tensor] = None, tables: Optional[torch.Tensor] = None,
