@@ -102,11 +102,12 @@ EngineConfig config_from_dict(const py::dict& d) {
   c.prep.nchw = nchw ? 1 : 0;
   std::string input_format = "json";
   opt(d, "input_format", input_format);
-  if (input_format != "json" && input_format != "b64")
-    throw std::invalid_argument("input_format: json or b64");
-  c.input_b64 = input_format == "b64";
+  if (input_format != "json" && input_format != "b64" && input_format != "raw")
+    throw std::invalid_argument("input_format: json, b64 or raw");
+  const bool input_raw = input_format == "raw";
+  c.input_b64 = input_format == "b64" || input_raw;
   opt(d, "b64_ingest", c.b64_ingest);
-  if (c.b64_ingest && !c.input_b64)
+  if (c.b64_ingest && (!c.input_b64 || input_raw))
     throw std::invalid_argument("b64_ingest needs input_format b64");
   // what the b64 strings carry (gale/models/preprocess.py YuvConvert / PixelUnpack
   // .engine_entries; absent = RGB bytes)
@@ -124,6 +125,7 @@ EngineConfig config_from_dict(const py::dict& d) {
       opt(d, "input_dtype", dt);
       c.pixels = c.pixels.with_elem(dt);
     }
+    if (input_raw) c.pixels = c.pixels.as_raw();
   }
   opt(d, "max_batch", c.max_batch);
   opt(d, "max_wait_us", c.max_wait_us);
@@ -195,6 +197,10 @@ void bind_engine(py::module_& m) {
            py::arg("high_priority") = false, py::arg("step_direct") = false)
       .def("enable_gpu_ingest",
            [](Engine& e, int device, int lanes, int poll_us) {
+             if (e.config().pixels.raw())
+               throw std::invalid_argument("enable_gpu_ingest: input_format raw has no GPU "
+                                           "ingest (the records are converted in the batch "
+                                           "step)");
              if (e.config().input_b64 && !e.config().b64_ingest)
                throw std::invalid_argument("enable_gpu_ingest: input_format b64 needs b64_ingest "
                                            "(without it the records are decoded in the batch "

@@ -837,6 +837,41 @@ void bind_host(py::module_& m) {
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("C"), py::arg("dtype"),
         py::arg("max_images") = -1);
+  // ---- raw binary records: the scan, the splitter and the host twin of raw_instances ----
+  m.def("scan_instances_raw", [](int64_t n, int64_t B) {
+    const codec::Scan sc = codec::scan_instances_raw(n < 0 ? 0 : (size_t)n, B);
+    return py::make_tuple(sc.status, sc.arr_off, sc.arr_len, sc.images);
+  });
+  m.def("split_instances_raw", [](int64_t n, int64_t B, int max_images) -> py::object {
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    if (!codec::split_instances_raw(n < 0 ? 0 : (size_t)n, B, max_images, spans))
+      return py::none();
+    return py::cast(spans);
+  });
+  m.def("parse_instances_raw_host",
+        [](py::bytes b, int HS, int WS, int C, const std::string& dtype,
+           const std::string& format, int max_images) {
+          // (status, float32 [N, HS*WS*C]: the images in record order, packed pixels as RGB)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          const int t = elem_type_of(dtype.c_str());
+          const int f = format == "rgb" ? (int)PACKED_NONE
+                        : packed_format_of(format.c_str()) ? packed_format_of(format.c_str())
+                                                           : -1;
+          int n = 0;
+          int st = codec::parse_instances_raw_host(p, s.size(), HS, WS, C, t, f, nullptr,
+                                                   max_images, &n);
+          if (st != codec::OK) n = 0;
+          const py::ssize_t per =
+              HS > 0 && WS > 0 && C > 0 ? (py::ssize_t)HS * WS * C : (py::ssize_t)0;
+          py::array_t<float> out({(py::ssize_t)n, per});
+          if (st == codec::OK)
+            st = codec::parse_instances_raw_host(p, s.size(), HS, WS, C, t, f,
+                                                 out.mutable_data(), max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("C"), py::arg("dtype") = "u8",
+        py::arg("format") = "rgb", py::arg("max_images") = -1);
   m.def("apply_input_prep",
         [](py::array_t<float, py::array::c_style | py::array::forcecast> x, int H, int W, int C,
            bool nchw, std::vector<float> a, std::vector<float> b) {

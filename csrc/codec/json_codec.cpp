@@ -598,6 +598,65 @@ int parse_instances_typed_host(const uint8_t* p, size_t n, int HS, int WS, int C
   return OK;
 }
 
+Scan scan_instances_raw(size_t n, int64_t B) {
+  Scan s;
+  if (n == 0) {
+    s.status = EMPTY;
+  } else if (B <= 0 || n % (uint64_t)B != 0) {
+    s.status = BAD_SHAPE;
+  } else if (n / (uint64_t)B > ((uint64_t)1 << 30)) {
+    s.status = TOO_LARGE;
+  } else {
+    s.arr_len = (int64_t)n;
+    s.images = (int)(n / (uint64_t)B);
+  }
+  return s;
+}
+
+bool split_instances_raw(size_t n, int64_t B, int max_images,
+                         std::vector<std::pair<uint32_t, uint32_t>>& spans) {
+  spans.clear();
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK || max_images < 1 || n > UINT32_MAX) return false;
+  for (int i = 0; i < s.images; i += max_images) {
+    const int i1 = std::min(s.images, i + max_images);
+    spans.emplace_back((uint32_t)((uint64_t)i * (uint64_t)B),
+                       (uint32_t)((uint64_t)i1 * (uint64_t)B));
+  }
+  return true;
+}
+
+int parse_instances_raw_host(const uint8_t* p, size_t n, int HS, int WS, int C, int type,
+                             int format, float* out, int max_images, int* images) {
+  *images = 0;
+  const bool packed = format != PACKED_NONE;
+  if (packed && (type != ELEM_U8 || C != 3)) return BAD_SHAPE;
+  const int64_t B = packed ? packed_bytes(HS, WS, format) : typed_bytes(HS, WS, C, type);
+  if (B <= 0) return BAD_SHAPE;
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  const size_t per = (size_t)HS * WS * C;
+  const bool judged = type == ELEM_F16 || type == ELEM_BF16 || type == ELEM_F32;
+  if (!out && !judged) {  // (every byte pattern of the integer types is a value)
+    *images = s.images;
+    return OK;
+  }
+  std::vector<float> scratch(out ? 0 : per);
+  bool finite = true;
+  for (int e = 0; e < s.images; ++e) {
+    const uint8_t* img = p + (size_t)e * (size_t)B;
+    float* dst = out ? out + (size_t)e * per : scratch.data();
+    if (packed)
+      packed_to_rgb_host(img, HS, WS, format, nullptr, dst);
+    else
+      finite &= typed_to_float_host(img, per, type, dst);
+  }
+  if (!finite) return BAD_NUMBER;
+  *images = s.images;
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

@@ -159,6 +159,29 @@ int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int 
 int parse_instances_typed_host(const uint8_t* p, size_t n, int HS, int WS, int C, int type,
                                float* out, int max_images, int* images);
 
+// ---- raw binary records (input format "raw") ---------------------------------------------------
+// The record value is N >= 1 images back to back, B bytes each (PixelSource::bytes), no envelope
+// and no separator: nothing of the body is read to count them.
+
+// Status and image count of a value of n bytes: EMPTY (n == 0), BAD_SHAPE (n not a multiple of B,
+// or B <= 0), TOO_LARGE (more than 2^30 images), else OK with arr_off = 0, arr_len = n.
+Scan scan_instances_raw(size_t n, int64_t B);
+
+// A scanned value's byte spans [begin, end) of fragments of at most max_images whole images, for a
+// record with more images than one micro-batch holds: sub-ranges of the value, nothing is copied.
+// false when the value is not whole images or max_images < 1.
+bool split_instances_raw(size_t n, int64_t B, int max_images,
+                         std::vector<std::pair<uint32_t, uint32_t>>& spans);
+
+// Full host decoder, the twin of raw_instances (gale/kernels.h): the scan's verdicts, TOO_LARGE
+// over max_images (>= 0), then every image converted into out[N][HS*WS*C] - format PACKED_NONE:
+// little-endian elements of `type` in record order by typed_to_float_host (ELEM_U8 included);
+// else packed pixels ([HS][WS][3] RGB by packed_to_rgb_host; needs type ELEM_U8 and C == 3). An
+// f16 / bf16 / f32 element with an all-ones exponent is BAD_NUMBER. An unknown type or format or
+// a non-positive size is BAD_SHAPE. out may be null (the elements are judged all the same).
+int parse_instances_raw_host(const uint8_t* p, size_t n, int HS, int WS, int C, int type,
+                             int format, float* out, int max_images, int* images);
+
 // Java Float.toString formatting (what Jackson emits for float[]): shortest digits
 // that round-trip, decimal for 1e-3 <= |v| < 1e7 ("0.125", "3.0"), else "1.0E-5". Returns length.
 int format_float_java(float v, char* out);

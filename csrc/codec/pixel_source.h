@@ -62,6 +62,15 @@ class PixelSource {
     return s;
   }
 
+  // The same source for raw binary records (input_format raw): the value is the images' bytes
+  // themselves, with no base64 and no envelope around them.
+  PixelSource as_raw() const {
+    PixelSource s = *this;
+    s.raw_ = true;
+    return s;
+  }
+  bool raw() const { return raw_; }  // the encoding: raw bytes, else b64 strings
+
   Kind kind() const {
     return packed_format_ ? PACKED : yuv_format_ ? YUV : elem_ != ELEM_U8 ? TYPED : RGB;
   }
@@ -78,12 +87,17 @@ class PixelSource {
   }
 
   // What a topology must look like to carry this source: model channels C, the prep's nchw,
-  // record-side HS x WS, input_format b64. std::invalid_argument otherwise; rgb goes with all,
-  // a typed tensor with everything rgb b64 records go with.
+  // record-side HS x WS, input_format b64 or raw (input_b64: one of the two). A raw source
+  // carries no YUV frame. std::invalid_argument otherwise; rgb goes with all, a typed tensor
+  // with everything rgb b64 records go with.
   // uniform_prep: whether the prep's four coefficient pairs are equal (a typed tensor may have
   // C > 4, which the decoders serve with uniform coefficients only: b64::prep_fits; the Python
   // configuration refuses the same by --input-mean / --input-std).
   void check(int C, bool nchw, int HS, int WS, bool input_b64, bool uniform_prep = true) const {
+    if (raw_ && kind() == YUV)
+      throw std::invalid_argument("input_format raw: no pixel_format i420 / nv12");
+    if (raw_ && kind() == RGB && C > 4 && !uniform_prep)
+      throw std::invalid_argument("input_format raw: per-channel input_a / input_b need C <= 4");
     if (kind() == RGB) return;
     if (kind() == TYPED) {  // (any C, either layout, any size: the rgb rules)
       if (!input_b64)
@@ -105,7 +119,7 @@ class PixelSource {
 
   // The ingest's b64 decode and its image arena hold RGB strings' images: for every other
   // source a GPU ingest runs CRC-only (ingest_parse off) and the step decodes from the mirror.
-  bool wants_ingest_decode() const { return kind() == RGB; }
+  bool wants_ingest_decode() const { return kind() == RGB && !raw_; }
 
   // What a string looks like to the ingest's plan (plan_b64_ingest), which checks it against
   // its record: a YUV frame's string is that of an (HS / 2) x WS x 3 byte image, a packed-pixel
@@ -119,10 +133,15 @@ class PixelSource {
                             : Dims{HS, WS * elem_bytes(elem_), C};
   }
 
-  // The host decode of one b64 record into out[N][HS][WS][C]: the source's public parser
+  // The host decode of one record (b64 or raw, by the encoding) into out[N][HS][WS][C]: the source's public parser
   // (json_codec.h), with its status, image count and floats.
   int parse_host(const uint8_t* p, size_t n, int HS, int WS, int C, float* out, int max_images,
                  int* images) const {
+    if (raw_)
+      return kind() == YUV ? (int)codec::BAD_SHAPE
+                           : codec::parse_instances_raw_host(p, n, HS, WS, C, elem_,
+                                                             packed_format_, out, max_images,
+                                                             images);
     if (kind() == TYPED)
       return codec::parse_instances_typed_host(p, n, HS, WS, C, elem_, out, max_images, images);
     return kind() == PACKED
@@ -139,6 +158,7 @@ class PixelSource {
   YuvCoeffs yuv_;
   int packed_format_ = PACKED_NONE;
   int elem_ = ELEM_U8;
+  bool raw_ = false;
 };
 
 }  // namespace gale

@@ -312,6 +312,26 @@ hipError_t b64_typed_instances(int images, const B64Image* imgs, const uint8_t* 
                                int WS, int C, float* out, int* status, hipStream_t stream,
                                const int* d_images, const InputPrep* prep, int type);
 
+// GPU conversion of raw binary tensor records (input format "raw", raw_convert.hip): every image
+// is B bytes with no text around them - HS*WS*C little-endian elements of type `elem`
+// (csrc/codec/elemtype.h, ELEM_U8 included; [H][W][C], or [C][H][W] with an nchw prep) when
+// packed_format is PACKED_NONE, else HS*WS packed pixels (csrc/codec/pixfmt.h) - and becomes the
+// floats fmaf(float32(x), a[c], b[c]) of the fp32 NHWC batch tensor: the bits the b64 decoders
+// give for the same bytes sent as a b64 string. imgs (off = the byte offset of the image's first
+// byte, any phase), status, d_images and prep are b64_typed_instances' and
+// b64_packed_instances'; status[rec] is set to 2 only for an f16 / bf16 / f32 element with an
+// all-ones exponent (the image is written anyway, within its own slot). Only aligned words that
+// hold a byte of an image are read, and alignment is reckoned on the address (`bytes` itself may
+// be any byte, a slice of a buffer included). 16-byte stores when the image's base is 16-byte aligned, one
+// float per lane otherwise; both contiguous over a wave.
+// hipErrorInvalidValue, before any launch: a null pointer, non-positive HS / WS / C, an unknown
+// type or format, a packed format with a type other than ELEM_U8, with C != 3 or with an nchw
+// prep, more than 65535 images, an image of more than 2^30 floats, C > 4 with non-uniform
+// coefficients. images == 0 launches nothing.
+hipError_t raw_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS, int WS,
+                         int C, float* out, int* status, hipStream_t stream, const int* d_images,
+                         const InputPrep* prep, int elem, int packed_format);
+
 // ---- input resize (resize_crop.hip) ---------------------------------------------------------
 // Bilinear resize (half-pixel centres, no antialiasing) + centre crop of fp32 NHWC images:
 // src [n][HS][WS][C] -> dst [n][H][W][C]. The six tables (device memory; per output row y0 / y1

@@ -1072,8 +1072,10 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
             scan_c = nchw ? rec_w : cfg_.C;
   const bool b64 = cfg_.input_b64;
   auto scan = [&](const uint8_t* p, size_t n) {
-    return b64 ? codec::scan_instances_b64_bytes(p, n, cfg_.rec_bytes())
-               : codec::scan_instances(p, n, scan_h, scan_w, scan_c);
+    // (a raw value is counted by its length alone)
+    return cfg_.pixels.raw() ? codec::scan_instances_raw(n, cfg_.rec_bytes())
+           : b64             ? codec::scan_instances_b64_bytes(p, n, cfg_.rec_bytes())
+                             : codec::scan_instances(p, n, scan_h, scan_w, scan_c);
   };
   if (cfg_.check_crcs && !f.crc_checked) {
     corrupt.assign(f.records.size(), 0);
@@ -1134,7 +1136,9 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       r.arr_len = s.arr_len;
       r.images = s.images;
       if (r.status == codec::OK && fault_hit(parse_error_p_)) r.status = codec::BAD_ENVELOPE;
-      if (b64 && r.status == codec::OK) {
+      if (cfg_.pixels.raw() && r.status == codec::OK) {
+        ++raw_records_;
+      } else if (b64 && r.status == codec::OK) {
         ++b64_records_;
         if (cfg_.pixels.kind() == PixelSource::YUV) ++yuv_records_;
         if (cfg_.pixels.kind() == PixelSource::PACKED) ++packed_records_;
@@ -1672,6 +1676,7 @@ void Engine::emit(InRecord& r, std::string value, bool null_value, kafka::Produc
 
 bool Engine::split_record(InRecord& r, std::vector<InRecord>& good) {
   std::vector<std::pair<uint32_t, uint32_t>> spans;
+  if (cfg_.pixels.raw()) return split_record_raw(r, good);
   const uint8_t* arr = r.value + r.arr_off;
   const bool ok = cfg_.input_b64 ? codec::split_instances_b64_bytes(arr, (size_t)r.arr_len,
                                                                     cfg_.rec_bytes(), spans)
@@ -1709,6 +1714,48 @@ bool Engine::split_record(InRecord& r, std::vector<InRecord>& good) {
     f.arr_off = (int64_t)hl - 1;
     f.arr_len = (int64_t)(e - b) + 2;
     f.images = i1 - i0;
+    f.status = codec::OK;
+    f.partition = r.partition;
+    f.offset = r.offset;
+    f.timestamp_ms = r.timestamp_ms;
+    f.t_fetch_ns = r.t_fetch_ns;
+    f.source = r.source;
+    f.split = sp;
+    f.split_index = k;
+    good.push_back(std::move(f));
+  }
+  ++split_records_;
+  split_fragments_ += parts;
+  return true;
+}
+
+// A raw record over max_batch: its fragments are sub-ranges of the value in the fetch buffer,
+// which they keep alive; nothing is copied.
+bool Engine::split_record_raw(InRecord& r, std::vector<InRecord>& good) {
+  std::vector<std::pair<uint32_t, uint32_t>> spans;
+  const int64_t B = cfg_.rec_bytes();
+  if (!codec::split_instances_raw((size_t)r.len, B, cfg_.max_batch, spans)) return false;
+  const int parts = (int)spans.size();
+  auto sp = std::make_shared<SplitRecord>();
+  sp->parent = r;
+  sp->parent.buf.reset();
+  sp->parent.value = nullptr;
+  sp->parent.dev_value = nullptr;
+  if (r.key && r.key_len >= 0) {
+    sp->key.assign(reinterpret_cast<const char*>(r.key), (size_t)r.key_len);
+    sp->parent.key = reinterpret_cast<const uint8_t*>(sp->key.data());
+  }
+  sp->parts = parts;
+  sp->rows.resize((size_t)parts);
+  for (int k = 0; k < parts; ++k) {
+    InRecord f;
+    f.buf = r.buf;
+    f.pinned = r.pinned;
+    f.value = r.value + spans[(size_t)k].first;
+    f.len = (int32_t)(spans[(size_t)k].second - spans[(size_t)k].first);
+    f.arr_off = 0;
+    f.arr_len = f.len;
+    f.images = (int)(f.len / B);
     f.status = codec::OK;
     f.partition = r.partition;
     f.offset = r.offset;
@@ -1819,6 +1866,7 @@ std::map<std::string, double> Engine::stats() const {
   s["yuv_records"] = (double)yuv_records_;
   s["packed_records"] = (double)packed_records_;
   s["typed_records"] = (double)typed_records_;
+  s["raw_records"] = (double)raw_records_;
   s["sparse_fetches"] = (double)sparse_fetches_;
   s["restored_fetches"] = (double)restored_fetches_;
   {

@@ -153,6 +153,9 @@ struct EngineConfig {
   // values>"} object per image (csrc/codec/json_codec.h) instead of nested number arrays. The
   // host scans with codec::scan_instances_b64 and the replicas decode the strings; a GPU ingest
   // is attached in this mode only with b64_ingest (run()'s counting pass is a number-token pass)
+  // Input format "raw" sets it too, with pixels.raw(): the value is the images' bytes with no
+  // text around them (codec::scan_instances_raw), the step's descriptor table, status words and
+  // decode launch site are the same and the launch is raw_instances. Never with a GPU ingest.
   bool input_b64 = false;
   // input_b64 with a GPU ingest attached (Ingest::run_b64): batch CRCs on the device and, with
   // ingest_parse, every string decoded into the fetch's image arena - the table step
@@ -373,6 +376,7 @@ class Engine {
   // an oversized record -> fragments of <= max_batch images appended to `good` (false: the
   // array could not be split; the record keeps its status for the error policy)
   bool split_record(InRecord& r, std::vector<InRecord>& good);
+  bool split_record_raw(InRecord& r, std::vector<InRecord>& good);
   void fragment_done(const InRecord& frag, std::string rows, int status, kafka::Producer* prod);
   void emit_error(InRecord& r, int status, kafka::Producer* prod);
   void complete_record(const InRecord& r, bool ok);
@@ -448,6 +452,7 @@ class Engine {
   std::atomic<int64_t> yuv_records_{0};  // those of them that carry YUV 4:2:0 frames
   std::atomic<int64_t> packed_records_{0};  // those that carry bgr24 / rgba / bgra / gray pixels
   std::atomic<int64_t> typed_records_{0};   // those that carry u16 / f16 / bf16 / f32 elements
+  std::atomic<int64_t> raw_records_{0};     // records the raw scan accepted (input_format raw)
   std::atomic<int64_t> sparse_fetches_{0}, restored_fetches_{0};  // bounce receive (pack_tap.h)
   Histogram h_queue_us_, h_device_us_, h_engine_e2e_us_, h_record_e2e_ms_, h_batch_images_;
   Histogram h_slo_win_us_;  // e2e latency of the SLO controller's current window

@@ -275,6 +275,13 @@ void GpuReplica::describe(const Batch& b, Slot& s) {
     }
     if (b64_ && !p.preparsed) {
       p.b64_first = (int32_t)s.b64_offs.size();
+      if (pixels_.raw()) {  // image i starts i B bytes into the value: the scan's count says it all
+        const int64_t B = pixels_.bytes(recH_, recW_, C_);
+        const codec::Scan sc = codec::scan_instances_raw((size_t)r.arr_len, B);
+        p.b64_n = sc.status == codec::OK ? sc.images : -1;
+        for (int k = 0; k < sc.images; ++k) s.b64_offs.push_back((uint32_t)((int64_t)k * B));
+        continue;
+      }
       p.b64_n = codec::b64_image_offsets_bytes(r.value + r.arr_off, (size_t)r.arr_len,
                                                pixels_.bytes(recH_, recW_, C_), s.b64_scan)
                     ? (int32_t)s.b64_scan.size()

@@ -11,7 +11,8 @@
     python -m gale broker [--port 9092] [--partitions N]     embedded Kafka-protocol broker
     python -m gale produce <TOPIC> [--images N] [--model M] [--rate R]   synthetic InstObj load
         [--pixels unit|byte] [--layout nhwc|nchw]     raw integer pixels / NCHW-nested records
-        [--encoding json|b64]                         b64: base64 uint8 records (--pixels byte)
+        [--encoding json|b64|raw]                     b64: base64 uint8 records (--pixels byte);
+                                                      raw: the images' bytes, no envelope
         [--size H,W]                                  images of that size (--input-size H,W)
         [--pixel-format rgb|i420|nv12|bgr24|rgba|bgra|gray]
                                                       YUV 4:2:0 frames / packed pixels
@@ -214,7 +215,8 @@ def cmd_produce(argv: List[str]) -> int:
 
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
-                           encode_records_packed, encode_records_typed, encode_records_yuv,
+                           encode_records_packed, encode_records_raw, encode_records_typed,
+                           encode_records_yuv,
                            synthetic_images, synthetic_pixels, synthetic_yuv_planes)
     from gale.models import get_model
 
@@ -233,7 +235,9 @@ def cmd_produce(argv: List[str]) -> int:
                     help="nesting of each record's instances array (nchw: --input-layout nchw)")
     ap.add_argument("--encoding", default="json", choices=CHOICES["input_format"],
                     help="b64: one {\"b64\": ...} object of base64 uint8 pixels per image "
-                         "(--input-format b64); needs --pixels byte")
+                         "(--input-format b64); needs --pixels byte; raw: each record value is "
+                         "its images' bytes back to back (--input-format raw), with the "
+                         "--pixel-format (not i420 / nv12) and --input-dtype choices of b64")
     ap.add_argument("--size", default="", metavar="H,W",
                     help="size of the synthetic images (default: the model's; serve them with "
                          "--input-size H,W)")
@@ -251,20 +255,21 @@ def cmd_produce(argv: List[str]) -> int:
                          "rgb")
     a = ap.parse_args(argv)
     typed = a.input_dtype != "u8"
-    if typed and (a.encoding != "b64" or a.pixel_format != "rgb"):
+    raw = a.encoding == "raw"
+    if typed and (a.encoding not in ("b64", "raw") or a.pixel_format != "rgb"):
         ap.error(f"--input-dtype {a.input_dtype} needs --encoding b64 and --pixel-format rgb")
     if typed and a.input_dtype == "u16" and a.pixels != "byte":
         ap.error("--input-dtype u16 carries integers: it needs --pixels byte")
     packed = a.pixel_format in ("bgr24", "rgba", "bgra", "gray")
     yuv = a.pixel_format != "rgb" and not packed
-    if (yuv or packed) and a.encoding != "b64":
+    if (yuv or packed) and a.encoding != "b64" and not (raw and packed):
         ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64")
     if yuv and a.layout != "nhwc":
         ap.error(f"--pixel-format {a.pixel_format} has its own plane order: no --layout nchw")
     if packed and a.layout != "nhwc":
         ap.error(f"--pixel-format {a.pixel_format} has its own byte order: no --layout nchw")
-    if a.encoding == "b64" and a.pixels != "byte" and not yuv and not typed:
-        ap.error("--encoding b64 carries uint8 pixels: it needs --pixels byte")
+    if a.encoding in ("b64", "raw") and a.pixels != "byte" and not yuv and not typed:
+        ap.error(f"--encoding {a.encoding} carries uint8 pixels: it needs --pixels byte")
     net = get_model(a.model)
     try:
         shape = produce_shape(net.input_shape, a.size)
@@ -286,7 +291,13 @@ def cmd_produce(argv: List[str]) -> int:
         elif a.pixel_format != "bgr24":
             alpha = np.random.default_rng(a.seed + 1).integers(0, 256, px.shape[:3],
                                                                dtype=np.uint8)
-        recs = encode_records_packed(px, a.pixel_format, a.images_per_record, alpha)
+        recs = (encode_records_raw(px, a.images_per_record, pixel_format=a.pixel_format,
+                                   alpha=alpha) if raw
+                else encode_records_packed(px, a.pixel_format, a.images_per_record, alpha))
+    elif raw:
+        imgs = (synthetic_pixels if a.pixels == "byte" else synthetic_images)(
+            a.images, shape, a.seed)
+        recs = encode_records_raw(imgs, a.images_per_record, a.input_dtype, layout=a.layout)
     elif typed:
         imgs = (synthetic_pixels if a.pixels == "byte" else synthetic_images)(
             a.images, shape, a.seed)

@@ -38,9 +38,10 @@ CHOICES = {
     # nesting order of a record's instances array (the model's tensors stay NHWC)
     "input_layout": ("nhwc", "nchw"),
     # what a record's instances array holds: "json" nested number arrays, "b64" one
-    # {"b64": "<base64 of H*W*C uint8 values>"} object per image, decoded on the GPU
-    "input_format": ("json", "b64"),
-    # what a b64 record's bytes are: interleaved RGB, or a YUV 4:2:0 video frame (I420: three
+    # {"b64": "<base64 of H*W*C uint8 values>"} object per image, decoded on the GPU; "raw": the
+    # record value is the images' bytes back to back, no envelope, converted on the GPU
+    "input_format": ("json", "b64", "raw"),
+    # what a b64 or raw record's bytes are (raw: not the YUV formats): interleaved RGB, or a YUV 4:2:0 video frame (I420: three
     # planes; NV12: a Y plane and an interleaved UV plane) converted to RGB on the GPU
     # (gale/models/preprocess.py YuvConvert), or packed pixels (bgr24 / rgba / bgra: the named
     # byte order, alpha ignored; gray: one byte a pixel, replicated) unpacked to RGB on the GPU
@@ -49,7 +50,7 @@ CHOICES = {
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
-    # the element type of an rgb b64 string (gale/models/preprocess.py ElemType): one uint8 a
+    # the element type of an rgb b64 string or raw image (gale/models/preprocess.py ElemType): one uint8 a
     # value, or little-endian 16-bit / float elements converted exactly on the GPU
     "input_dtype": ("u8", "u16", "f16", "bf16", "f32"),
 }
@@ -69,21 +70,23 @@ HELP = {
                     "becomes S, the longer int(S*long/short); default: the model's H,W (plain "
                     "resize, no crop); HR >= H and WR >= W (no padding)",
     "input_pixel_format": "i420 / nv12: every b64 string is a YUV 4:2:0 frame of HS*WS*3/2 bytes "
-                          "(HS,WS even; the model must have 3 channels), converted to RGB on the "
-                          "GPU; bgr24 / rgba / bgra / gray: every b64 string is HS*WS pixels of "
+                          "(HS,WS even; the model must have 3 channels; --input-format b64 "
+                          "only), converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
+                          "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
                           "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
                           "--input-mean / --input-std stay in R,G,B order; all of them need "
-                          "--input-format b64 and the nhwc layout; rgb (default): interleaved RGB "
+                          "--input-format b64 (the packed ones: or raw) and the nhwc layout; rgb "
+                          "(default): interleaved RGB "
                           "bytes",
     "input_yuv_matrix": "bt601 (default) or bt709; only with a YUV --input-pixel-format",
     "input_yuv_range": "limited (default: Y 16..235, chroma 16..240) or full; only with a YUV "
                        "--input-pixel-format",
-    "input_dtype": "the element type of every b64 string: u8 (default) one byte a value; u16 / f16 "
+    "input_dtype": "the element type of every b64 string or raw image: u8 (default) one byte a value; u16 / f16 "
                    "/ bf16 / f32: HS*WS*C little-endian elements of 2 / 2 / 2 / 4 bytes, converted "
                    "exactly to float32 on the GPU before --input-scale / --input-mean / "
                    "--input-std; an Inf or NaN element makes its record bad_number; anything but "
-                   "u8 needs --input-format b64 and --input-pixel-format rgb",
+                   "u8 needs --input-format b64 or raw and --input-pixel-format rgb",
     "input_antialias": "resample with the antialiased (support-scaled triangle) filter of PIL / "
                        "torchvision antialias=True instead of two-tap bilinear; needs an active "
                        "--input-size / --input-resize and a downscale of at most 8x per axis",
@@ -211,13 +214,14 @@ class GaleConfig:
     input_resize: str = ""             # "HR,WR" or "S" (torchvision Resize(S) on HS,WS)
     input_antialias: bool = False      # the antialiased tap filter on both axes (downscale <= 8x)
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
-                                       # ingest only with b64_ingest)
+                                       # ingest only with b64_ingest); raw: the value is the
+                                       # images' bytes, no envelope (never a GPU ingest)
     input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames;
-                                       # bgr24 | rgba | bgra | gray: packed pixels
+                                       # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
-    input_dtype: str = "u8"            # u16 | f16 | bf16 | f32: rgb b64 strings carry little-endian
-                                       # elements of that type (typed tensor records)
+    input_dtype: str = "u8"            # u16 | f16 | bf16 | f32: rgb b64 strings or raw images carry
+                                       # little-endian elements of that type
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
                                        # the device, strings decoded into the fetch's image
                                        # arena, the table step); needs gpu_ingest, no effect
@@ -311,6 +315,9 @@ class GaleConfig:
             raise ValueError("--no-fold-bn (standalone BatchNorm plan) is bf16 / fp32 only")
         if self.b64_ingest and self.input_format != "b64":
             raise ValueError("--b64-ingest needs --input-format b64")
+        if self.input_format == "raw" and self.input_pixel_format in ("i420", "nv12"):
+            raise ValueError(f"--input-pixel-format {self.input_pixel_format} is not served with "
+                             "--input-format raw: YUV frames need --input-format b64")
         self.input_prep()  # (ValueError on a bad scale / mean / std / layout)
         # (ValueError naming --input-size / --input-resize / --input-antialias)
         rs = self.input_resize_plan()
@@ -339,7 +346,7 @@ class GaleConfig:
             return
         from gale.models import get_model
 
-        if self.input_format != "b64":
+        if self.input_format not in ("b64", "raw"):
             raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64")
         if self.input_layout != "nhwc":
             raise ValueError(f"--input-pixel-format {fmt} has its own "
@@ -362,7 +369,7 @@ class GaleConfig:
         dt = self.input_dtype
         if dt == "u8":
             return
-        if self.input_format != "b64":
+        if self.input_format not in ("b64", "raw"):
             raise ValueError(f"--input-dtype {dt} needs --input-format b64")
         if self.input_pixel_format != "rgb":
             raise ValueError(f"--input-dtype {dt} names the elements of an rgb tensor: it needs "

@@ -186,6 +186,32 @@ def encode_records_typed(x: np.ndarray, dtype: str, images_per_record: int = 1,
     return out
 
 
+def encode_records_raw(x: np.ndarray, images_per_record: int = 1, dtype: str = "u8",
+                       pixel_format: str = "rgb", layout: str = "nhwc",
+                       alpha: Optional[np.ndarray] = None) -> List[bytes]:
+    """[N, H, W, C] values -> raw binary records (--input-format raw): each record value is its
+    images' bytes back to back, nothing around them. ``pixel_format`` rgb: the H*W*C elements
+    rounded to ``dtype`` (``ElemType.to_wire``), little-endian, ordered [H][W][C] or [C][H][W]
+    with ``layout="nchw"``; a packed format: uint8 RGB images packed by ``pack_pixels``."""
+    from gale.models.preprocess import ElemType
+
+    if layout not in ("nhwc", "nchw"):
+        raise ValueError(f"layout={layout!r}: expected nhwc or nchw")
+    x = np.asarray(x)
+    if x.ndim != 4:
+        raise ValueError("encode_records_raw: [N, H, W, C] images")
+    if pixel_format != "rgb":
+        if dtype != "u8" or layout != "nhwc":
+            raise ValueError(f"pixel_format={pixel_format!r} carries uint8 pixels in nhwc order")
+        wire = pack_pixels(x, pixel_format, alpha)
+    else:
+        if layout == "nchw":
+            x = x.transpose(0, 3, 1, 2)
+        wire = ElemType(dtype).to_wire(np.ascontiguousarray(x)).reshape(x.shape[0], -1)
+    return [wire[i:i + images_per_record].tobytes()
+            for i in range(0, wire.shape[0], images_per_record)]
+
+
 def encode_batches(records: Sequence[bytes], records_per_batch: int = 64) -> List[bytes]:
     """Group records into Kafka RecordBatch v2 blobs (for the broker's shared-append preload)."""
     K = native().kafka

@@ -62,11 +62,13 @@ class Engine:
         # pinned fetch buffers unless --b64-ingest attaches the GPU ingest's b64 form (batch CRCs
         # on the device, strings decoded into the fetch's image arena); base64 text does not
         # nibble-pack either way
-        b64 = cfg.input_format == "b64"
+        # raw records (--input-format raw) take the same host path and never a GPU ingest
+        raw = cfg.input_format == "raw"
+        b64 = cfg.input_format == "b64" or raw
         ingest = cfg.gpu_ingest and (not b64 or cfg.b64_ingest)
         if b64 and not cfg.b64_ingest and not cfg.stub and (cfg.gpu_ingest or cfg.text_pack):
-            log.info("input_format=b64: GPU ingest and text packing are not used (records are "
-                     "decoded in the batch step)")
+            log.info("input_format=%s: GPU ingest and text packing are not used (records are "
+                     "%s in the batch step)", cfg.input_format, "converted" if raw else "decoded")
         if cfg.b64_ingest and (cfg.stub or not cfg.gpu_ingest):
             log.info("b64_ingest has no effect %s", "with stub replicas" if cfg.stub
                      else "without gpu_ingest")

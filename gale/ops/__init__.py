@@ -472,6 +472,47 @@ def b64_typed_instances(staged: torch.Tensor, table: torch.Tensor, shape, out: t
     return out
 
 
+def raw_instances(staged: torch.Tensor, table: torch.Tensor, shape, out: torch.Tensor,
+                  status: torch.Tensor, dtype: str = "u8", pixel_format: str = "rgb",
+                  images: Optional[int] = None, d_images: Optional[torch.Tensor] = None,
+                  prep=None) -> torch.Tensor:
+    """Convert raw binary images (input format ``raw``) into the fp32 NHWC batch tensor ``out``
+    [slots, HS, WS, C], in place; returns ``out``.
+
+    ``staged``: uint8 bytes holding the images, each ``B`` bytes with no text around them, at any
+    byte offset (``staged`` itself may be a slice at any byte). ``table`` / ``status`` / ``images`` / ``d_images`` / ``prep``: as
+    ``b64_decode_instances`` (both launch forms, either layout; the offset is the image's first
+    byte; only a non-finite element gives status 2). ``shape``: (HS, WS, C). ``dtype``: the
+    element type of the ``rgb`` layout; ``pixel_format``: ``rgb`` or a packed format (``u8``,
+    C = 3, NHWC only). A shape or argument the launcher refuses raises ``ValueError`` before
+    anything is launched."""
+    HS, WS, C = (int(v) for v in shape)
+    _check(staged, torch.uint8, "staged")
+    _check(table, torch.int32, "table")
+    _check(out, torch.float32, "out")
+    _check(status, torch.int32, "status")
+    if table.dim() != 2 or table.shape[1] != native().B64_IMAGE_BYTES // 4:
+        raise ValueError("gale op: table must be int32 [images, 4]")
+    n = table.shape[0] if images is None else int(images)
+    if n > table.shape[0]:
+        raise ValueError("gale op: more images than descriptors")
+    if HS > 0 and WS > 0 and C > 0 and out.numel() % (HS * WS * C) != 0:
+        raise ValueError("gale op: out must hold whole [HS, WS, C] images")
+    if d_images is not None:
+        _check(d_images, torch.int32, "d_images")
+    kw = prep.kernel_kwargs() if prep is not None else {}
+    err = native().raw_instances(n, table.data_ptr(), staged.data_ptr(), HS, WS, C,
+                                 out.data_ptr(), status.data_ptr(), _stream(),
+                                 d_images.data_ptr() if d_images is not None else 0,
+                                 dtype=str(dtype), format=str(pixel_format), **kw)
+    if err == native().HIP_ERROR_INVALID_VALUE:
+        raise ValueError(f"raw_instances: the launcher refused {HS}x{WS}x{C} {dtype} "
+                         f"{pixel_format} (images={n})")
+    if err != 0:
+        raise RuntimeError(f"raw_instances: HIP error {err}")
+    return out
+
+
 def ingest_crc_b64(staged: torch.Tensor, shape, arena: Optional[torch.Tensor] = None,
                    table: Optional[torch.Tensor] = None, wg_bad: Optional[torch.Tensor] = None,
                    windows: Optional[torch.Tensor] = None, tables: Optional[torch.Tensor] = None,
