@@ -40,6 +40,8 @@ $(OBJ)/%.o: csrc/%.cpp $(HDRS)
 # nothing in a kernel bound by its loads and stores; the scalar forms need up to 4 VGPRs fewer
 # on some instantiations (28 at most either way; the bits are the same, fmaf is fused in both)
 $(OBJ)/kernels/raw_convert.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# the 4:2:2 decoders likewise: six independent fmas per macropixel, a kernel bound by its stores
+$(OBJ)/kernels/yuv422.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 gale/_C.so: $(HIP_OBJ) $(CXX_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lz -ldl -pthread \

@@ -563,6 +563,17 @@ int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int for
                            });
 }
 
+int parse_instances_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                const YuvCoeffs& k, float* out, int max_images, int* images) {
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || (WS & 1) || !yuv_is_422(format)) return BAD_SHAPE;
+  const size_t per = (size_t)HS * WS * 3;
+  return parse_b64_records(p, n, yuv422_bytes(HS, WS), out != nullptr, max_images, images,
+                           [&](const uint8_t* frame, size_t e) {
+                             yuv422_to_rgb_host(frame, HS, WS, format, k, nullptr, out + e * per);
+                           });
+}
+
 int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                 float* out, int max_images, int* images) {
   *images = 0;
@@ -653,6 +664,22 @@ int parse_instances_raw_host(const uint8_t* p, size_t n, int HS, int WS, int C, 
       finite &= typed_to_float_host(img, per, type, dst);
   }
   if (!finite) return BAD_NUMBER;
+  *images = s.images;
+  return OK;
+}
+
+int parse_instances_raw_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                    const YuvCoeffs& k, float* out, int max_images, int* images) {
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || (WS & 1) || !yuv_is_422(format)) return BAD_SHAPE;
+  const int64_t B = yuv422_bytes(HS, WS);
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  const size_t per = (size_t)HS * WS * 3;
+  for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
+    yuv422_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, format, k, nullptr,
+                       out + (size_t)e * per);
   *images = s.images;
   return OK;
 }

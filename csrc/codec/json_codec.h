@@ -138,6 +138,20 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
 int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                              const YuvCoeffs& k, float* out, int max_images, int* images);
 
+// Full host decoders of packed YUV 4:2:2 frame records (yuv.h: yuyv422 / uyvy422), b64 and raw.
+// b64: the same envelope, element list and verdicts with strings of yuv422_bytes(HS, WS) bytes
+// (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3 of them '='; a character outside
+// the alphabet in the data part or a non-'=' in the padding is BAD_NUMBER). raw: the value is N
+// frames of B bytes back to back (scan_instances_raw's verdicts, TOO_LARGE over max_images;
+// nothing else can be wrong with one). Every frame is converted by yuv422_to_rgb_host into
+// out[N][HS][WS][3] as (float)RGB - what parse_instances_b64_host gives for the converted image
+// sent as an RGB record. A non-positive size, an odd WS or another format is BAD_SHAPE. out may
+// be null.
+int parse_instances_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                const YuvCoeffs& k, float* out, int max_images, int* images);
+int parse_instances_raw_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                    const YuvCoeffs& k, float* out, int max_images, int* images);
+
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes
 // (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3 of them '='; a character outside

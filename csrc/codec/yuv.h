@@ -11,6 +11,11 @@
 //     B = clamp((cy (Y - yo) + cbu (U - 128)                  + 2^19) >> 20, 0, 255)
 // The coefficients are the exact rationals of the matrix times 2^20, rounded half to even; the
 // largest accumulator magnitude over every (Y, U, V) and table is 573 636 921 < 2^31.
+//
+// Packed 4:2:2 frames (input pixel formats "yuyv422" / "uyvy422"; kernel csrc/kernels/yuv422.hip):
+// a frame of HS x WS pixels (WS even, HS any) is B = 2*HS*WS bytes, [HS][WS/2] macropixels of 4
+// bytes - yuyv422 Y0 U Y1 V, uyvy422 U Y0 V Y1. Pixel (y, x) takes Y[x & 1], U and V of
+// macropixel (y, x >> 1): the horizontal half of the 4:2:0 rule. Same formulas, same tables.
 // No HIP in this header: the sanitizer programs of the host codec include it.
 #pragma once
 #include <stddef.h>
@@ -18,7 +23,9 @@
 
 namespace gale {
 
-enum YuvFormat : int { YUV_NONE = 0, YUV_I420 = 1, YUV_NV12 = 2 };
+enum YuvFormat : int {
+  YUV_NONE = 0, YUV_I420 = 1, YUV_NV12 = 2, YUV_YUYV422 = 3, YUV_UYVY422 = 4
+};
 enum YuvMatrix : int { YUV_BT601 = 0, YUV_BT709 = 1 };
 enum YuvRange : int { YUV_LIMITED = 0, YUV_FULL = 1 };
 
@@ -44,6 +51,15 @@ inline bool yuv_coeffs(int matrix, int range, YuvCoeffs* k) {
 
 // Bytes of one frame (HS, WS even).
 inline int64_t yuv420_bytes(int HS, int WS) { return (int64_t)HS * WS / 2 * 3; }
+
+// Packed 4:2:2: whether `format` is one, the bytes of one frame (WS even), and the byte offsets
+// of Y0 / Y1 / U / V in a macropixel (the host twin and the kernel both take them from here).
+constexpr bool yuv_is_422(int format) { return format == YUV_YUYV422 || format == YUV_UYVY422; }
+inline int64_t yuv422_bytes(int HS, int WS) { return (int64_t)HS * WS * 2; }
+constexpr int yuv422_y0(int format) { return format == YUV_UYVY422 ? 1 : 0; }
+constexpr int yuv422_y1(int format) { return format == YUV_UYVY422 ? 3 : 2; }
+constexpr int yuv422_u(int format) { return format == YUV_UYVY422 ? 0 : 1; }
+constexpr int yuv422_v(int format) { return format == YUV_UYVY422 ? 2 : 3; }
 
 namespace codec {
 
@@ -83,6 +99,29 @@ inline bool yuv420_to_rgb_host(const uint8_t* src, int HS, int WS, int format, c
         if (f32) f32[o + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
       }
     }
+  return true;
+}
+
+// The same for one packed 4:2:2 frame: yuv422_bytes(HS, WS) bytes at src -> [HS][WS][3]. false
+// (nothing written) for a non-positive size, an odd WS or a format that is not a 4:2:2 one.
+inline bool yuv422_to_rgb_host(const uint8_t* src, int HS, int WS, int format, const YuvCoeffs& k,
+                               uint8_t* rgb, float* f32, const float* a = nullptr,
+                               const float* b = nullptr) {
+  if (HS <= 0 || WS <= 0 || (WS & 1) || !yuv_is_422(format)) return false;
+  const size_t nmp = (size_t)HS * WS / 2;
+  for (size_t m = 0; m < nmp; ++m) {
+    const uint8_t* mp = src + 4 * m;
+    const int U = mp[yuv422_u(format)], V = mp[yuv422_v(format)];
+    for (int h = 0; h < 2; ++h) {
+      uint8_t px[3];
+      yuv_pixel_rgb(k, mp[h ? yuv422_y1(format) : yuv422_y0(format)], U, V, px);
+      const size_t o = (2 * m + h) * 3;
+      for (int c = 0; c < 3; ++c) {
+        if (rgb) rgb[o + c] = px[c];
+        if (f32) f32[o + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
+      }
+    }
+  }
   return true;
 }
 

@@ -275,6 +275,37 @@ hipError_t b64_yuv_instances(int images, const B64Image* imgs, const uint8_t* by
                              const int* d_images, const InputPrep* prep, int format,
                              const YuvCoeffs& coeffs, int pairs = 0);
 
+// GPU decoders of packed YUV 4:2:2 video-frame records (input pixel formats "yuyv422" /
+// "uyvy422", yuv422.hip), one for either encoding. A frame is B = 2*HS*WS bytes, [HS][WS/2]
+// macropixels of 4 bytes (csrc/codec/yuv.h: the byte offsets; WS even, HS any), and becomes the
+// HS*WS*3 floats of its RGB image in the fp32 NHWC batch tensor by the integer conversion of
+// yuv.h (format: YUV_YUYV422 or YUV_UYVY422; coeffs: its table, by value in the kernel arguments
+// like prep): the bits b64_decode_instances gives for the converted image sent as an RGB record
+// with the same prep.
+// b64_yuv422_instances: every frame's string is L = 4 ceil(B / 3) characters of standard base64,
+// padded like an RGB string. imgs, status (2 for a character outside the alphabet in the data
+// part or a non-'=' in the padding of one of the record's strings; the frame is written anyway,
+// within its own slot), d_images, the grid and the read bounds around a string are
+// b64_decode_instances'.
+// raw_yuv422_instances: imgs[].off is the byte offset of the frame's first byte, any phase, and
+// `bytes` may be any byte, as for raw_instances: only aligned words that hold a byte of a frame
+// are read. The grid is ceil(HS*WS / 2048) x images. Nothing can be wrong with a frame: status
+// is never written (it must still be given).
+// Both convert every pixel once, in the lane that loaded its macropixel, and re-stage the floats
+// through per-wave LDS: 16-byte stores when the image's base is 16-byte aligned, one float per
+// lane otherwise; both contiguous over a wave. No workgroup barrier, no atomics.
+// hipErrorInvalidValue, before any launch: a null pointer, non-positive HS / WS, odd WS, C != 3,
+// a format other than the two, an nchw prep, more than 65535 images, a frame of more than 2^30
+// floats. images == 0 launches nothing.
+hipError_t b64_yuv422_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                int WS, int C, float* out, int* status, hipStream_t stream,
+                                const int* d_images, const InputPrep* prep, int format,
+                                const YuvCoeffs& coeffs);
+hipError_t raw_yuv422_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                int WS, int C, float* out, int* status, hipStream_t stream,
+                                const int* d_images, const InputPrep* prep, int format,
+                                const YuvCoeffs& coeffs);
+
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard
 // base64, B = HS*WS*P bytes (csrc/codec/pixfmt.h), padded like an RGB string - becomes the

@@ -7,14 +7,21 @@
 namespace gale {
 
 // The decode launch of b64 strings that carry `src` (csrc/codec/pixel_source.h): exactly one of
-// the four b64 launchers of gale/kernels.h, or raw_instances for a raw source, with these
-// arguments. *which (optional): that launcher's name.
+// the b64 launchers of gale/kernels.h, or raw_instances for a raw source (a packed 4:2:2 frame:
+// b64_yuv422_instances or raw_yuv422_instances), with these arguments. *which (optional): that
+// launcher's name.
 inline hipError_t b64_source_instances(int images, const B64Image* imgs, const uint8_t* bytes,
                                        int HS, int WS, int C, float* out, int* status,
                                        hipStream_t stream, const int* d_images,
                                        const InputPrep* prep, const PixelSource& src,
                                        const char** which = nullptr) {
   const PixelSource::Kind k = src.kind();
+  if (src.yuv422()) {
+    if (which) *which = src.raw() ? "raw_yuv422_instances" : "b64_yuv422_instances";
+    return (src.raw() ? raw_yuv422_instances : b64_yuv422_instances)(
+        images, imgs, bytes, HS, WS, C, out, status, stream, d_images, prep, src.yuv_format(),
+        src.yuv());
+  }
   if (src.raw()) {
     if (which) *which = "raw_instances";
     if (k == PixelSource::YUV) return hipErrorInvalidValue;  // (PixelSource::check refuses it)

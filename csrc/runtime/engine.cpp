@@ -1138,6 +1138,7 @@ void Engine::decode_fetch(FetchItem& it, std::vector<InRecord>& good, int lane) 
       if (r.status == codec::OK && fault_hit(parse_error_p_)) r.status = codec::BAD_ENVELOPE;
       if (cfg_.pixels.raw() && r.status == codec::OK) {
         ++raw_records_;
+        if (cfg_.pixels.kind() == PixelSource::YUV) ++yuv_records_;  // (packed 4:2:2 frames)
       } else if (b64 && r.status == codec::OK) {
         ++b64_records_;
         if (cfg_.pixels.kind() == PixelSource::YUV) ++yuv_records_;

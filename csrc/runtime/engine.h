@@ -449,7 +449,7 @@ class Engine {
   std::atomic<int64_t> poison_unknown_span_{0};  // legacy wrapper poison on an estimated span
   std::atomic<int64_t> split_records_{0}, split_fragments_{0};
   std::atomic<int64_t> b64_records_{0};  // records the b64 scan accepted (handed to a decoder)
-  std::atomic<int64_t> yuv_records_{0};  // those of them that carry YUV 4:2:0 frames
+  std::atomic<int64_t> yuv_records_{0};  // records of a YUV topology (4:2:0, packed 4:2:2) the scan accepted
   std::atomic<int64_t> packed_records_{0};  // those that carry bgr24 / rgba / bgra / gray pixels
   std::atomic<int64_t> typed_records_{0};   // those that carry u16 / f16 / bf16 / f32 elements
   std::atomic<int64_t> raw_records_{0};     // records the raw scan accepted (input_format raw)

@@ -14,7 +14,7 @@
         [--encoding json|b64|raw]                     b64: base64 uint8 records (--pixels byte);
                                                       raw: the images' bytes, no envelope
         [--size H,W]                                  images of that size (--input-size H,W)
-        [--pixel-format rgb|i420|nv12|bgr24|rgba|bgra|gray]
+        [--pixel-format rgb|i420|nv12|yuyv422|uyvy422|bgr24|rgba|bgra|gray]
                                                       YUV 4:2:0 frames / packed pixels
                                                       (--encoding b64; --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
@@ -216,8 +216,9 @@ def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
                            encode_records_packed, encode_records_raw, encode_records_typed,
-                           encode_records_yuv,
-                           synthetic_images, synthetic_pixels, synthetic_yuv_planes)
+                           encode_records_yuv, encode_records_yuv422,
+                           synthetic_images, synthetic_pixels, synthetic_yuv422_planes,
+                           synthetic_yuv_planes)
     from gale.models import get_model
 
     ap = argparse.ArgumentParser(prog="python -m gale produce")
@@ -244,7 +245,9 @@ def cmd_produce(argv: List[str]) -> int:
     ap.add_argument("--pixel-format", default="rgb", choices=CHOICES["input_pixel_format"],
                     help="i420 / nv12: synthetic YUV 4:2:0 frames of HS*WS*3/2 bytes (serve them "
                          "with --input-pixel-format); needs --encoding b64, the nhwc layout, a "
-                         "3-channel model and even sizes; bgr24 / rgba / bgra / gray: the "
+                         "3-channel model and even sizes; yuyv422 / uyvy422: synthetic packed "
+                         "YUV 4:2:2 frames of 2*HS*WS bytes; --encoding b64 or raw, the nhwc "
+                         "layout, a 3-channel model and an even width; bgr24 / rgba / bgra / gray: the "
                          "synthetic pixels of rgb in that byte order (alpha random; gray: their "
                          "first channel alone); needs --encoding b64, the nhwc layout and a "
                          "3-channel model")
@@ -261,9 +264,11 @@ def cmd_produce(argv: List[str]) -> int:
     if typed and a.input_dtype == "u16" and a.pixels != "byte":
         ap.error("--input-dtype u16 carries integers: it needs --pixels byte")
     packed = a.pixel_format in ("bgr24", "rgba", "bgra", "gray")
+    yuv422 = a.pixel_format in ("yuyv422", "uyvy422")
     yuv = a.pixel_format != "rgb" and not packed
-    if (yuv or packed) and a.encoding != "b64" and not (raw and packed):
-        ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64")
+    if (yuv or packed) and a.encoding != "b64" and not (raw and (packed or yuv422)):
+        ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64"
+                 + (" or raw" if yuv422 else ""))
     if yuv and a.layout != "nhwc":
         ap.error(f"--pixel-format {a.pixel_format} has its own plane order: no --layout nchw")
     if packed and a.layout != "nhwc":
@@ -275,7 +280,14 @@ def cmd_produce(argv: List[str]) -> int:
         shape = produce_shape(net.input_shape, a.size)
     except ValueError as e:
         ap.error(str(e))
-    if yuv:
+    if yuv422:
+        if shape[2] != 3 or shape[1] % 2:
+            ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and an even width, got "
+                     f"{shape}")
+        recs = encode_records_yuv422(
+            *synthetic_yuv422_planes(a.images, shape[0], shape[1], a.seed), a.pixel_format,
+            a.images_per_record, a.encoding)
+    elif yuv:
         if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
             ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
                      f"{shape}")

@@ -45,8 +45,11 @@ CHOICES = {
     # planes; NV12: a Y plane and an interleaved UV plane) converted to RGB on the GPU
     # (gale/models/preprocess.py YuvConvert), or packed pixels (bgr24 / rgba / bgra: the named
     # byte order, alpha ignored; gray: one byte a pixel, replicated) unpacked to RGB on the GPU
-    # (PixelUnpack). The names are ffmpeg's pix_fmts
-    "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray"),
+    # (PixelUnpack), or a packed YUV 4:2:2 frame (yuyv422: Y0 U Y1 V macropixels; uyvy422:
+    # U Y0 V Y1; b64 or raw) converted to RGB on the GPU (Yuv422Convert). The names are ffmpeg's
+    # pix_fmts
+    "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray", "yuyv422",
+                           "uyvy422"),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -71,7 +74,10 @@ HELP = {
                     "resize, no crop); HR >= H and WR >= W (no padding)",
     "input_pixel_format": "i420 / nv12: every b64 string is a YUV 4:2:0 frame of HS*WS*3/2 bytes "
                           "(HS,WS even; the model must have 3 channels; --input-format b64 "
-                          "only), converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
+                          "only), converted to RGB on the GPU; yuyv422 / uyvy422: every b64 "
+                          "string or raw image is a packed YUV 4:2:2 frame of 2*HS*WS bytes "
+                          "(Y0 U Y1 V / U Y0 V Y1 macropixels; WS even, any HS; a 3-channel "
+                          "model; --input-format b64 or raw), converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
                           "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
                           "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
@@ -216,7 +222,8 @@ class GaleConfig:
     input_format: str = "json"         # b64: base64 uint8 image records (no text packing; GPU
                                        # ingest only with b64_ingest); raw: the value is the
                                        # images' bytes, no envelope (never a GPU ingest)
-    input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames;
+    input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames; yuyv422 |
+                                       # uyvy422: b64 strings / raw images are 4:2:2 frames;
                                        # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
@@ -336,8 +343,9 @@ class GaleConfig:
     def _validate_pixel_format(self, rs) -> None:
         """ValueError naming the option for a YUV or packed pixel format that cannot be served."""
         fmt = self.input_pixel_format
+        yuv422 = fmt in ("yuyv422", "uyvy422")
         yuv = fmt in ("i420", "nv12")
-        if not yuv:
+        if not yuv and not yuv422:
             for k in ("input_yuv_matrix", "input_yuv_range"):
                 if getattr(self, k):
                     raise ValueError(f"--{k.replace('_', '-')} applies to the YUV formats only: "
@@ -347,7 +355,8 @@ class GaleConfig:
         from gale.models import get_model
 
         if self.input_format not in ("b64", "raw"):
-            raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64")
+            raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64"
+                             + (" or raw" if yuv422 else ""))
         if self.input_layout != "nhwc":
             raise ValueError(f"--input-pixel-format {fmt} has its own "
                              f"{'plane' if yuv else 'byte'} order: "
@@ -362,6 +371,10 @@ class GaleConfig:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
+        if yuv422 and rs.WS % 2:
+            opt = "--input-size" if self.input_size else "--input-pixel-format"
+            raise ValueError(f"{opt}: a 4:2:2 frame (--input-pixel-format {fmt}) needs an even "
+                             f"WS, got {rs.HS},{rs.WS}")
 
     def _validate_dtype(self) -> None:
         """ValueError naming the option for an element type that cannot be served. (Per-channel
@@ -382,10 +395,11 @@ class GaleConfig:
         return ElemType.from_config(self)
 
     def input_yuv(self):
-        """The ``YuvConvert`` of this configuration, None for rgb."""
-        from gale.models.preprocess import YuvConvert
+        """The ``YuvConvert`` (4:2:0) or ``Yuv422Convert`` (packed 4:2:2) of this configuration,
+        None for rgb and the packed pixel formats."""
+        from gale.models.preprocess import Yuv422Convert, YuvConvert
 
-        return YuvConvert.from_config(self)
+        return YuvConvert.from_config(self) or Yuv422Convert.from_config(self)
 
     def input_unpack(self):
         """The ``PixelUnpack`` of this configuration, None for rgb and the YUV formats."""

@@ -117,6 +117,57 @@ def synthetic_yuv_planes(n: int, HS: int, WS: int, seed: int = 0):
             rng.integers(0, 256, (n, HS // 2, WS // 2), dtype=np.uint8))
 
 
+def pack_yuv422(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str) -> np.ndarray:
+    """uint8 planes Y [N, HS, WS], U / V [N, HS, WS/2] -> uint8 [N, 2*HS*WS] packed 4:2:2 frames:
+    yuyv422 (``Y0 U Y1 V`` macropixels) or uyvy422 (``U Y0 V Y1``); the inverse of
+    ``gale.models.preprocess.Yuv422Convert.planes``."""
+    from gale.models.preprocess import YUV422_FORMATS
+
+    Y, U, V = (np.asarray(p) for p in (Y, U, V))
+    if any(p.dtype != np.uint8 or p.ndim != 3 for p in (Y, U, V)):
+        raise ValueError("pack_yuv422: uint8 [N, rows, cols] planes")
+    N, HS, WS = Y.shape
+    if WS % 2 or U.shape != (N, HS, WS // 2) or V.shape != U.shape:
+        raise ValueError(f"pack_yuv422: Y {Y.shape} needs an even width and U, V of "
+                         f"{(N, HS, WS // 2)}, got {U.shape}, {V.shape}")
+    if pixel_format not in YUV422_FORMATS:
+        raise ValueError(f"pixel_format={pixel_format!r}: expected yuyv422 or uyvy422")
+    y0, y1, u, v = YUV422_FORMATS[pixel_format]
+    mp = np.empty((N, HS, WS // 2, 4), np.uint8)
+    mp[..., y0], mp[..., y1], mp[..., u], mp[..., v] = Y[..., 0::2], Y[..., 1::2], U, V
+    return mp.reshape(N, -1)
+
+
+def encode_records_yuv422(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str,
+                          images_per_record: int = 1, encoding: str = "b64") -> List[bytes]:
+    """uint8 planes (``pack_yuv422``) -> records of packed 4:2:2 frames (--input-pixel-format
+    yuyv422 | uyvy422). ``encoding`` b64: ``{"instances":[{"b64":"..."},...]}`` with each
+    frame's 2*HS*WS bytes in standard base64, '=' padded; raw: each record value is its frames'
+    bytes back to back (--input-format raw)."""
+    if encoding not in ("b64", "raw"):
+        raise ValueError(f"encoding={encoding!r}: expected b64 or raw")
+    frames = pack_yuv422(Y, U, V, pixel_format)
+    out = []
+    for i in range(0, frames.shape[0], images_per_record):
+        part = frames[i:i + images_per_record]
+        if encoding == "raw":
+            out.append(part.tobytes())
+        else:
+            elems = [b'{"b64":"' + base64.b64encode(fr.tobytes()) + b'"}' for fr in part]
+            out.append(b'{"instances":[' + b",".join(elems) + b"]}")
+    return out
+
+
+def synthetic_yuv422_planes(n: int, HS: int, WS: int, seed: int = 0):
+    """Deterministic uint8 planes (Y [n, HS, WS], U, V [n, HS, WS/2]) of synthetic frames."""
+    if WS % 2:
+        raise ValueError(f"a 4:2:2 frame needs an even width, got {HS},{WS}")
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 256, (n, HS, WS), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS, WS // 2), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS, WS // 2), dtype=np.uint8))
+
+
 def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
                 alpha: Optional[np.ndarray] = None) -> np.ndarray:
     """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of

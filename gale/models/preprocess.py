@@ -432,14 +432,15 @@ class YuvConvert:
     1, 1). ``codec::yuv420_to_rgb_host`` (csrc/codec/yuv.h, which holds them as literals) and the
     ``b64_yuv_instances`` kernel give the same bits. There is no pre-clamp of ``Y - yo``."""
 
+    FORMATS = PIXEL_FORMATS[1:]  # (the formats of this layout; Yuv422Convert has its own)
     format: str = "i420"
     matrix: str = "bt601"
     range: str = "limited"
 
     def __post_init__(self):
-        if self.format not in PIXEL_FORMATS[1:]:
+        if self.format not in self.FORMATS:
             raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
-                             f"{PIXEL_FORMATS[1:]} for a YUV conversion")
+                             f"{self.FORMATS} for a YUV conversion")
         if self.matrix not in YUV_MATRICES:
             raise ValueError(f"input_yuv_matrix={self.matrix!r}: expected one of {YUV_MATRICES}")
         if self.range not in YUV_RANGES:
@@ -449,7 +450,7 @@ class YuvConvert:
     def from_config(cls, cfg) -> Optional["YuvConvert"]:
         """The conversion of a configuration, None for ``rgb``. (GaleConfig.validate refuses the
         combinations that have none.)"""
-        if cfg.input_pixel_format not in PIXEL_FORMATS[1:]:  # (rgb, or a PixelUnpack format)
+        if cfg.input_pixel_format not in cls.FORMATS:  # (rgb, or another class's format)
             return None
         return cls(cfg.input_pixel_format, cfg.input_yuv_matrix or "bt601",
                    cfg.input_yuv_range or "limited")
@@ -506,6 +507,55 @@ class YuvConvert:
         Y, U, V = self.planes(frame, HS, WS)
         up = lambda c: np.repeat(np.repeat(c, 2, axis=-2), 2, axis=-1)  # noqa: E731
         acc = self.accumulators(Y, up(U), up(V))
+        assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
+        return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
+
+
+# the packed 4:2:2 formats: name -> byte offset in a macropixel of (Y0, Y1, U, V)
+YUV422_FORMATS = {"yuyv422": (0, 2, 1, 3), "uyvy422": (1, 3, 0, 2)}
+
+
+@dataclass(frozen=True)
+class Yuv422Convert(YuvConvert):
+    """Packed YUV 4:2:2 frames (``--input-pixel-format yuyv422 | uyvy422``) to RGB: the integer
+    conversion of ``YuvConvert`` - same formulas, coefficient tables, ``yo``, no pre-clamp - on
+    another frame layout.
+
+    A frame of HS x WS pixels (WS even, HS any) is ``B = 2*HS*WS`` bytes, ``[HS][WS/2]``
+    macropixels of 4 bytes: yuyv422 ``Y0 U Y1 V``, uyvy422 ``U Y0 V Y1``. Pixel (y, x) takes
+    ``Y[x & 1]``, ``U`` and ``V`` of macropixel ``(y, x >> 1)``: the horizontal half of the 4:2:0
+    rule (nearest chroma, no siting filter). ``codec::yuv422_to_rgb_host`` (csrc/codec/yuv.h) and
+    the ``b64_yuv422_instances`` / ``raw_yuv422_instances`` kernels give the same bits."""
+
+    FORMATS = tuple(YUV422_FORMATS)
+    format: str = "yuyv422"
+
+    @staticmethod
+    def frame_bytes(HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or WS % 2:
+            raise ValueError(f"a 4:2:2 frame needs positive sizes and an even WS, got {HS},{WS}")
+        return HS * WS * 2
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``b64_yuv422_instances`` / ``raw_yuv422_instances``
+        bindings."""
+        return dict(format=self.format, coeffs=[*self.coeffs(), self.yo])
+
+    def planes(self, frame, HS: int, WS: int):
+        """uint8 [..., B] frames -> (Y [..., HS, WS], U, V [..., HS, WS/2])."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        mp = f.reshape(*f.shape[:-1], HS, WS // 2, 4)
+        y0, y1, u, v = YUV422_FORMATS[self.format]
+        Y = np.stack([mp[..., y0], mp[..., y1]], axis=-1).reshape(*f.shape[:-1], HS, WS)
+        return Y, mp[..., u], mp[..., v]
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint8 [..., HS, WS, 3] RGB."""
+        Y, U, V = self.planes(frame, HS, WS)
+        acc = self.accumulators(Y, np.repeat(U, 2, axis=-1), np.repeat(V, 2, axis=-1))
         assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
         return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
 

@@ -396,6 +396,59 @@ def b64_yuv_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torc
     return out
 
 
+def _yuv422_instances(name, staged, table, size, out, status, yuv, images, d_images, prep):
+    HS, WS = (int(v) for v in size)
+    _check(staged, torch.uint8, "staged")
+    _check(table, torch.int32, "table")
+    _check(out, torch.float32, "out")
+    _check(status, torch.int32, "status")
+    if table.dim() != 2 or table.shape[1] != native().B64_IMAGE_BYTES // 4:
+        raise ValueError("gale op: table must be int32 [images, 4]")
+    n = table.shape[0] if images is None else int(images)
+    if n > table.shape[0]:
+        raise ValueError("gale op: more images than descriptors")
+    if HS > 0 and WS > 0 and out.numel() % (HS * WS * 3) != 0:
+        raise ValueError("gale op: out must hold whole [HS, WS, 3] images")
+    if d_images is not None:
+        _check(d_images, torch.int32, "d_images")
+    kw = prep.kernel_kwargs() if prep is not None else {}
+    err = getattr(native(), name)(n, table.data_ptr(), staged.data_ptr(), HS, WS, 3,
+                                  out.data_ptr(), status.data_ptr(), _stream(),
+                                  d_images.data_ptr() if d_images is not None else 0,
+                                  **yuv.kernel_kwargs(), **kw)
+    if err == native().HIP_ERROR_INVALID_VALUE:
+        raise ValueError(f"{name}: the launcher refused {HS}x{WS} {yuv.format} (images={n})")
+    if err != 0:
+        raise RuntimeError(f"{name}: HIP error {err}")
+    return out
+
+
+def b64_yuv422_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                         status: torch.Tensor, yuv, images: Optional[int] = None,
+                         d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Decode base64 packed YUV 4:2:2 frame strings (``--input-pixel-format yuyv422 | uyvy422``)
+    into the fp32 NHWC batch tensor ``out`` [slots, HS, WS, 3] as RGB, in place; returns ``out``.
+
+    ``staged`` / ``table`` / ``status`` / ``images`` / ``d_images`` / ``prep``: as
+    ``b64_decode_instances`` (both launch forms). ``size``: (HS, WS), WS even; every string is
+    4 * ceil(2*HS*WS / 3) characters. ``yuv``: a ``gale.models.preprocess.Yuv422Convert`` (format
+    and coefficient table). A shape or argument the launcher refuses raises ``ValueError`` before
+    anything is launched."""
+    return _yuv422_instances("b64_yuv422_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep)
+
+
+def raw_yuv422_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                         status: torch.Tensor, yuv, images: Optional[int] = None,
+                         d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Convert raw packed YUV 4:2:2 frames (input format ``raw``) into ``out``, as
+    ``b64_yuv422_instances``: ``staged`` holds the frames, 2*HS*WS bytes each with no text around
+    them, at any byte offset (``staged`` itself may be a slice at any byte), and a descriptor's
+    offset is the frame's first byte. ``status`` is never written."""
+    return _yuv422_instances("raw_yuv422_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
