@@ -47,6 +47,10 @@ int yuv422_format_of(const std::string& name) {
   return name == "yuyv422" ? YUV_YUYV422 : name == "uyvy422" ? YUV_UYVY422 : YUV_NONE;
 }
 
+int yuvp_format_of(const std::string& name) {
+  return name == "yuv422p" ? YUV_YUV422P : name == "yuv444p" ? YUV_YUV444P : YUV_NONE;
+}
+
 py::object opt_bytes(const uint8_t* base, int64_t off, int32_t len) {
   if (len < 0) return py::none();
   return py::bytes(reinterpret_cast<const char*>(base + off), (size_t)len);
@@ -800,6 +804,60 @@ void bind_host(py::module_& m) {
           k.cbu = coeffs[4], k.yo = coeffs[5];
           const auto parse = raw ? codec::parse_instances_raw_yuv422_host
                                  : codec::parse_instances_yuv422_host;
+          int n = 0;
+          int st = parse(p, s.size(), HS, WS, fmt, k, nullptr, max_images, &n);
+          if (st != codec::OK) n = 0;
+          py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
+                                  (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
+          if (st == codec::OK)
+            st = parse(p, s.size(), HS, WS, fmt, k, out.mutable_data(), max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("raw") = false, py::arg("max_images") = -1);
+  // ---- planar YUV 4:2:2 / 4:4:4 frames (csrc/codec/yuv.h: yuv422p / yuv444p) ----
+  m.def("yuvp_bytes", [](int HS, int WS, const std::string& format) {
+    return yuvp_bytes(HS, WS, yuvp_format_of(format));
+  });
+  m.def("yuvp_to_rgb_host",
+        [](py::bytes frame, int HS, int WS, const std::string& format,
+           std::vector<int32_t> coeffs, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b) {
+          // one frame -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep (3+ values)
+          const std::string_view s = view(frame);
+          if (coeffs.size() != 6 || (a && a->size() < 3) || (b && b->size() < 3) ||
+              bool(a) != bool(b))
+            throw std::invalid_argument("yuvp_to_rgb_host: coeffs (6), a / b (>= 3 each)");
+          const int fmt = yuvp_format_of(format);
+          if (fmt == YUV_NONE || HS <= 0 || WS <= 0 || (yuvp_shift(fmt) && (WS & 1)) ||
+              (int64_t)s.size() != yuvp_bytes(HS, WS, fmt))
+            throw std::invalid_argument("yuvp_to_rgb_host: format / size / byte count");
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          codec::yuvp_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, fmt, k,
+                                  rgb.mutable_data(), f32.mutable_data(),
+                                  a ? a->data() : nullptr, b ? b->data() : nullptr);
+          return py::make_tuple(rgb, f32);
+        },
+        py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("parse_instances_yuvp_host",
+        [](py::bytes b, int HS, int WS, const std::string& format, std::vector<int32_t> coeffs,
+           bool raw, int max_images) {
+          // (status, float32 [N, HS, WS, 3]: (float)RGB of every frame); raw: the value is the
+          // frames' bytes, else a b64 record
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          if (coeffs.size() != 6) throw std::invalid_argument("parse_instances_yuvp_host: coeffs");
+          const int fmt = yuvp_format_of(format);
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          const auto parse = raw ? codec::parse_instances_raw_yuvp_host
+                                 : codec::parse_instances_yuvp_host;
           int n = 0;
           int st = parse(p, s.size(), HS, WS, fmt, k, nullptr, max_images, &n);
           if (st != codec::OK) n = 0;

@@ -297,6 +297,39 @@ PYBIND11_MODULE(_C, m) {
               std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
           py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
   }
+  // The planar 4:2:2 / 4:4:4 decoders (yuv_planar.hip), one for either encoding: the arguments of
+  // the packed 4:2:2 pair above with format "yuv422p" | "yuv444p"
+  for (const bool raw : {false, true}) {
+    const char* name = raw ? "raw_yuvp_instances" : "b64_yuvp_instances";
+    m.def(name,
+          [raw, name](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C,
+                      uintptr_t out, uintptr_t status, uintptr_t stream, uintptr_t d_images,
+                      const std::string& format, std::vector<int32_t> coeffs,
+                      std::optional<std::vector<float>> a, std::optional<std::vector<float>> b,
+                      bool nchw) {
+            const auto prep = prep_from(name, a, b, nchw);
+            if (coeffs.size() != 6)
+              throw std::invalid_argument(std::string(name) +
+                                          ": coeffs takes (cy, crv, cgu, cgv, cbu, yo)");
+            gale::YuvCoeffs k;
+            k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+            k.cbu = coeffs[4], k.yo = coeffs[5];
+            const int fmt = format == "yuv422p"   ? (int)gale::YUV_YUV422P
+                            : format == "yuv444p" ? (int)gale::YUV_YUV444P
+                                                  : (int)gale::YUV_NONE;
+            return (int)(raw ? gale::raw_yuvp_instances : gale::b64_yuvp_instances)(
+                images, static_cast<const gale::B64Image*>(P(imgs)),
+                static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+                static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+                prep ? &*prep : nullptr, fmt, k);
+          },
+          py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+          py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+          py::arg("d_images") = 0, py::arg("format") = "yuv444p",
+          py::arg("coeffs") =
+              std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
+          py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
+  }
   m.def("b64_packed_instances",
         [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
            uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,

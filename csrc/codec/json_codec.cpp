@@ -574,6 +574,18 @@ int parse_instances_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int 
                            });
 }
 
+int parse_instances_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                              const YuvCoeffs& k, float* out, int max_images, int* images) {
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || !yuv_is_planar(format) || (yuvp_shift(format) && (WS & 1)))
+    return BAD_SHAPE;
+  const size_t per = (size_t)HS * WS * 3;
+  return parse_b64_records(p, n, yuvp_bytes(HS, WS, format), out != nullptr, max_images, images,
+                           [&](const uint8_t* frame, size_t e) {
+                             yuvp_to_rgb_host(frame, HS, WS, format, k, nullptr, out + e * per);
+                           });
+}
+
 int parse_instances_packed_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                 float* out, int max_images, int* images) {
   *images = 0;
@@ -680,6 +692,23 @@ int parse_instances_raw_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, 
   for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
     yuv422_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, format, k, nullptr,
                        out + (size_t)e * per);
+  *images = s.images;
+  return OK;
+}
+
+int parse_instances_raw_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                  const YuvCoeffs& k, float* out, int max_images, int* images) {
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || !yuv_is_planar(format) || (yuvp_shift(format) && (WS & 1)))
+    return BAD_SHAPE;
+  const int64_t B = yuvp_bytes(HS, WS, format);
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  const size_t per = (size_t)HS * WS * 3;
+  for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
+    yuvp_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, format, k, nullptr,
+                     out + (size_t)e * per);
   *images = s.images;
   return OK;
 }

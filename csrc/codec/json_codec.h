@@ -152,6 +152,14 @@ int parse_instances_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int 
 int parse_instances_raw_yuv422_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                     const YuvCoeffs& k, float* out, int max_images, int* images);
 
+// The same pair for planar YUV 4:2:2 / 4:4:4 frame records (yuv.h: yuv422p / yuv444p): strings
+// or raw frames of yuvp_bytes(HS, WS, format) bytes, converted by yuvp_to_rgb_host. A
+// non-positive size, an odd WS with yuv422p or another format is BAD_SHAPE.
+int parse_instances_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                              const YuvCoeffs& k, float* out, int max_images, int* images);
+int parse_instances_raw_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                  const YuvCoeffs& k, float* out, int max_images, int* images);
+
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes
 // (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3 of them '='; a character outside

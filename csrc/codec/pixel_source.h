@@ -1,5 +1,5 @@
 // What the b64 strings of a topology carry (engine keys pixel_format and input_dtype):
-// interleaved RGB bytes, a YUV 4:2:0 or packed 4:2:2 frame (yuv.h), packed pixels (pixfmt.h) or a typed tensor
+// interleaved RGB bytes, a YUV 4:2:0, packed 4:2:2 or planar 4:2:2 / 4:4:4 frame (yuv.h), packed pixels (pixfmt.h) or a typed tensor
 // (elemtype.h: the rgb layout with 16-bit or float elements). PixelSource is the one holder of
 // {yuv format, YuvCoeffs, packed format, element type} and of the rules about them: the configuration names,
 // the bytes of a string, what a topology may combine them with, what the ingest sees and which
@@ -30,8 +30,8 @@ class PixelSource {
 
   PixelSource() = default;  // rgb
 
-  // From the configuration names: pixel_format rgb | i420 | nv12 | yuyv422 | uyvy422 | bgr24 |
-  // rgba | bgra | gray;
+  // From the configuration names: pixel_format rgb | i420 | nv12 | yuyv422 | uyvy422 | yuv422p |
+  // yuv444p | bgr24 | rgba | bgra | gray;
   // yuv_matrix bt601 | bt709 and yuv_range limited | full, null where the configuration does not
   // name one (bt601, limited; naming one with a packed format is refused).
   static PixelSource from_names(const std::string& pixel_format, const std::string* yuv_matrix,
@@ -42,6 +42,8 @@ class PixelSource {
       s.yuv_format_ = pixel_format == "i420" ? (int)YUV_I420 : (int)YUV_NV12;
     else if (pixel_format == "yuyv422" || pixel_format == "uyvy422")
       s.yuv_format_ = pixel_format == "yuyv422" ? (int)YUV_YUYV422 : (int)YUV_UYVY422;
+    else if (pixel_format == "yuv422p" || pixel_format == "yuv444p")
+      s.yuv_format_ = pixel_format == "yuv422p" ? (int)YUV_YUV422P : (int)YUV_YUV444P;
     else if (pixel_format != "rgb" && !s.packed_format_)
       throw std::invalid_argument("pixel_format: rgb, i420, nv12, bgr24, rgba, bgra or gray");
     if (s.packed_format_ && (yuv_matrix || yuv_range))
@@ -79,6 +81,7 @@ class PixelSource {
   }
   int yuv_format() const { return yuv_format_; }        // YuvFormat (YUV_NONE unless YUV)
   bool yuv422() const { return yuv_is_422(yuv_format_); }  // a packed 4:2:2 frame (kind YUV)
+  bool planar() const { return yuv_is_planar(yuv_format_); }  // a planar 4:2:2 / 4:4:4 frame (YUV)
   const YuvCoeffs& yuv() const { return yuv_; }
   int packed_format() const { return packed_format_; }  // PackedFormat (PACKED_NONE unless PACKED)
   int elem() const { return elem_; }                    // InputElem (ELEM_U8 unless TYPED)
@@ -87,6 +90,7 @@ class PixelSource {
   int64_t bytes(int HS, int WS, int C) const {
     return kind() == PACKED ? packed_bytes(HS, WS, packed_format_)
            : yuv422()       ? yuv422_bytes(HS, WS)
+           : planar()       ? yuvp_bytes(HS, WS, yuv_format_)
            : kind() == YUV  ? yuv420_bytes(HS, WS)
                             : (int64_t)HS * WS * C * elem_bytes(elem_);
   }
@@ -94,13 +98,13 @@ class PixelSource {
   // What a topology must look like to carry this source: model channels C, the prep's nchw,
   // record-side HS x WS, input_format b64 or raw (input_b64: one of the two). A raw source
   // carries no YUV 4:2:0 frame; a packed 4:2:2 frame goes with either encoding, any HS and an
-  // even WS. std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
+  // even WS, and so does a planar frame (yuv444p: any WS). std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
   // rgb b64 records go with.
   // uniform_prep: whether the prep's four coefficient pairs are equal (a typed tensor may have
   // C > 4, which the decoders serve with uniform coefficients only: b64::prep_fits; the Python
   // configuration refuses the same by --input-mean / --input-std).
   void check(int C, bool nchw, int HS, int WS, bool input_b64, bool uniform_prep = true) const {
-    if (raw_ && kind() == YUV && !yuv422())
+    if (raw_ && kind() == YUV && !yuv422() && !planar())
       throw std::invalid_argument("input_format raw: no pixel_format i420 / nv12");
     if (raw_ && kind() == RGB && C > 4 && !uniform_prep)
       throw std::invalid_argument("input_format raw: per-channel input_a / input_b need C <= 4");
@@ -115,13 +119,16 @@ class PixelSource {
       return;
     }
     const std::string what = yuv422()        ? "pixel_format yuyv422 / uyvy422"
+                             : planar()      ? "pixel_format yuv422p / yuv444p"
                              : kind() == YUV ? "pixel_format i420 / nv12"
                                              : "pixel_format bgr24 / rgba / bgra / gray";
     if (!input_b64) throw std::invalid_argument(what + " needs input_format b64");
     if (nchw) throw std::invalid_argument(what + ": no nchw layout");
     if (C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
     if (yuv422() && (WS & 1)) throw std::invalid_argument(what + " needs an even record-side W");
-    if (kind() == YUV && !yuv422() && ((HS | WS) & 1))
+    if (yuv_format_ == YUV_YUV422P && (WS & 1))
+      throw std::invalid_argument("pixel_format yuv422p needs an even record-side W");
+    if (kind() == YUV && !yuv422() && !planar() && ((HS | WS) & 1))
       throw std::invalid_argument(what + " needs even record-side H, W");
   }
 
@@ -131,7 +138,8 @@ class PixelSource {
 
   // What a string looks like to the ingest's plan (plan_b64_ingest), which checks it against
   // its record: a YUV 4:2:0 frame's string is that of an (HS / 2) x WS x 3 byte image, a packed
-  // 4:2:2 frame's that of an HS x WS x 2 one, a packed-pixel
+  // 4:2:2 frame's that of an HS x WS x 2 one, a planar frame's that of an HS x WS x 2 (yuv422p)
+  // or x 3 (yuv444p) one, a packed-pixel
   // string that of an HS x WS x P one, a typed tensor's string that of an HS x (WS E) x C one -
   // the element size widens a row, not the channel count, because the ingest's launcher applies
   // the C > 4 coefficient rule to the C it is given even when it decodes nothing.
@@ -139,6 +147,7 @@ class PixelSource {
   Dims ingest_dims(int HS, int WS, int C) const {
     return kind() == PACKED ? Dims{HS, WS, packed_bpp(packed_format_)}
            : yuv422()       ? Dims{HS, WS, 2}
+           : planar()       ? Dims{HS, WS, 3 - yuvp_shift(yuv_format_)}
            : kind() == YUV  ? Dims{HS / 2, WS, 3}
                             : Dims{HS, WS * elem_bytes(elem_), C};
   }
@@ -152,6 +161,11 @@ class PixelSource {
                                                            max_images, images)
                   : codec::parse_instances_yuv422_host(p, n, HS, WS, yuv_format_, yuv_, out,
                                                        max_images, images);
+    if (planar())
+      return raw_ ? codec::parse_instances_raw_yuvp_host(p, n, HS, WS, yuv_format_, yuv_, out,
+                                                         max_images, images)
+                  : codec::parse_instances_yuvp_host(p, n, HS, WS, yuv_format_, yuv_, out,
+                                                     max_images, images);
     if (raw_)
       return kind() == YUV ? (int)codec::BAD_SHAPE
                            : codec::parse_instances_raw_host(p, n, HS, WS, C, elem_,

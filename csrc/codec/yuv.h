@@ -16,6 +16,12 @@
 // a frame of HS x WS pixels (WS even, HS any) is B = 2*HS*WS bytes, [HS][WS/2] macropixels of 4
 // bytes - yuyv422 Y0 U Y1 V, uyvy422 U Y0 V Y1. Pixel (y, x) takes Y[x & 1], U and V of
 // macropixel (y, x >> 1): the horizontal half of the 4:2:0 rule. Same formulas, same tables.
+//
+// Planar 4:2:2 / 4:4:4 frames (input pixel formats "yuv422p" / "yuv444p", what a JPEG decoder
+// hands back; kernel csrc/kernels/yuv_planar.hip): with s = 1 (4:2:2, WS even) or 0 (4:4:4, any
+// WS), any HS, a frame is Y[HS][WS], U[HS][WS >> s], V[HS][WS >> s], B = HS*WS + 2 (HS*WS >> s)
+// bytes. Pixel (y, x) takes Y[y][x], U[y][x >> s], V[y][x >> s]; with the linear pixel index
+// p = y WS + x that is Y[p], U[p >> s], V[p >> s] of three byte streams. Same formulas and tables.
 // No HIP in this header: the sanitizer programs of the host codec include it.
 #pragma once
 #include <stddef.h>
@@ -24,7 +30,8 @@
 namespace gale {
 
 enum YuvFormat : int {
-  YUV_NONE = 0, YUV_I420 = 1, YUV_NV12 = 2, YUV_YUYV422 = 3, YUV_UYVY422 = 4
+  YUV_NONE = 0, YUV_I420 = 1, YUV_NV12 = 2, YUV_YUYV422 = 3, YUV_UYVY422 = 4,
+  YUV_YUV422P = 5, YUV_YUV444P = 6
 };
 enum YuvMatrix : int { YUV_BT601 = 0, YUV_BT709 = 1 };
 enum YuvRange : int { YUV_LIMITED = 0, YUV_FULL = 1 };
@@ -60,6 +67,15 @@ constexpr int yuv422_y0(int format) { return format == YUV_UYVY422 ? 1 : 0; }
 constexpr int yuv422_y1(int format) { return format == YUV_UYVY422 ? 3 : 2; }
 constexpr int yuv422_u(int format) { return format == YUV_UYVY422 ? 0 : 1; }
 constexpr int yuv422_v(int format) { return format == YUV_UYVY422 ? 2 : 3; }
+
+// Planar 4:2:2 / 4:4:4: whether `format` is one, its horizontal chroma shift s, and the bytes of
+// one frame (WS even for 4:2:2).
+constexpr bool yuv_is_planar(int format) { return format == YUV_YUV422P || format == YUV_YUV444P; }
+constexpr int yuvp_shift(int format) { return format == YUV_YUV422P ? 1 : 0; }
+inline int64_t yuvp_bytes(int HS, int WS, int format) {
+  const int64_t hw = (int64_t)HS * WS;
+  return hw + 2 * (hw >> yuvp_shift(format));
+}
 
 namespace codec {
 
@@ -120,6 +136,28 @@ inline bool yuv422_to_rgb_host(const uint8_t* src, int HS, int WS, int format, c
         if (rgb) rgb[o + c] = px[c];
         if (f32) f32[o + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
       }
+    }
+  }
+  return true;
+}
+
+// The same for one planar 4:2:2 / 4:4:4 frame: yuvp_bytes(HS, WS, format) bytes at src ->
+// [HS][WS][3]. false (nothing written) for a non-positive size, an odd WS with 4:2:2 or a format
+// that is not a planar one.
+inline bool yuvp_to_rgb_host(const uint8_t* src, int HS, int WS, int format, const YuvCoeffs& k,
+                             uint8_t* rgb, float* f32, const float* a = nullptr,
+                             const float* b = nullptr) {
+  if (HS <= 0 || WS <= 0 || !yuv_is_planar(format)) return false;
+  const int s = yuvp_shift(format);
+  if (s && (WS & 1)) return false;
+  const size_t hw = (size_t)HS * WS;
+  const uint8_t *const up = src + hw, *const vp = up + (hw >> s);
+  for (size_t p = 0; p < hw; ++p) {  // (WS even with s = 1: the chroma index of pixel p is p >> 1)
+    uint8_t px[3];
+    yuv_pixel_rgb(k, src[p], up[p >> s], vp[p >> s], px);
+    for (int c = 0; c < 3; ++c) {
+      if (rgb) rgb[3 * p + c] = px[c];
+      if (f32) f32[3 * p + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
     }
   }
   return true;

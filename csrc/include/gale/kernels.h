@@ -306,6 +306,36 @@ hipError_t raw_yuv422_instances(int images, const B64Image* imgs, const uint8_t*
                                 const int* d_images, const InputPrep* prep, int format,
                                 const YuvCoeffs& coeffs);
 
+// GPU decoders of planar YUV 4:2:2 / 4:4:4 frame records (input pixel formats "yuv422p" /
+// "yuv444p", yuv_planar.hip), one for either encoding, with the arguments, descriptor table and
+// status words of the yuv422 launchers. With s = 1 (YUV_YUV422P, WS even) or 0 (YUV_YUV444P, any
+// WS) and any HS, a frame is the three byte streams Y[HS*WS], U[HS*WS >> s], V[HS*WS >> s] back
+// to back, B = HS*WS + 2 (HS*WS >> s) bytes; pixel p = y WS + x takes Y[p], U[p >> s], V[p >> s]
+// and becomes three floats of the fp32 NHWC batch tensor by the integer conversion of yuv.h: the
+// bits b64_decode_instances gives for the converted image sent as an RGB record with this prep.
+// b64_yuvp_instances: every frame's string is L = 4 ceil(B / 3) characters of standard base64,
+// padded like an RGB string; every character of it is judged (status 2 as for yuv422, the frame
+// written anyway). Reads stay within the aligned 16-byte words that hold a character of the
+// string.
+// raw_yuvp_instances: imgs[].off is the byte offset of the frame's first byte, any phase, and
+// `bytes` may be any byte: only aligned dwords that hold a byte of a frame are read. status is
+// never written (it must still be given).
+// The grid of both is ceil(HS*WS / 3072) x images. A lane converts a run of 12 (4:4:4) or 24
+// (4:2:2) consecutive pixels once and the floats are re-staged through per-wave LDS: 16-byte
+// stores when the image's base is 16-byte aligned, one float per lane otherwise, contiguous over
+// a wave. No workgroup barrier, no atomics.
+// hipErrorInvalidValue, before any launch: a null pointer, non-positive HS / WS, odd WS with
+// 4:2:2, C != 3, a format other than the two, an nchw prep, more than 65535 images, a frame of
+// more than 2^30 floats. images == 0 launches nothing.
+hipError_t b64_yuvp_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                              int WS, int C, float* out, int* status, hipStream_t stream,
+                              const int* d_images, const InputPrep* prep, int format,
+                              const YuvCoeffs& coeffs);
+hipError_t raw_yuvp_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                              int WS, int C, float* out, int* status, hipStream_t stream,
+                              const int* d_images, const InputPrep* prep, int format,
+                              const YuvCoeffs& coeffs);
+
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard
 // base64, B = HS*WS*P bytes (csrc/codec/pixfmt.h), padded like an RGB string - becomes the

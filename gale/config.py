@@ -46,10 +46,11 @@ CHOICES = {
     # (gale/models/preprocess.py YuvConvert), or packed pixels (bgr24 / rgba / bgra: the named
     # byte order, alpha ignored; gray: one byte a pixel, replicated) unpacked to RGB on the GPU
     # (PixelUnpack), or a packed YUV 4:2:2 frame (yuyv422: Y0 U Y1 V macropixels; uyvy422:
-    # U Y0 V Y1; b64 or raw) converted to RGB on the GPU (Yuv422Convert). The names are ffmpeg's
-    # pix_fmts
+    # U Y0 V Y1; b64 or raw) converted to RGB on the GPU (Yuv422Convert), or a planar YUV 4:2:2 /
+    # 4:4:4 frame (yuv422p / yuv444p: Y, U, V planes with full-height chroma, what a JPEG decoder
+    # hands back; b64 or raw; YuvPlanarConvert). The names are ffmpeg's pix_fmts
     "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray", "yuyv422",
-                           "uyvy422"),
+                           "uyvy422", "yuv422p", "yuv444p"),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -77,7 +78,11 @@ HELP = {
                           "only), converted to RGB on the GPU; yuyv422 / uyvy422: every b64 "
                           "string or raw image is a packed YUV 4:2:2 frame of 2*HS*WS bytes "
                           "(Y0 U Y1 V / U Y0 V Y1 macropixels; WS even, any HS; a 3-channel "
-                          "model; --input-format b64 or raw), converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
+                          "model; --input-format b64 or raw), converted to RGB on the GPU; "
+                          "yuv422p / yuv444p: every b64 string or raw image is a planar frame, "
+                          "Y[HS][WS] then U and V of [HS][WS/2] (yuv422p: 2*HS*WS bytes, WS "
+                          "even) or [HS][WS] (yuv444p: 3*HS*WS bytes, any size); a 3-channel "
+                          "model; --input-format b64 or raw; converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
                           "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
                           "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
@@ -224,6 +229,7 @@ class GaleConfig:
                                        # images' bytes, no envelope (never a GPU ingest)
     input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames; yuyv422 |
                                        # uyvy422: b64 strings / raw images are 4:2:2 frames;
+                                       # yuv422p | yuv444p: planar 4:2:2 / 4:4:4 frames;
                                        # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
@@ -343,7 +349,8 @@ class GaleConfig:
     def _validate_pixel_format(self, rs) -> None:
         """ValueError naming the option for a YUV or packed pixel format that cannot be served."""
         fmt = self.input_pixel_format
-        yuv422 = fmt in ("yuyv422", "uyvy422")
+        planar = fmt in ("yuv422p", "yuv444p")
+        yuv422 = fmt in ("yuyv422", "uyvy422") or planar  # (either encoding, any HS)
         yuv = fmt in ("i420", "nv12")
         if not yuv and not yuv422:
             for k in ("input_yuv_matrix", "input_yuv_range"):
@@ -359,7 +366,7 @@ class GaleConfig:
                              + (" or raw" if yuv422 else ""))
         if self.input_layout != "nhwc":
             raise ValueError(f"--input-pixel-format {fmt} has its own "
-                             f"{'plane' if yuv else 'byte'} order: "
+                             f"{'plane' if yuv or planar else 'byte'} order: "
                              "--input-layout nchw does not apply")
         C = get_model(self.model).input_shape[2]
         if C != 3:
@@ -371,7 +378,7 @@ class GaleConfig:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
-        if yuv422 and rs.WS % 2:
+        if yuv422 and fmt != "yuv444p" and rs.WS % 2:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:2 frame (--input-pixel-format {fmt}) needs an even "
                              f"WS, got {rs.HS},{rs.WS}")
@@ -395,11 +402,12 @@ class GaleConfig:
         return ElemType.from_config(self)
 
     def input_yuv(self):
-        """The ``YuvConvert`` (4:2:0) or ``Yuv422Convert`` (packed 4:2:2) of this configuration,
-        None for rgb and the packed pixel formats."""
-        from gale.models.preprocess import Yuv422Convert, YuvConvert
+        """The ``YuvConvert`` (4:2:0), ``Yuv422Convert`` (packed 4:2:2) or ``YuvPlanarConvert``
+        (planar 4:2:2 / 4:4:4) of this configuration, None for rgb and the packed pixel formats."""
+        from gale.models.preprocess import Yuv422Convert, YuvConvert, YuvPlanarConvert
 
-        return YuvConvert.from_config(self) or Yuv422Convert.from_config(self)
+        return (YuvConvert.from_config(self) or Yuv422Convert.from_config(self)
+                or YuvPlanarConvert.from_config(self))
 
     def input_unpack(self):
         """The ``PixelUnpack`` of this configuration, None for rgb and the YUV formats."""

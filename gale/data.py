@@ -168,6 +168,56 @@ def synthetic_yuv422_planes(n: int, HS: int, WS: int, seed: int = 0):
             rng.integers(0, 256, (n, HS, WS // 2), dtype=np.uint8))
 
 
+def pack_yuvp(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str) -> np.ndarray:
+    """uint8 planes Y [N, HS, WS], U / V [N, HS, WS >> s] -> uint8 [N, B] planar frames (Y, U, V
+    planes back to back): yuv422p (s = 1, WS even) or yuv444p (s = 0)."""
+    from gale.models.preprocess import YUVP_FORMATS
+
+    Y, U, V = (np.asarray(p) for p in (Y, U, V))
+    if any(p.dtype != np.uint8 or p.ndim != 3 for p in (Y, U, V)):
+        raise ValueError("pack_yuvp: uint8 [N, rows, cols] planes")
+    if pixel_format not in YUVP_FORMATS:
+        raise ValueError(f"pixel_format={pixel_format!r}: expected yuv422p or yuv444p")
+    s = YUVP_FORMATS[pixel_format]
+    N, HS, WS = Y.shape
+    if WS % (1 << s) or U.shape != (N, HS, WS >> s) or V.shape != U.shape:
+        raise ValueError(f"pack_yuvp: {pixel_format} with Y {Y.shape} needs "
+                         f"{'an even width and ' if s else ''}U, V of {(N, HS, WS >> s)}, got "
+                         f"{U.shape}, {V.shape}")
+    return np.ascontiguousarray(np.concatenate([p.reshape(N, -1) for p in (Y, U, V)], axis=1))
+
+
+def encode_records_yuvp(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str,
+                        images_per_record: int = 1, encoding: str = "b64") -> List[bytes]:
+    """uint8 planes (``pack_yuvp``) -> records of planar 4:2:2 / 4:4:4 frames
+    (--input-pixel-format yuv422p | yuv444p). ``encoding`` b64:
+    ``{"instances":[{"b64":"..."},...]}`` with each frame's bytes in standard base64, '=' padded;
+    raw: each record value is its frames' bytes back to back (--input-format raw)."""
+    if encoding not in ("b64", "raw"):
+        raise ValueError(f"encoding={encoding!r}: expected b64 or raw")
+    frames = pack_yuvp(Y, U, V, pixel_format)
+    out = []
+    for i in range(0, frames.shape[0], images_per_record):
+        part = frames[i:i + images_per_record]
+        if encoding == "raw":
+            out.append(part.tobytes())
+        else:
+            elems = [b'{"b64":"' + base64.b64encode(fr.tobytes()) + b'"}' for fr in part]
+            out.append(b'{"instances":[' + b",".join(elems) + b"]}")
+    return out
+
+
+def synthetic_yuvp_planes(n: int, HS: int, WS: int, pixel_format: str, seed: int = 0):
+    """Deterministic uint8 planes (Y [n, HS, WS], U, V [n, HS, WS >> s]) of synthetic frames."""
+    s = 1 if pixel_format == "yuv422p" else 0
+    if WS % (1 << s):
+        raise ValueError(f"a 4:2:2 frame needs an even width, got {HS},{WS}")
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 256, (n, HS, WS), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS, WS >> s), dtype=np.uint8),
+            rng.integers(0, 256, (n, HS, WS >> s), dtype=np.uint8))
+
+
 def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
                 alpha: Optional[np.ndarray] = None) -> np.ndarray:
     """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of

@@ -560,6 +560,58 @@ class Yuv422Convert(YuvConvert):
         return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
 
 
+# the planar 4:2:2 / 4:4:4 formats: name -> horizontal chroma shift s
+YUVP_FORMATS = {"yuv422p": 1, "yuv444p": 0}
+
+
+@dataclass(frozen=True)
+class YuvPlanarConvert(YuvConvert):
+    """Planar YUV 4:2:2 / 4:4:4 frames (``--input-pixel-format yuv422p | yuv444p``, what a JPEG
+    decoder hands back) to RGB: the integer conversion of ``YuvConvert`` - same formulas,
+    coefficient tables, ``yo``, no pre-clamp - on another frame layout.
+
+    With s = 1 (yuv422p, WS even) or 0 (yuv444p, any WS) and any HS, a frame is ``Y[HS][WS]``,
+    ``U[HS][WS >> s]``, ``V[HS][WS >> s]``, ``B = HS*WS + 2*(HS*WS >> s)`` bytes. Pixel (y, x)
+    takes ``Y[y][x]``, ``U[y][x >> s]``, ``V[y][x >> s]`` (nearest chroma, no siting filter).
+    ``codec::yuvp_to_rgb_host`` (csrc/codec/yuv.h) and the ``b64_yuvp_instances`` /
+    ``raw_yuvp_instances`` kernels give the same bits."""
+
+    FORMATS = tuple(YUVP_FORMATS)
+    format: str = "yuv444p"
+
+    @property
+    def shift(self) -> int:
+        return YUVP_FORMATS[self.format]
+
+    def frame_bytes(self, HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or WS % (1 << self.shift):
+            raise ValueError(f"a {self.format} frame needs positive sizes"
+                             f"{' and an even WS' if self.shift else ''}, got {HS},{WS}")
+        return HS * WS + 2 * (HS * (WS >> self.shift))
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``b64_yuvp_instances`` / ``raw_yuvp_instances`` bindings."""
+        return dict(format=self.format, coeffs=[*self.coeffs(), self.yo])
+
+    def planes(self, frame, HS: int, WS: int):
+        """uint8 [..., B] frames -> (Y [..., HS, WS], U, V [..., HS, WS >> s])."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        lead, hw, wc = f.shape[:-1], HS * WS, WS >> self.shift
+        return (f[..., :hw].reshape(*lead, HS, WS), f[..., hw:hw + HS * wc].reshape(*lead, HS, wc),
+                f[..., hw + HS * wc:].reshape(*lead, HS, wc))
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint8 [..., HS, WS, 3] RGB."""
+        Y, U, V = self.planes(frame, HS, WS)
+        up = lambda c: np.repeat(c, 1 << self.shift, axis=-1)  # noqa: E731
+        acc = self.accumulators(Y, up(U), up(V))
+        assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
+        return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
+
+
 # the packed formats: name -> (bytes per pixel, byte offset in a pixel of R, G, B)
 PACKED_FORMATS = {"bgr24": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)),
                   "gray": (1, (0, 0, 0))}

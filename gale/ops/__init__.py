@@ -449,6 +449,30 @@ def raw_yuv422_instances(staged: torch.Tensor, table: torch.Tensor, size, out: t
                              images, d_images, prep)
 
 
+def b64_yuvp_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                       status: torch.Tensor, yuv, images: Optional[int] = None,
+                       d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Decode base64 planar YUV 4:2:2 / 4:4:4 frame strings (``--input-pixel-format yuv422p |
+    yuv444p``) into the fp32 NHWC batch tensor ``out`` [slots, HS, WS, 3] as RGB, in place;
+    returns ``out``. Arguments as ``b64_yuv422_instances``; ``yuv``: a
+    ``gale.models.preprocess.YuvPlanarConvert``; every string is 4 * ceil(B / 3) characters,
+    B = HS*WS + 2*(HS*WS >> s). There is no CPU path: a shape or argument the launcher refuses
+    raises ``ValueError`` before anything is launched."""
+    return _yuv422_instances("b64_yuvp_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep)
+
+
+def raw_yuvp_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                       status: torch.Tensor, yuv, images: Optional[int] = None,
+                       d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Convert raw planar YUV 4:2:2 / 4:4:4 frames (input format ``raw``) into ``out``, as
+    ``b64_yuvp_instances``: ``staged`` holds the frames, B bytes each with no text around them, at
+    any byte offset (``staged`` itself may be a slice at any byte), and a descriptor's offset is
+    the frame's first byte. ``status`` is never written."""
+    return _yuv422_instances("raw_yuvp_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
