@@ -44,6 +44,8 @@ $(OBJ)/kernels/raw_convert.o: HIP_FLAGS += -Xclang -target-feature -Xclang -pack
 $(OBJ)/kernels/yuv422.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # and the planar 4:2:2 / 4:4:4 decoders: 36 independent fmas per 12 pixels, bound by its stores
 $(OBJ)/kernels/yuv_planar.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# and the 10-bit 4:2:0 decoder: 24 independent multiplies and fmas per row of a block
+$(OBJ)/kernels/yuv420_hi.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 gale/_C.so: $(HIP_OBJ) $(CXX_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lz -ldl -pthread \
@@ -105,6 +107,16 @@ build/asan/yuvp_check: csrc/tests/yuvp_check.cpp csrc/codec/json_codec.cpp \
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/yuvp_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# the 10-bit 4:2:0 host codec (csrc/tests/yuv10_check.cpp): the conversion twin, the raw parser,
+# the splitter and PixelSource's rules for p010le / yuv420p10le on mutated and truncated records;
+# codec only, no engine, no HIP call
+build/asan/yuv10_check: csrc/tests/yuv10_check.cpp csrc/codec/json_codec.cpp \
+                        csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/yuv10_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
 # the packed-pixel host codec (csrc/tests/pixfmt_check.cpp): the unpack twin, the record decoder
 # and the byte-count forms of the scan / offsets / splitter on mutated and truncated records;

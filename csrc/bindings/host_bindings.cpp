@@ -51,6 +51,10 @@ int yuvp_format_of(const std::string& name) {
   return name == "yuv422p" ? YUV_YUV422P : name == "yuv444p" ? YUV_YUV444P : YUV_NONE;
 }
 
+int yuv10_format_of(const std::string& name) {
+  return name == "p010le" ? YUV_P010LE : name == "yuv420p10le" ? YUV_YUV420P10LE : YUV_NONE;
+}
+
 py::object opt_bytes(const uint8_t* base, int64_t off, int32_t len) {
   if (len < 0) return py::none();
   return py::bytes(reinterpret_cast<const char*>(base + off), (size_t)len);
@@ -869,6 +873,66 @@ void bind_host(py::module_& m) {
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
         py::arg("raw") = false, py::arg("max_images") = -1);
+  // ---- 10-bit YUV 4:2:0 frames (csrc/codec/yuv.h: p010le / yuv420p10le, raw records) ----
+  m.def("yuv420p10_bytes", [](int HS, int WS) { return yuv420p10_bytes(HS, WS); });
+  m.def("yuv10_coeffs", [](const std::string& matrix, const std::string& range) {
+    // (cy, crv, cgu, cgv, cbu, yo): the 2^18 literals of csrc/codec/yuv.h
+    YuvCoeffs k;
+    const int mi = matrix == "bt601" ? 0 : matrix == "bt709" ? 1 : -1;
+    const int ri = range == "limited" ? 0 : range == "full" ? 1 : -1;
+    if (!yuv10_coeffs(mi, ri, &k)) throw std::invalid_argument("yuv10_coeffs: matrix / range");
+    return py::make_tuple(k.cy, k.crv, k.cgu, k.cgv, k.cbu, k.yo);
+  });
+  m.def("yuv420p10_to_rgb_host",
+        [](py::bytes frame, int HS, int WS, const std::string& format,
+           std::vector<int32_t> coeffs, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b) {
+          // one frame -> (uint16 [HS, WS, 3] quarter steps, float32 [HS, WS, 3]); a / b: the prep
+          const std::string_view s = view(frame);
+          if (coeffs.size() != 6 || (a && a->size() < 3) || (b && b->size() < 3) ||
+              bool(a) != bool(b))
+            throw std::invalid_argument("yuv420p10_to_rgb_host: coeffs (6), a / b (>= 3 each)");
+          const int fmt = yuv10_format_of(format);
+          if (fmt == YUV_NONE || HS <= 0 || WS <= 0 || ((HS | WS) & 1) ||
+              (int64_t)s.size() != yuv420p10_bytes(HS, WS))
+            throw std::invalid_argument("yuv420p10_to_rgb_host: format / size / byte count");
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          py::array_t<uint16_t> q({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          codec::yuv420p10_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, fmt, k,
+                                       q.mutable_data(), f32.mutable_data(),
+                                       a ? a->data() : nullptr, b ? b->data() : nullptr);
+          return py::make_tuple(q, f32);
+        },
+        py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("parse_instances_raw_yuv420p10_host",
+        [](py::bytes b, int HS, int WS, const std::string& format, std::vector<int32_t> coeffs,
+           int max_images) {
+          // (status, float32 [N, HS, WS, 3]: (float)q * 0.25f of every frame of the raw value)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          if (coeffs.size() != 6)
+            throw std::invalid_argument("parse_instances_raw_yuv420p10_host: coeffs");
+          const int fmt = yuv10_format_of(format);
+          YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          int n = 0;
+          int st = codec::parse_instances_raw_yuv420p10_host(p, s.size(), HS, WS, fmt, k, nullptr,
+                                                             max_images, &n);
+          if (st != codec::OK) n = 0;
+          py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
+                                  (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
+          if (st == codec::OK)
+            st = codec::parse_instances_raw_yuv420p10_host(p, s.size(), HS, WS, fmt, k,
+                                                           out.mutable_data(), max_images, &n);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"), py::arg("coeffs"),
+        py::arg("max_images") = -1);
   // ---- packed pixel formats (csrc/codec/pixfmt.h) ----
   m.def("packed_bpp", [](const std::string& format) {
     return packed_bpp(packed_format_of(format.c_str()));

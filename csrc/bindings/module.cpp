@@ -330,6 +330,34 @@ PYBIND11_MODULE(_C, m) {
               std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
           py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
   }
+  // The raw 10-bit 4:2:0 decoder (yuv420_hi.hip): the arguments of raw_yuvp_instances with format
+  // "p010le" | "yuv420p10le" and a table of yuv10_coeffs
+  m.def("raw_yuv420p10_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,
+           std::vector<int32_t> coeffs, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b, bool nchw) {
+          const auto prep = prep_from("raw_yuv420p10_instances", a, b, nchw);
+          if (coeffs.size() != 6)
+            throw std::invalid_argument(
+                "raw_yuv420p10_instances: coeffs takes (cy, crv, cgu, cgv, cbu, yo)");
+          gale::YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          const int fmt = format == "p010le"        ? (int)gale::YUV_P010LE
+                          : format == "yuv420p10le" ? (int)gale::YUV_YUV420P10LE
+                                                    : (int)gale::YUV_NONE;
+          return (int)gale::raw_yuv420p10_instances(
+              images, static_cast<const gale::B64Image*>(P(imgs)),
+              static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+              static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+              prep ? &*prep : nullptr, fmt, k);
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("format") = "p010le",
+        py::arg("coeffs") = std::vector<int32_t>{305236, 418389, -102698, -213115, 528805, 64},
+        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("b64_packed_instances",
         [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
            uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,

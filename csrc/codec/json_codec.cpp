@@ -713,6 +713,23 @@ int parse_instances_raw_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, in
   return OK;
 }
 
+int parse_instances_raw_yuv420p10_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                       const YuvCoeffs& k, float* out, int max_images,
+                                       int* images) {
+  *images = 0;
+  if (HS <= 0 || WS <= 0 || ((HS | WS) & 1) || !yuv_is_420_hi(format)) return BAD_SHAPE;
+  const int64_t B = yuv420p10_bytes(HS, WS);
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  const size_t per = (size_t)HS * WS * 3;
+  for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
+    yuv420p10_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, format, k, nullptr,
+                          out + (size_t)e * per);
+  *images = s.images;
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

@@ -160,6 +160,14 @@ int parse_instances_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int fo
 int parse_instances_raw_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                   const YuvCoeffs& k, float* out, int max_images, int* images);
 
+// Host decoder of raw 10-bit YUV 4:2:0 frame records (yuv.h: p010le / yuv420p10le; there is no
+// b64 form): the value is N frames of yuv420p10_bytes(HS, WS) bytes, converted by
+// yuv420p10_to_rgb_host with the table k of yuv10_coeffs to (float)q * 0.25f. The verdicts of
+// parse_instances_raw_host; odd or non-positive sizes or another format are BAD_SHAPE.
+int parse_instances_raw_yuv420p10_host(const uint8_t* p, size_t n, int HS, int WS, int format,
+                                       const YuvCoeffs& k, float* out, int max_images,
+                                       int* images);
+
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes
 // (L = 4 ceil(B / 3) characters, the last (3 - B mod 3) mod 3 of them '='; a character outside

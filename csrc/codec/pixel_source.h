@@ -1,5 +1,6 @@
 // What the b64 strings of a topology carry (engine keys pixel_format and input_dtype):
-// interleaved RGB bytes, a YUV 4:2:0, packed 4:2:2 or planar 4:2:2 / 4:4:4 frame (yuv.h), packed pixels (pixfmt.h) or a typed tensor
+// interleaved RGB bytes, a YUV 4:2:0, packed 4:2:2, planar 4:2:2 / 4:4:4 or 10-bit 4:2:0 (raw
+// only) frame (yuv.h), packed pixels (pixfmt.h) or a typed tensor
 // (elemtype.h: the rgb layout with 16-bit or float elements). PixelSource is the one holder of
 // {yuv format, YuvCoeffs, packed format, element type} and of the rules about them: the configuration names,
 // the bytes of a string, what a topology may combine them with, what the ingest sees and which
@@ -31,7 +32,7 @@ class PixelSource {
   PixelSource() = default;  // rgb
 
   // From the configuration names: pixel_format rgb | i420 | nv12 | yuyv422 | uyvy422 | yuv422p |
-  // yuv444p | bgr24 | rgba | bgra | gray;
+  // yuv444p | p010le | yuv420p10le | bgr24 | rgba | bgra | gray;
   // yuv_matrix bt601 | bt709 and yuv_range limited | full, null where the configuration does not
   // name one (bt601, limited; naming one with a packed format is refused).
   static PixelSource from_names(const std::string& pixel_format, const std::string* yuv_matrix,
@@ -44,14 +45,18 @@ class PixelSource {
       s.yuv_format_ = pixel_format == "yuyv422" ? (int)YUV_YUYV422 : (int)YUV_UYVY422;
     else if (pixel_format == "yuv422p" || pixel_format == "yuv444p")
       s.yuv_format_ = pixel_format == "yuv422p" ? (int)YUV_YUV422P : (int)YUV_YUV444P;
+    else if (pixel_format == "p010le" || pixel_format == "yuv420p10le")
+      s.yuv_format_ = pixel_format == "p010le" ? (int)YUV_P010LE : (int)YUV_YUV420P10LE;
     else if (pixel_format != "rgb" && !s.packed_format_)
       throw std::invalid_argument("pixel_format: rgb, i420, nv12, bgr24, rgba, bgra or gray");
     if (s.packed_format_ && (yuv_matrix || yuv_range))
       throw std::invalid_argument("yuv_matrix / yuv_range need pixel_format i420 or nv12");
     const std::string ym = yuv_matrix ? *yuv_matrix : "bt601";
     const std::string yr = yuv_range ? *yuv_range : "limited";
-    if (!yuv_coeffs(ym == "bt601" ? 0 : ym == "bt709" ? 1 : -1,
-                    yr == "limited" ? 0 : yr == "full" ? 1 : -1, &s.yuv_))
+    // (the 10-bit formats have tables of their own: the scale 2^18, yo = 64)
+    if (!(yuv_is_420_hi(s.yuv_format_) ? yuv10_coeffs : yuv_coeffs)(
+            ym == "bt601" ? 0 : ym == "bt709" ? 1 : -1,
+            yr == "limited" ? 0 : yr == "full" ? 1 : -1, &s.yuv_))
       throw std::invalid_argument("yuv_matrix: bt601 or bt709; yuv_range: limited or full");
     return s;
   }
@@ -82,6 +87,7 @@ class PixelSource {
   int yuv_format() const { return yuv_format_; }        // YuvFormat (YUV_NONE unless YUV)
   bool yuv422() const { return yuv_is_422(yuv_format_); }  // a packed 4:2:2 frame (kind YUV)
   bool planar() const { return yuv_is_planar(yuv_format_); }  // a planar 4:2:2 / 4:4:4 frame (YUV)
+  bool hi420() const { return yuv_is_420_hi(yuv_format_); }   // a 10-bit 4:2:0 frame (YUV)
   const YuvCoeffs& yuv() const { return yuv_; }
   int packed_format() const { return packed_format_; }  // PackedFormat (PACKED_NONE unless PACKED)
   int elem() const { return elem_; }                    // InputElem (ELEM_U8 unless TYPED)
@@ -91,6 +97,7 @@ class PixelSource {
     return kind() == PACKED ? packed_bytes(HS, WS, packed_format_)
            : yuv422()       ? yuv422_bytes(HS, WS)
            : planar()       ? yuvp_bytes(HS, WS, yuv_format_)
+           : hi420()        ? yuv420p10_bytes(HS, WS)
            : kind() == YUV  ? yuv420_bytes(HS, WS)
                             : (int64_t)HS * WS * C * elem_bytes(elem_);
   }
@@ -98,13 +105,14 @@ class PixelSource {
   // What a topology must look like to carry this source: model channels C, the prep's nchw,
   // record-side HS x WS, input_format b64 or raw (input_b64: one of the two). A raw source
   // carries no YUV 4:2:0 frame; a packed 4:2:2 frame goes with either encoding, any HS and an
-  // even WS, and so does a planar frame (yuv444p: any WS). std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
+  // even WS, and so does a planar frame (yuv444p: any WS); a 10-bit 4:2:0 frame goes with raw
+  // only and even HS, WS. std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
   // rgb b64 records go with.
   // uniform_prep: whether the prep's four coefficient pairs are equal (a typed tensor may have
   // C > 4, which the decoders serve with uniform coefficients only: b64::prep_fits; the Python
   // configuration refuses the same by --input-mean / --input-std).
   void check(int C, bool nchw, int HS, int WS, bool input_b64, bool uniform_prep = true) const {
-    if (raw_ && kind() == YUV && !yuv422() && !planar())
+    if (raw_ && kind() == YUV && !yuv422() && !planar() && !hi420())
       throw std::invalid_argument("input_format raw: no pixel_format i420 / nv12");
     if (raw_ && kind() == RGB && C > 4 && !uniform_prep)
       throw std::invalid_argument("input_format raw: per-channel input_a / input_b need C <= 4");
@@ -120,8 +128,11 @@ class PixelSource {
     }
     const std::string what = yuv422()        ? "pixel_format yuyv422 / uyvy422"
                              : planar()      ? "pixel_format yuv422p / yuv444p"
+                             : hi420()       ? "pixel_format p010le / yuv420p10le"
                              : kind() == YUV ? "pixel_format i420 / nv12"
                                              : "pixel_format bgr24 / rgba / bgra / gray";
+    if (hi420() && (!input_b64 || !raw_))
+      throw std::invalid_argument(what + " needs input_format raw");
     if (!input_b64) throw std::invalid_argument(what + " needs input_format b64");
     if (nchw) throw std::invalid_argument(what + ": no nchw layout");
     if (C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
@@ -148,6 +159,7 @@ class PixelSource {
     return kind() == PACKED ? Dims{HS, WS, packed_bpp(packed_format_)}
            : yuv422()       ? Dims{HS, WS, 2}
            : planar()       ? Dims{HS, WS, 3 - yuvp_shift(yuv_format_)}
+           : hi420()        ? Dims{HS, WS, 3}
            : kind() == YUV  ? Dims{HS / 2, WS, 3}
                             : Dims{HS, WS * elem_bytes(elem_), C};
   }
@@ -166,6 +178,10 @@ class PixelSource {
                                                          max_images, images)
                   : codec::parse_instances_yuvp_host(p, n, HS, WS, yuv_format_, yuv_, out,
                                                      max_images, images);
+    if (hi420())  // (raw only: check() refuses the b64 form)
+      return raw_ ? codec::parse_instances_raw_yuv420p10_host(p, n, HS, WS, yuv_format_, yuv_,
+                                                              out, max_images, images)
+                  : (int)codec::BAD_SHAPE;
     if (raw_)
       return kind() == YUV ? (int)codec::BAD_SHAPE
                            : codec::parse_instances_raw_host(p, n, HS, WS, C, elem_,

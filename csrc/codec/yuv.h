@@ -22,6 +22,24 @@
 // WS), any HS, a frame is Y[HS][WS], U[HS][WS >> s], V[HS][WS >> s], B = HS*WS + 2 (HS*WS >> s)
 // bytes. Pixel (y, x) takes Y[y][x], U[y][x >> s], V[y][x >> s]; with the linear pixel index
 // p = y WS + x that is Y[p], U[p >> s], V[p >> s] of three byte streams. Same formulas and tables.
+//
+// 10-bit 4:2:0 frames (input pixel formats "p010le" / "yuv420p10le", raw records only; kernel
+// csrc/kernels/yuv420_hi.hip): a frame of HS x WS pixels (both even) is B = 3*HS*WS bytes of
+// little-endian 16-bit words:
+//     p010le:      Y[HS][WS], UV[HS/2][WS/2][2]            sample = word >> 6   (low six bits ignored)
+//     yuv420p10le: Y[HS][WS], U[HS/2][WS/2], V[HS/2][WS/2]  sample = word & 1023 (high six ignored)
+// Pixel (y, x) takes Y[y][x] and the chroma sample (y >> 1, x >> 1). The result is in quarter
+// steps of the 8-bit scale, q in [0, 1020]; with yo = 64 (limited) or 0 (full):
+//     q_R = clamp((cy (Y - yo)                  + crv (V - 512) + 2^17) >> 18, 0, 1020)
+//     q_G = clamp((cy (Y - yo) + cgu (U - 512) + cgv (V - 512) + 2^17) >> 18, 0, 1020)
+//     q_B = clamp((cy (Y - yo) + cbu (U - 512)                  + 2^17) >> 18, 0, 1020)
+// and the model input of channel c is fmaf((float)q * 0.25f, a[c], b[c]) (the product is exact).
+// The coefficients are the rationals above (limited: sy = 255/219, sc = 255/224 as for 8 bits,
+// 64 .. 940 being 4 x (16 .. 235); full: sy = sc = 1020/1023) times 2^18, rounded half to even -
+// 2^18 because 2^20 overflows 32 bits with 10-bit samples. The accumulator is affine in
+// (Y, U, V); over the 8 corners of the cube, the 4 tables and the 3 channels its largest
+// magnitude, rounding term included, is 575 820 179 < 2^31. The unclamped result lies within
+// 0.5 + 2047 * 2^-19 quarter steps of the real-valued matrix.
 // No HIP in this header: the sanitizer programs of the host codec include it.
 #pragma once
 #include <stddef.h>
@@ -31,7 +49,7 @@ namespace gale {
 
 enum YuvFormat : int {
   YUV_NONE = 0, YUV_I420 = 1, YUV_NV12 = 2, YUV_YUYV422 = 3, YUV_UYVY422 = 4,
-  YUV_YUV422P = 5, YUV_YUV444P = 6
+  YUV_YUV422P = 5, YUV_YUV444P = 6, YUV_P010LE = 7, YUV_YUV420P10LE = 8
 };
 enum YuvMatrix : int { YUV_BT601 = 0, YUV_BT709 = 1 };
 enum YuvRange : int { YUV_LIMITED = 0, YUV_FULL = 1 };
@@ -75,6 +93,30 @@ constexpr int yuvp_shift(int format) { return format == YUV_YUV422P ? 1 : 0; }
 inline int64_t yuvp_bytes(int HS, int WS, int format) {
   const int64_t hw = (int64_t)HS * WS;
   return hw + 2 * (hw >> yuvp_shift(format));
+}
+
+// 10-bit 4:2:0: whether `format` is one, the bytes of one frame (HS, WS even), the table of
+// (matrix, range) at the scale 2^18 (false for a value outside the enums), and the 10 bits of a
+// 16-bit word.
+constexpr bool yuv_is_420_hi(int format) {
+  return format == YUV_P010LE || format == YUV_YUV420P10LE;
+}
+inline int64_t yuv420p10_bytes(int HS, int WS) { return (int64_t)HS * WS * 3; }
+inline bool yuv10_coeffs(int matrix, int range, YuvCoeffs* k) {
+  static const int32_t kTable[2][2][5] = {
+      {{305236, 418389, -102698, -213115, 528805},   // bt601 limited
+       {261375, 366448, -89949, -186658, 463157}},   // bt601 full
+      {{305236, 469956, -55902, -139699, 553753},    // bt709 limited
+       {261375, 411614, -48962, -122356, 485008}},   // bt709 full
+  };
+  if (matrix < 0 || matrix > 1 || range < 0 || range > 1) return false;
+  const int32_t* t = kTable[matrix][range];
+  k->cy = t[0], k->crv = t[1], k->cgu = t[2], k->cgv = t[3], k->cbu = t[4];
+  k->yo = range == YUV_LIMITED ? 64 : 0;
+  return true;
+}
+constexpr int yuv10_sample(int format, int word) {
+  return format == YUV_P010LE ? (word >> 6) & 1023 : word & 1023;
 }
 
 namespace codec {
@@ -160,6 +202,42 @@ inline bool yuvp_to_rgb_host(const uint8_t* src, int HS, int WS, int format, con
       if (f32) f32[3 * p + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
     }
   }
+  return true;
+}
+
+inline uint16_t yuv10_clampq(int32_t acc) {
+  const int32_t v = acc >> 18;
+  return (uint16_t)(v < 0 ? 0 : v > 1020 ? 1020 : v);
+}
+
+// The same for one 10-bit 4:2:0 frame: yuv420p10_bytes(HS, WS) bytes at src (any alignment) ->
+// [HS][WS][3]. q (optional): the quarter steps, 0 .. 1020. f32 (optional): the model-side floats,
+// fmaf((float)q * 0.25f, a[c], b[c]), or (float)q * 0.25f when a is null. k: a table of
+// yuv10_coeffs. false (nothing written) for odd or non-positive sizes or another format.
+inline bool yuv420p10_to_rgb_host(const uint8_t* src, int HS, int WS, int format,
+                                  const YuvCoeffs& k, uint16_t* q, float* f32,
+                                  const float* a = nullptr, const float* b = nullptr) {
+  if (HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1) || !yuv_is_420_hi(format)) return false;
+  const size_t hw = (size_t)HS * WS, cw = (size_t)WS / 2;
+  const auto word = [&](size_t i) { return (int)src[2 * i] | (int)src[2 * i + 1] << 8; };
+  for (int y = 0; y < HS; ++y)
+    for (int x = 0; x < WS; ++x) {
+      const size_t ci = (size_t)(y >> 1) * cw + (size_t)(x >> 1);
+      const size_t iu = format == YUV_P010LE ? hw + 2 * ci : hw + ci;
+      const size_t iv = format == YUV_P010LE ? hw + 2 * ci + 1 : hw + hw / 4 + ci;
+      const int Y = yuv10_sample(format, word((size_t)y * WS + x));
+      const int u = yuv10_sample(format, word(iu)) - 512, v = yuv10_sample(format, word(iv)) - 512;
+      const int32_t yy = k.cy * (Y - k.yo) + (1 << 17);
+      const uint16_t px[3] = {yuv10_clampq(yy + k.crv * v),
+                              yuv10_clampq(yy + k.cgu * u + k.cgv * v),
+                              yuv10_clampq(yy + k.cbu * u)};
+      const size_t o = ((size_t)y * WS + x) * 3;
+      for (int c = 0; c < 3; ++c) {
+        const float f = (float)px[c] * 0.25f;
+        if (q) q[o + c] = px[c];
+        if (f32) f32[o + c] = a ? __builtin_fmaf(f, a[c], b[c]) : f;
+      }
+    }
   return true;
 }
 

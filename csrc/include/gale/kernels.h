@@ -336,6 +336,29 @@ hipError_t raw_yuvp_instances(int images, const B64Image* imgs, const uint8_t* b
                               const int* d_images, const InputPrep* prep, int format,
                               const YuvCoeffs& coeffs);
 
+// GPU decoder of raw 10-bit YUV 4:2:0 frame records (input pixel formats "p010le" /
+// "yuv420p10le", yuv420_hi.hip), with the arguments, descriptor table and early exit of
+// raw_yuvp_instances. A frame of HS x WS pixels (both even) is B = 3*HS*WS bytes of little-endian
+// 16-bit words: YUV_P010LE Y[HS][WS], UV[HS/2][WS/2][2] with the sample in the top ten bits;
+// YUV_YUV420P10LE Y[HS][WS], U[HS/2][WS/2], V[HS/2][WS/2] with it in the low ten. Pixel (y, x)
+// takes Y[y][x] and chroma (y >> 1, x >> 1) and becomes three floats of the fp32 NHWC batch
+// tensor, fmaf((float)q * 0.25f, a[c], b[c]) with q the quarter steps 0 .. 1020 of yuv.h's
+// integer matrix (coeffs: a table of yuv10_coeffs): the bits of codec::yuv420p10_to_rgb_host.
+// imgs[].off is the byte offset of the frame's first byte, any phase, and `bytes` may be any
+// byte: only aligned dwords that hold a byte of a frame are read. status is never written (it
+// must still be given).
+// The grid is ceil((HS/2) ceil(WS/8) / 256) x images. A lane converts a block of 2 rows x 8
+// columns once, in registers, and the floats are re-staged through per-wave LDS one image row at
+// a time: 16-byte stores when WS mod 4 == 0 and the image's base is 16-byte aligned, 8-byte
+// stores otherwise. No workgroup barrier, no atomics.
+// hipErrorInvalidValue, before any launch: a null pointer, odd or non-positive HS / WS, C != 3,
+// a format other than the two, an nchw prep, more than 65535 images, a frame of more than 2^30
+// floats. images == 0 launches nothing.
+hipError_t raw_yuv420p10_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                   int WS, int C, float* out, int* status, hipStream_t stream,
+                                   const int* d_images, const InputPrep* prep, int format,
+                                   const YuvCoeffs& coeffs);
+
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard
 // base64, B = HS*WS*P bytes (csrc/codec/pixfmt.h), padded like an RGB string - becomes the

@@ -14,7 +14,8 @@
         [--encoding json|b64|raw]                     b64: base64 uint8 records (--pixels byte);
                                                       raw: the images' bytes, no envelope
         [--size H,W]                                  images of that size (--input-size H,W)
-        [--pixel-format rgb|i420|nv12|yuyv422|uyvy422|yuv422p|yuv444p|bgr24|rgba|bgra|gray]
+        [--pixel-format rgb|i420|nv12|yuyv422|uyvy422|yuv422p|yuv444p|p010le|yuv420p10le|
+                        bgr24|rgba|bgra|gray]
                                                       YUV 4:2:0 frames / packed pixels
                                                       (--encoding b64; --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
@@ -216,8 +217,9 @@ def cmd_produce(argv: List[str]) -> int:
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_text,
                            encode_records_packed, encode_records_raw, encode_records_typed,
-                           encode_records_yuv, encode_records_yuv422, encode_records_yuvp,
-                           synthetic_images, synthetic_pixels, synthetic_yuv422_planes,
+                           encode_records_yuv, encode_records_yuv420p10, encode_records_yuv422,
+                           encode_records_yuvp, synthetic_images, synthetic_pixels,
+                           synthetic_yuv420p10_planes, synthetic_yuv422_planes,
                            synthetic_yuv_planes, synthetic_yuvp_planes)
     from gale.models import get_model
 
@@ -250,7 +252,9 @@ def cmd_produce(argv: List[str]) -> int:
                          "layout, a 3-channel model and an even width; yuv422p / yuv444p: "
                          "synthetic planar frames (Y, U, V planes; chroma of half / full width); "
                          "--encoding b64 or raw, the nhwc layout, a 3-channel model and, for "
-                         "yuv422p, an even width; bgr24 / rgba / bgra / gray: the "
+                         "yuv422p, an even width; p010le / yuv420p10le: synthetic 10-bit 4:2:0 "
+                         "frames of 3*HS*WS bytes; --encoding raw only, the nhwc layout, a "
+                         "3-channel model and even sizes; bgr24 / rgba / bgra / gray: the "
                          "synthetic pixels of rgb in that byte order (alpha random; gray: their "
                          "first channel alone); needs --encoding b64, the nhwc layout and a "
                          "3-channel model")
@@ -270,7 +274,10 @@ def cmd_produce(argv: List[str]) -> int:
     planar = a.pixel_format in ("yuv422p", "yuv444p")
     yuv422 = a.pixel_format in ("yuyv422", "uyvy422") or planar  # (either encoding)
     yuv = a.pixel_format != "rgb" and not packed
-    if (yuv or packed) and a.encoding != "b64" and not (raw and (packed or yuv422)):
+    hi = a.pixel_format in ("p010le", "yuv420p10le")
+    if hi and not raw:
+        ap.error(f"--pixel-format {a.pixel_format} needs --encoding raw")
+    if (yuv or packed) and a.encoding != "b64" and not (raw and (packed or yuv422 or hi)):
         ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64"
                  + (" or raw" if yuv422 else ""))
     if yuv and a.layout != "nhwc":
@@ -284,7 +291,14 @@ def cmd_produce(argv: List[str]) -> int:
         shape = produce_shape(net.input_shape, a.size)
     except ValueError as e:
         ap.error(str(e))
-    if planar:
+    if hi:
+        if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
+            ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
+                     f"{shape}")
+        recs = encode_records_yuv420p10(
+            *synthetic_yuv420p10_planes(a.images, shape[0], shape[1], a.seed), a.pixel_format,
+            a.images_per_record)
+    elif planar:
         if shape[2] != 3 or (a.pixel_format == "yuv422p" and shape[1] % 2):
             ap.error(f"--pixel-format {a.pixel_format} needs 3 channels"
                      f"{' and an even width' if a.pixel_format == 'yuv422p' else ''}, got {shape}")

@@ -48,9 +48,11 @@ CHOICES = {
     # (PixelUnpack), or a packed YUV 4:2:2 frame (yuyv422: Y0 U Y1 V macropixels; uyvy422:
     # U Y0 V Y1; b64 or raw) converted to RGB on the GPU (Yuv422Convert), or a planar YUV 4:2:2 /
     # 4:4:4 frame (yuv422p / yuv444p: Y, U, V planes with full-height chroma, what a JPEG decoder
-    # hands back; b64 or raw; YuvPlanarConvert). The names are ffmpeg's pix_fmts
+    # hands back; b64 or raw; YuvPlanarConvert), or a 10-bit 4:2:0 frame of 16-bit words (p010le:
+    # what hardware video decoders write; yuv420p10le: what software decoders write; raw only;
+    # Yuv420HiConvert). The names are ffmpeg's pix_fmts
     "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray", "yuyv422",
-                           "uyvy422", "yuv422p", "yuv444p"),
+                           "uyvy422", "yuv422p", "yuv444p", "p010le", "yuv420p10le"),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -82,7 +84,13 @@ HELP = {
                           "yuv422p / yuv444p: every b64 string or raw image is a planar frame, "
                           "Y[HS][WS] then U and V of [HS][WS/2] (yuv422p: 2*HS*WS bytes, WS "
                           "even) or [HS][WS] (yuv444p: 3*HS*WS bytes, any size); a 3-channel "
-                          "model; --input-format b64 or raw; converted to RGB on the GPU; bgr24 / rgba / bgra / gray: every "
+                          "model; --input-format b64 or raw; converted to RGB on the GPU; "
+                          "p010le / yuv420p10le: every raw image is a 10-bit 4:2:0 frame of "
+                          "3*HS*WS bytes, little-endian 16-bit words (p010le: Y then interleaved "
+                          "UV, the ten bits at the top; yuv420p10le: Y, U, V planes, the ten "
+                          "bits at the bottom; HS, WS even; a 3-channel model; --input-format "
+                          "raw only), converted on the GPU to RGB in quarter steps of the 8-bit "
+                          "scale; bgr24 / rgba / bgra / gray: every "
                           "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
                           "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
@@ -230,6 +238,7 @@ class GaleConfig:
     input_pixel_format: str = "rgb"    # i420 | nv12: b64 strings are YUV 4:2:0 frames; yuyv422 |
                                        # uyvy422: b64 strings / raw images are 4:2:2 frames;
                                        # yuv422p | yuv444p: planar 4:2:2 / 4:4:4 frames;
+                                       # p010le | yuv420p10le: raw 10-bit 4:2:0 frames;
                                        # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
@@ -351,7 +360,8 @@ class GaleConfig:
         fmt = self.input_pixel_format
         planar = fmt in ("yuv422p", "yuv444p")
         yuv422 = fmt in ("yuyv422", "uyvy422") or planar  # (either encoding, any HS)
-        yuv = fmt in ("i420", "nv12")
+        hi = fmt in ("p010le", "yuv420p10le")  # (raw only, even HS and WS)
+        yuv = fmt in ("i420", "nv12") or hi
         if not yuv and not yuv422:
             for k in ("input_yuv_matrix", "input_yuv_range"):
                 if getattr(self, k):
@@ -361,6 +371,9 @@ class GaleConfig:
             return
         from gale.models import get_model
 
+        if hi and self.input_format != "raw":
+            raise ValueError(f"--input-pixel-format {fmt} needs --input-format raw: 16-bit 4:2:0 "
+                             f"frames are not served as {self.input_format} records")
         if self.input_format not in ("b64", "raw"):
             raise ValueError(f"--input-pixel-format {fmt} needs --input-format b64"
                              + (" or raw" if yuv422 else ""))
@@ -402,12 +415,14 @@ class GaleConfig:
         return ElemType.from_config(self)
 
     def input_yuv(self):
-        """The ``YuvConvert`` (4:2:0), ``Yuv422Convert`` (packed 4:2:2) or ``YuvPlanarConvert``
-        (planar 4:2:2 / 4:4:4) of this configuration, None for rgb and the packed pixel formats."""
-        from gale.models.preprocess import Yuv422Convert, YuvConvert, YuvPlanarConvert
+        """The ``YuvConvert`` (4:2:0), ``Yuv422Convert`` (packed 4:2:2), ``YuvPlanarConvert``
+        (planar 4:2:2 / 4:4:4) or ``Yuv420HiConvert`` (10-bit 4:2:0) of this configuration, None
+        for rgb and the packed pixel formats."""
+        from gale.models.preprocess import (Yuv420HiConvert, Yuv422Convert, YuvConvert,
+                                            YuvPlanarConvert)
 
         return (YuvConvert.from_config(self) or Yuv422Convert.from_config(self)
-                or YuvPlanarConvert.from_config(self))
+                or YuvPlanarConvert.from_config(self) or Yuv420HiConvert.from_config(self))
 
     def input_unpack(self):
         """The ``PixelUnpack`` of this configuration, None for rgb and the YUV formats."""

@@ -218,6 +218,54 @@ def synthetic_yuvp_planes(n: int, HS: int, WS: int, pixel_format: str, seed: int
             rng.integers(0, 256, (n, HS, WS >> s), dtype=np.uint8))
 
 
+def pack_yuv420p10(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str,
+                   junk: Optional[np.ndarray] = None) -> np.ndarray:
+    """10-bit samples Y [N, HS, WS], U / V [N, HS/2, WS/2] (integers 0 .. 1023) -> uint8
+    [N, 3*HS*WS] frames of little-endian 16-bit words: p010le (Y, interleaved UV, the sample in
+    the top ten bits) or yuv420p10le (Y, U, V planes, the sample in the low ten). ``junk``
+    (uint16 [N, 3*HS*WS/2], optional): its six bits that a reader ignores are set in every word."""
+    from gale.models.preprocess import YUV420_HI_FORMATS
+
+    Y, U, V = (np.asarray(p) for p in (Y, U, V))
+    if pixel_format not in YUV420_HI_FORMATS:
+        raise ValueError(f"pixel_format={pixel_format!r}: expected p010le or yuv420p10le")
+    if any(p.ndim != 3 or p.dtype.kind not in "iu" or p.min(initial=0) < 0
+           or p.max(initial=0) > 1023 for p in (Y, U, V)):
+        raise ValueError("pack_yuv420p10: integer [N, rows, cols] planes of 0 .. 1023")
+    N, HS, WS = Y.shape
+    if HS % 2 or WS % 2 or U.shape != (N, HS // 2, WS // 2) or V.shape != U.shape:
+        raise ValueError(f"pack_yuv420p10: Y {Y.shape} needs even sizes and U, V of "
+                         f"{(N, HS // 2, WS // 2)}, got {U.shape}, {V.shape}")
+    chroma = [np.stack([U, V], axis=-1)] if pixel_format == "p010le" else [U, V]
+    w = np.concatenate([p.reshape(N, -1) for p in (Y, *chroma)], axis=1).astype(np.uint16)
+    sh = YUV420_HI_FORMATS[pixel_format]
+    w = w << sh
+    if junk is not None:
+        w |= np.asarray(junk, np.uint16) & np.uint16(~(1023 << sh) & 0xFFFF)
+    return np.ascontiguousarray(w.astype("<u2")).view(np.uint8).reshape(N, -1)
+
+
+def encode_records_yuv420p10(Y: np.ndarray, U: np.ndarray, V: np.ndarray, pixel_format: str,
+                             images_per_record: int = 1,
+                             junk: Optional[np.ndarray] = None) -> List[bytes]:
+    """10-bit samples (``pack_yuv420p10``) -> raw records of 10-bit 4:2:0 frames
+    (--input-pixel-format p010le | yuv420p10le, --input-format raw): each record value is its
+    frames' bytes back to back."""
+    frames = pack_yuv420p10(Y, U, V, pixel_format, junk)
+    return [frames[i:i + images_per_record].tobytes()
+            for i in range(0, frames.shape[0], images_per_record)]
+
+
+def synthetic_yuv420p10_planes(n: int, HS: int, WS: int, seed: int = 0):
+    """Deterministic 10-bit samples (Y [n, HS, WS], U, V [n, HS/2, WS/2]) of synthetic frames."""
+    if HS % 2 or WS % 2:
+        raise ValueError(f"a 4:2:0 frame needs even sizes, got {HS},{WS}")
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 1024, (n, HS, WS), dtype=np.uint16),
+            rng.integers(0, 1024, (n, HS // 2, WS // 2), dtype=np.uint16),
+            rng.integers(0, 1024, (n, HS // 2, WS // 2), dtype=np.uint16))
+
+
 def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
                 alpha: Optional[np.ndarray] = None) -> np.ndarray:
     """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of

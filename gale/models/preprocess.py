@@ -612,6 +612,101 @@ class YuvPlanarConvert(YuvConvert):
         return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
 
 
+# the 10-bit 4:2:0 formats: name -> right shift of a 16-bit word to its sample
+YUV420_HI_FORMATS = {"p010le": 6, "yuv420p10le": 0}
+YUV10_SHIFT = 18  # their coefficients' fixed point: 2^20 overflows 32 bits with 10-bit samples
+
+
+@dataclass(frozen=True)
+class Yuv420HiConvert(YuvConvert):
+    """Raw 10-bit YUV 4:2:0 frames (``--input-pixel-format p010le | yuv420p10le``) to RGB, in
+    integers, in quarter steps of the 8-bit scale.
+
+    A frame of HS x WS pixels (both even) is ``B = 3*HS*WS`` bytes of little-endian 16-bit words:
+    p010le ``Y[HS][WS]``, ``UV[HS/2][WS/2][2]`` with the sample in the top ten bits (``word >> 6``);
+    yuv420p10le ``Y[HS][WS]``, ``U[HS/2][WS/2]``, ``V[HS/2][WS/2]`` with it in the low ten
+    (``word & 1023``). Pixel (y, x) takes ``Y[y][x]`` and chroma ``(y >> 1, x >> 1)``. With
+    ``yo = 64`` (limited) or 0 (full), in signed 32-bit arithmetic::
+
+        q_R = clamp((cy (Y - yo)                  + crv (V - 512) + 2^17) >> 18, 0, 1020)
+        q_G = clamp((cy (Y - yo) + cgu (U - 512) + cgv (V - 512) + 2^17) >> 18, 0, 1020)
+        q_B = clamp((cy (Y - yo) + cbu (U - 512)                  + 2^17) >> 18, 0, 1020)
+
+    and the model input of channel c is ``fmaf(float(q) * 0.25f, a[c], b[c])``: the range
+    [0, 255] of an 8-bit record, with two more bits. The coefficients are ``YuvConvert``'s
+    rationals (limited: sy = 255/219, sc = 255/224, since 64 .. 940 is 4 x (16 .. 235); full:
+    sy = sc = 1020/1023) times 2^18, rounded half to even. ``codec::yuv420p10_to_rgb_host``
+    (csrc/codec/yuv.h, which holds them as literals) and the ``raw_yuv420p10_instances`` kernel
+    give the same bits."""
+
+    FORMATS = tuple(YUV420_HI_FORMATS)
+    format: str = "p010le"
+
+    def rationals(self):
+        from fractions import Fraction as F
+
+        r = _yuv_rationals(self.matrix, self.range)  # (full: sy = sc = 1)
+        return r if self.range == "limited" else tuple(q * F(1020, 1023) for q in r)
+
+    @property
+    def yo(self) -> int:
+        return 64 if self.range == "limited" else 0
+
+    def coeffs(self) -> Tuple[int, int, int, int, int]:
+        """(cy, crv, cgu, cgv, cbu) at the scale 2^18."""
+        return tuple(_round_half_even(q * (1 << YUV10_SHIFT)) for q in self.rationals())
+
+    @staticmethod
+    def frame_bytes(HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or HS % 2 or WS % 2:
+            raise ValueError(f"a 4:2:0 frame needs even, positive sizes, got {HS},{WS}")
+        return HS * WS * 3
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``raw_yuv420p10_instances`` binding."""
+        return dict(format=self.format, coeffs=[*self.coeffs(), self.yo])
+
+    def accumulators(self, Y, U, V):
+        """The three int64 accumulators (rounding term included) of 10-bit int arrays Y, U, V."""
+        cy, crv, cgu, cgv, cbu = self.coeffs()
+        Y, U, V = (np.asarray(v).astype(np.int64) for v in (Y, U, V))
+        yy = cy * (Y - self.yo) + (1 << (YUV10_SHIFT - 1))
+        u, v = U - 512, V - 512
+        return yy + crv * v, yy + cgu * u + cgv * v, yy + cbu * u
+
+    def planes(self, frame, HS: int, WS: int):
+        """uint8 [..., B] frames -> 10-bit samples (Y [..., HS, WS], U, V [..., HS/2, WS/2])."""
+        B = self.frame_bytes(HS, WS)
+        f = np.ascontiguousarray(np.asarray(frame, np.uint8))
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        w = (f.view("<u2") >> YUV420_HI_FORMATS[self.format]) & 1023
+        lead, hw = f.shape[:-1], HS * WS
+        Y = w[..., :hw].reshape(*lead, HS, WS)
+        if self.format == "p010le":
+            uv = w[..., hw:].reshape(*lead, HS // 2, WS // 2, 2)
+            return Y, uv[..., 0], uv[..., 1]
+        return (Y, w[..., hw:hw + hw // 4].reshape(*lead, HS // 2, WS // 2),
+                w[..., hw + hw // 4:].reshape(*lead, HS // 2, WS // 2))
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint16 [..., HS, WS, 3] quarter steps q."""
+        Y, U, V = self.planes(frame, HS, WS)
+        up = lambda c: np.repeat(np.repeat(c, 2, axis=-2), 2, axis=-1)  # noqa: E731
+        acc = self.accumulators(Y, up(U), up(V))
+        assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
+        return np.stack([np.clip(a >> YUV10_SHIFT, 0, 1020) for a in acc],
+                        axis=-1).astype(np.uint16)
+
+    @staticmethod
+    def to_float(q, prep=None) -> np.ndarray:
+        """The model-side floats of quarter steps q: ``fmaf(float(q) * 0.25f, a[c], b[c])`` with
+        the coefficients of ``prep`` (an ``InputPrep``; None: the identity). The product by 0.25
+        is exact, so this is ``prep.apply`` of it."""
+        x = np.asarray(q).astype(np.float32) * np.float32(0.25)
+        return x if prep is None else prep.apply(x)
+
+
 # the packed formats: name -> (bytes per pixel, byte offset in a pixel of R, G, B)
 PACKED_FORMATS = {"bgr24": (3, (2, 1, 0)), "rgba": (4, (0, 1, 2)), "bgra": (4, (2, 1, 0)),
                   "gray": (1, (0, 0, 0))}

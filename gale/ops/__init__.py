@@ -473,6 +473,20 @@ def raw_yuvp_instances(staged: torch.Tensor, table: torch.Tensor, size, out: tor
                              images, d_images, prep)
 
 
+def raw_yuv420p10_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                            status: torch.Tensor, yuv, images: Optional[int] = None,
+                            d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Convert raw 10-bit YUV 4:2:0 frames (``--input-pixel-format p010le | yuv420p10le``, input
+    format ``raw``) into the fp32 NHWC batch tensor ``out`` [slots, HS, WS, 3] as RGB in quarter
+    steps of the 8-bit scale, in place; returns ``out``. Arguments as ``raw_yuvp_instances``;
+    ``yuv``: a ``gale.models.preprocess.Yuv420HiConvert``; ``size``: (HS, WS), both even; every
+    frame is 3*HS*WS bytes at any byte offset of ``staged``. ``status`` is never written. There
+    is no CPU path: a shape or argument the launcher refuses raises ``ValueError`` before
+    anything is launched."""
+    return _yuv422_instances("raw_yuv420p10_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
