@@ -46,6 +46,8 @@ $(OBJ)/kernels/yuv422.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp
 $(OBJ)/kernels/yuv_planar.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # and the 10-bit 4:2:0 decoder: 24 independent multiplies and fmas per row of a block
 $(OBJ)/kernels/yuv420_hi.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# and the linear-chroma 4:2:0 decoder: the same 24 independent fmas per row of a block
+$(OBJ)/kernels/b64_yuv_linear.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 gale/_C.so: $(HIP_OBJ) $(CXX_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lz -ldl -pthread \
@@ -117,6 +119,16 @@ build/asan/yuv10_check: csrc/tests/yuv10_check.cpp csrc/codec/json_codec.cpp \
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/yuv10_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# linear chroma for i420 / nv12 (csrc/tests/yuv_chroma_check.cpp): the host twin against a
+# loop-form upsampler, the record parser's linear form and PixelSource's rules for yuv_chroma;
+# codec only, no engine, no HIP call
+build/asan/yuv_chroma_check: csrc/tests/yuv_chroma_check.cpp csrc/codec/json_codec.cpp \
+                             csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/yuv_chroma_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
 # the packed-pixel host codec (csrc/tests/pixfmt_check.cpp): the unpack twin, the record decoder
 # and the byte-count forms of the scan / offsets / splitter on mutated and truncated records;

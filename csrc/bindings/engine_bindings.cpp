@@ -125,6 +125,12 @@ EngineConfig config_from_dict(const py::dict& d) {
       opt(d, "input_dtype", dt);
       c.pixels = c.pixels.with_elem(dt);
     }
+    // the 4:2:0 chroma upsampling (YuvConvert.engine_entries; absent = nearest)
+    if (d.contains("yuv_chroma")) {
+      std::string ch = "nearest";
+      opt(d, "yuv_chroma", ch);
+      c.pixels = c.pixels.with_chroma(ch);
+    }
     if (input_raw) c.pixels = c.pixels.as_raw();
   }
   opt(d, "max_batch", c.max_batch);

@@ -262,6 +262,38 @@ PYBIND11_MODULE(_C, m) {
         py::arg("coeffs") = std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
         py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false,
         py::arg("pairs") = 0);
+  // The same records with triangle-filtered chroma (b64_yuv_linear.hip): the arguments and the
+  // return value of b64_yuv_instances
+  m.def("b64_yuv_linear_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,
+           std::vector<int32_t> coeffs, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b, bool nchw, int pairs) {
+          const auto prep = prep_from("b64_yuv_linear_instances", a, b, nchw);
+          if (coeffs.size() != 6)
+            throw std::invalid_argument("b64_yuv_linear_instances: coeffs takes (cy, crv, cgu, "
+                                        "cgv, cbu, yo)");
+          gale::YuvCoeffs k;
+          k.cy = coeffs[0], k.crv = coeffs[1], k.cgu = coeffs[2], k.cgv = coeffs[3];
+          k.cbu = coeffs[4], k.yo = coeffs[5];
+          const int fmt = format == "i420"   ? (int)gale::YUV_I420
+                          : format == "nv12" ? (int)gale::YUV_NV12
+                                             : (int)gale::YUV_NONE;
+          return (int)gale::b64_yuv_linear_instances(
+              images, static_cast<const gale::B64Image*>(P(imgs)),
+              static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+              static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+              prep ? &*prep : nullptr, fmt, k, pairs);
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("format") = "i420",
+        py::arg("coeffs") = std::vector<int32_t>{1220945, 1673555, -410793, -852458, 2115221, 16},
+        py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false,
+        py::arg("pairs") = 0);
+  m.def("b64_yuv_linear_pairs", &gale::b64_yuv_linear_pairs);
+  m.def("b64_yuv_linear_lds_bytes", &gale::b64_yuv_linear_lds_bytes);
+  m.attr("YUV_LINEAR_MAX_WS") = (int)gale::kYuv420LinearMaxWS;
   // The packed 4:2:2 decoders, one for either encoding: the same arguments. format: "yuyv422" |
   // "uyvy422" (anything else reaches the launcher as an unknown format); the rest as
   // b64_yuv_instances (raw: imgs[].off = the frame's first byte). Returns the launcher's

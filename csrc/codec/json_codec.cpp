@@ -550,16 +550,19 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
 }
 
 int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
-                             const YuvCoeffs& k, float* out, int max_images, int* images) {
+                             const YuvCoeffs& k, float* out, int max_images, int* images,
+                             bool linear) {
   *images = 0;
   if (HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1) ||
       (format != YUV_I420 && format != YUV_NV12))
     return BAD_SHAPE;
   // (B is a multiple of 3: every character of the L = 4 B / 3 is a data character)
   const size_t per = (size_t)HS * WS * 3;
+  const auto convert = linear ? yuv420_linear_to_rgb_host : yuv420_to_rgb_host;
   return parse_b64_records(p, n, yuv420_bytes(HS, WS), out != nullptr, max_images, images,
                            [&](const uint8_t* frame, size_t e) {
-                             yuv420_to_rgb_host(frame, HS, WS, format, k, nullptr, out + e * per);
+                             convert(frame, HS, WS, format, k, nullptr, out + e * per, nullptr,
+                                     nullptr);
                            });
 }
 

@@ -134,9 +134,11 @@ int parse_instances_b64_host(const uint8_t* p, size_t n, int H, int W, int C, fl
 // character outside the alphabet anywhere is BAD_NUMBER), every frame converted by
 // yuv420_to_rgb_host into out[N][HS][WS][3] as (float)RGB - what parse_instances_b64_host gives
 // for the converted image sent as an RGB record. Odd or non-positive sizes and unknown formats
-// are BAD_SHAPE. out may be null.
+// are BAD_SHAPE. out may be null. linear: the triangle-filtered chroma of input-yuv-chroma
+// "linear" (yuv420_linear_to_rgb_host) instead of the nearest sample.
 int parse_instances_yuv_host(const uint8_t* p, size_t n, int HS, int WS, int format,
-                             const YuvCoeffs& k, float* out, int max_images, int* images);
+                             const YuvCoeffs& k, float* out, int max_images, int* images,
+                             bool linear = false);
 
 // Full host decoders of packed YUV 4:2:2 frame records (yuv.h: yuyv422 / uyvy422), b64 and raw.
 // b64: the same envelope, element list and verdicts with strings of yuv422_bytes(HS, WS) bytes

@@ -72,6 +72,17 @@ class PixelSource {
     return s;
   }
 
+  // The same source with the chroma upsampling of the configuration name yuv_chroma: nearest |
+  // linear (yuv.h: the triangle filter). check() refuses linear on anything but b64 i420 / nv12.
+  PixelSource with_chroma(const std::string& yuv_chroma) const {
+    PixelSource s = *this;
+    if (yuv_chroma != "nearest" && yuv_chroma != "linear")
+      throw std::invalid_argument("yuv_chroma: nearest or linear");
+    s.chroma_linear_ = yuv_chroma == "linear";
+    return s;
+  }
+  bool chroma_linear() const { return chroma_linear_; }
+
   // The same source for raw binary records (input_format raw): the value is the images' bytes
   // themselves, with no base64 and no envelope around them.
   PixelSource as_raw() const {
@@ -112,6 +123,14 @@ class PixelSource {
   // C > 4, which the decoders serve with uniform coefficients only: b64::prep_fits; the Python
   // configuration refuses the same by --input-mean / --input-std).
   void check(int C, bool nchw, int HS, int WS, bool input_b64, bool uniform_prep = true) const {
+    if (chroma_linear_) {
+      if (raw_ || !input_b64 || (yuv_format_ != YUV_I420 && yuv_format_ != YUV_NV12))
+        throw std::invalid_argument(
+            "yuv_chroma linear needs input_format b64 and pixel_format i420 or nv12");
+      if (WS > kYuv420LinearMaxWS)
+        throw std::invalid_argument("yuv_chroma linear needs a record-side W of at most " +
+                                    std::to_string(kYuv420LinearMaxWS));
+    }
     if (raw_ && kind() == YUV && !yuv422() && !planar() && !hi420())
       throw std::invalid_argument("input_format raw: no pixel_format i420 / nv12");
     if (raw_ && kind() == RGB && C > 4 && !uniform_prep)
@@ -194,7 +213,7 @@ class PixelSource {
                                                     max_images, images)
            : kind() == YUV
                ? codec::parse_instances_yuv_host(p, n, HS, WS, yuv_format_, yuv_, out,
-                                                 max_images, images)
+                                                 max_images, images, chroma_linear_)
                : codec::parse_instances_b64_host(p, n, HS, WS, C, out, max_images, images);
   }
 
@@ -204,6 +223,7 @@ class PixelSource {
   int packed_format_ = PACKED_NONE;
   int elem_ = ELEM_U8;
   bool raw_ = false;
+  bool chroma_linear_ = false;
 };
 
 }  // namespace gale

@@ -40,6 +40,17 @@
 // (Y, U, V); over the 8 corners of the cube, the 4 tables and the 3 channels its largest
 // magnitude, rounding term included, is 575 820 179 < 2^31. The unclamped result lies within
 // 0.5 + 2047 * 2^-19 quarter steps of the real-valued matrix.
+//
+// Triangle-filter chroma for I420 / NV12 (input-yuv-chroma "linear", b64 records only; kernel
+// csrc/kernels/b64_yuv_linear.hip): libjpeg's h2v2_fancy_upsample, a centre-sited 3:1 filter in
+// both directions, in integers. For pixel (y, x) and a chroma plane C of HS/2 x WS/2:
+//     cy0 = y >> 1    cyn = clamp(cy0 + (y & 1 ? +1 : -1), 0, HS/2 - 1)
+//     cx0 = x >> 1    cxn = clamp(cx0 + (x & 1 ? +1 : -1), 0, WS/2 - 1)
+//     col(cx) = 3 C[cy0][cx] + C[cyn][cx]                          (0 .. 1020)
+//     C'(y, x) = (3 col(cx0) + col(cxn) + (x & 1 ? 7 : 8)) >> 4    (0 .. 255)
+// U', V' then go with Y[y][x] through the formulas above, unchanged: a linear frame gives the
+// bits of a yuv444p frame that carries (Y, U', V'), and the accumulator bound holds because
+// U', V' are bytes.
 // No HIP in this header: the sanitizer programs of the host codec include it.
 #pragma once
 #include <stddef.h>
@@ -76,6 +87,10 @@ inline bool yuv_coeffs(int matrix, int range, YuvCoeffs* k) {
 
 // Bytes of one frame (HS, WS even).
 inline int64_t yuv420_bytes(int HS, int WS) { return (int64_t)HS * WS / 2 * 3; }
+
+// The widest frame b64_yuv_linear_instances serves: one row pair with its chroma halo, 5 WS bytes
+// and 24 of slack rounded up to 16, and the kernel's 24 KB of float staging fill 64 KB of LDS.
+constexpr int kYuv420LinearMaxWS = 8186;
 
 // Packed 4:2:2: whether `format` is one, the bytes of one frame (WS even), and the byte offsets
 // of Y0 / Y1 / U / V in a macropixel (the host twin and the kernel both take them from here).
@@ -149,6 +164,47 @@ inline bool yuv420_to_rgb_host(const uint8_t* src, int HS, int WS, int format, c
       const size_t ci = (size_t)(y >> 1) * cw + (size_t)(x >> 1);
       const int U = format == YUV_NV12 ? chroma[2 * ci] : chroma[ci];
       const int V = format == YUV_NV12 ? chroma[2 * ci + 1] : chroma[hw / 4 + ci];
+      uint8_t px[3];
+      yuv_pixel_rgb(k, src[(size_t)y * WS + x], U, V, px);
+      const size_t o = ((size_t)y * WS + x) * 3;
+      for (int c = 0; c < 3; ++c) {
+        if (rgb) rgb[o + c] = px[c];
+        if (f32) f32[o + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
+      }
+    }
+  return true;
+}
+
+// One triangle-filtered chroma sample (the header's formulas): plane C with `step` bytes between
+// the samples of a row and `stride` between rows (I420: 1, WS/2; NV12: 2, WS), of ch x cw samples.
+inline int yuv420_linear_chroma(const uint8_t* C, size_t stride, size_t step, int ch, int cw, int y,
+                                int x) {
+  const int cy0 = y >> 1, cx0 = x >> 1;
+  int cyn = cy0 + ((y & 1) ? 1 : -1), cxn = cx0 + ((x & 1) ? 1 : -1);
+  cyn = cyn < 0 ? 0 : cyn > ch - 1 ? ch - 1 : cyn;
+  cxn = cxn < 0 ? 0 : cxn > cw - 1 ? cw - 1 : cxn;
+  const auto col = [&](int cx) {
+    return 3 * (int)C[(size_t)cy0 * stride + (size_t)cx * step] +
+           (int)C[(size_t)cyn * stride + (size_t)cx * step];
+  };
+  return (3 * col(cx0) + col(cxn) + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+// yuv420_to_rgb_host with the triangle-filtered chroma of input-yuv-chroma "linear": the host twin
+// of the b64_yuv_linear_instances kernel. Same arguments, same refusals.
+inline bool yuv420_linear_to_rgb_host(const uint8_t* src, int HS, int WS, int format,
+                                      const YuvCoeffs& k, uint8_t* rgb, float* f32,
+                                      const float* a = nullptr, const float* b = nullptr) {
+  if (HS <= 0 || WS <= 0 || (HS & 1) || (WS & 1)) return false;
+  if (format != YUV_I420 && format != YUV_NV12) return false;
+  const size_t hw = (size_t)HS * WS;
+  const bool nv12 = format == YUV_NV12;
+  const uint8_t *const up = src + hw, *const vp = nv12 ? up + 1 : up + hw / 4;
+  const size_t stride = nv12 ? (size_t)WS : (size_t)WS / 2, step = nv12 ? 2 : 1;
+  for (int y = 0; y < HS; ++y)
+    for (int x = 0; x < WS; ++x) {
+      const int U = yuv420_linear_chroma(up, stride, step, HS / 2, WS / 2, y, x);
+      const int V = yuv420_linear_chroma(vp, stride, step, HS / 2, WS / 2, y, x);
       uint8_t px[3];
       yuv_pixel_rgb(k, src[(size_t)y * WS + x], U, V, px);
       const size_t o = ((size_t)y * WS + x) * 3;

@@ -275,6 +275,28 @@ hipError_t b64_yuv_instances(int images, const B64Image* imgs, const uint8_t* by
                              const int* d_images, const InputPrep* prep, int format,
                              const YuvCoeffs& coeffs, int pairs = 0);
 
+// GPU decoder of the same records with triangle-filtered chroma (input-yuv-chroma "linear",
+// b64_yuv_linear.hip): the arguments, descriptor table, status words, d_images early exit and
+// read bounds of b64_yuv_instances. Pixel (y, x) takes Y[y][x] and U', V' of yuv.h's linear
+// formulas (libjpeg's h2v2_fancy_upsample: 3:1 in both directions, centre sited, the first and
+// last chroma row and column replicated) through the same integer matrix: the bits of
+// codec::yuv420_linear_to_rgb_host, and of a yuv444p frame that carries (Y, U', V').
+// A workgroup owns `pairs` whole row pairs (pairs = 0: b64_yuv_linear_pairs(HS, WS), about 4096
+// pixels) and decodes their luma and chroma rows p0 - 1 .. p0 + pairs, clamped to the frame, into
+// LDS. A lane then converts a block of 2 rows x 8 columns once, from its luma and the 3 x 6
+// chroma samples around it, and the floats are re-staged through per-wave LDS one image row at a
+// time: 16-byte stores when WS mod 4 == 0 and the image's base is 16-byte aligned, 8-byte stores
+// otherwise, contiguous over a wave. One workgroup barrier, no atomics.
+// hipErrorInvalidValue, before any launch: what b64_yuv_instances refuses, with
+// b64_yuv_linear_lds_bytes(WS, pairs) > kYuvLdsBudget for the block (a single row pair of
+// WS > kYuv420LinearMaxWS = 8186). images == 0 launches nothing.
+int b64_yuv_linear_pairs(int HS, int WS);
+size_t b64_yuv_linear_lds_bytes(int WS, int pairs);
+hipError_t b64_yuv_linear_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                    int WS, int C, float* out, int* status, hipStream_t stream,
+                                    const int* d_images, const InputPrep* prep, int format,
+                                    const YuvCoeffs& coeffs, int pairs = 0);
+
 // GPU decoders of packed YUV 4:2:2 video-frame records (input pixel formats "yuyv422" /
 // "uyvy422", yuv422.hip), one for either encoding. A frame is B = 2*HS*WS bytes, [HS][WS/2]
 // macropixels of 4 bytes (csrc/codec/yuv.h: the byte offsets; WS even, HS any), and becomes the

@@ -9,7 +9,8 @@ namespace gale {
 // The decode launch of b64 strings that carry `src` (csrc/codec/pixel_source.h): exactly one of
 // the b64 launchers of gale/kernels.h, or raw_instances for a raw source (a packed 4:2:2 frame:
 // b64_yuv422_instances or raw_yuv422_instances; a planar 4:2:2 / 4:4:4 frame: b64_yuvp_instances
-// or raw_yuvp_instances; a raw 10-bit 4:2:0 frame: raw_yuv420p10_instances), with these arguments. *which (optional): that
+// or raw_yuvp_instances; a raw 10-bit 4:2:0 frame: raw_yuv420p10_instances; a b64 4:2:0 frame with
+// linear chroma: b64_yuv_linear_instances), with these arguments. *which (optional): that
 // launcher's name.
 inline hipError_t b64_source_instances(int images, const B64Image* imgs, const uint8_t* bytes,
                                        int HS, int WS, int C, float* out, int* status,
@@ -40,6 +41,11 @@ inline hipError_t b64_source_instances(int images, const B64Image* imgs, const u
     if (k == PixelSource::YUV) return hipErrorInvalidValue;  // (PixelSource::check refuses it)
     return raw_instances(images, imgs, bytes, HS, WS, C, out, status, stream, d_images, prep,
                          src.elem(), src.packed_format());
+  }
+  if (src.chroma_linear()) {  // (b64 i420 / nv12: PixelSource::check refuses anything else)
+    if (which) *which = "b64_yuv_linear_instances";
+    return b64_yuv_linear_instances(images, imgs, bytes, HS, WS, C, out, status, stream, d_images,
+                                    prep, src.yuv_format(), src.yuv());
   }
   if (which)
     *which = k == PixelSource::PACKED  ? "b64_packed_instances"

@@ -56,6 +56,9 @@ CHOICES = {
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
+    # how b64 i420 / nv12 chroma becomes full resolution: the nearest sample, or libjpeg's
+    # centre-sited 3:1 triangle filter (gale/models/preprocess.py YuvLinearConvert)
+    "input_yuv_chroma": ("nearest", "linear"),
     # the element type of an rgb b64 string or raw image (gale/models/preprocess.py ElemType): one uint8 a
     # value, or little-endian 16-bit / float elements converted exactly on the GPU
     "input_dtype": ("u8", "u16", "f16", "bf16", "f32"),
@@ -101,6 +104,10 @@ HELP = {
     "input_yuv_matrix": "bt601 (default) or bt709; only with a YUV --input-pixel-format",
     "input_yuv_range": "limited (default: Y 16..235, chroma 16..240) or full; only with a YUV "
                        "--input-pixel-format",
+    "input_yuv_chroma": "nearest (default): a pixel takes the chroma sample of its 2x2 quad; "
+                        "linear: libjpeg's fancy upsampling, a centre-sited 3:1 triangle filter "
+                        "in both directions, on the GPU; linear needs --input-format b64, "
+                        "--input-pixel-format i420 or nv12 and WS <= 8186",
     "input_dtype": "the element type of every b64 string or raw image: u8 (default) one byte a value; u16 / f16 "
                    "/ bf16 / f32: HS*WS*C little-endian elements of 2 / 2 / 2 / 4 bytes, converted "
                    "exactly to float32 on the GPU before --input-scale / --input-mean / "
@@ -242,6 +249,7 @@ class GaleConfig:
                                        # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
+    input_yuv_chroma: str = "nearest"  # linear: triangle-filtered chroma, b64 i420 | nv12 only
     input_dtype: str = "u8"            # u16 | f16 | bf16 | f32: rgb b64 strings or raw images carry
                                        # little-endian elements of that type
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
@@ -367,6 +375,16 @@ class GaleConfig:
                 if getattr(self, k):
                     raise ValueError(f"--{k.replace('_', '-')} applies to the YUV formats only: "
                                      "it needs --input-pixel-format i420 or nv12")
+        if self.input_yuv_chroma == "linear":
+            from gale.models.preprocess import YUV_LINEAR_MAX_WS
+
+            if fmt not in ("i420", "nv12") or self.input_format != "b64":
+                raise ValueError("--input-yuv-chroma linear needs --input-format b64 and "
+                                 f"--input-pixel-format i420 or nv12, not {self.input_format} "
+                                 f"records of {fmt}")
+            if rs.WS > YUV_LINEAR_MAX_WS:
+                raise ValueError(f"--input-yuv-chroma linear serves WS <= {YUV_LINEAR_MAX_WS} "
+                                 f"(a row pair with its chroma halo in LDS), got {rs.WS}")
         if fmt == "rgb":
             return
         from gale.models import get_model
@@ -415,12 +433,14 @@ class GaleConfig:
         return ElemType.from_config(self)
 
     def input_yuv(self):
-        """The ``YuvConvert`` (4:2:0), ``Yuv422Convert`` (packed 4:2:2), ``YuvPlanarConvert``
+        """The ``YuvConvert`` (4:2:0; ``YuvLinearConvert`` with linear chroma), ``Yuv422Convert`` (packed 4:2:2), ``YuvPlanarConvert``
         (planar 4:2:2 / 4:4:4) or ``Yuv420HiConvert`` (10-bit 4:2:0) of this configuration, None
         for rgb and the packed pixel formats."""
         from gale.models.preprocess import (Yuv420HiConvert, Yuv422Convert, YuvConvert,
-                                            YuvPlanarConvert)
+                                            YuvLinearConvert, YuvPlanarConvert)
 
+        if self.input_yuv_chroma == "linear":  # (validate(): b64 i420 / nv12 only)
+            return YuvLinearConvert.from_config(self)
         return (YuvConvert.from_config(self) or Yuv422Convert.from_config(self)
                 or YuvPlanarConvert.from_config(self) or Yuv420HiConvert.from_config(self))
 

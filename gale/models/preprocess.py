@@ -511,6 +511,50 @@ class YuvConvert:
         return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
 
 
+YUV_CHROMA = ("nearest", "linear")
+
+
+@dataclass(frozen=True)
+class YuvLinearConvert(YuvConvert):
+    """``YuvConvert`` with triangle-filtered chroma (``--input-yuv-chroma linear``): libjpeg's
+    ``h2v2_fancy_upsample``, a centre-sited 3:1 filter in both directions, in integers.
+
+    For output pixel (y, x) and a chroma plane ``C`` of ``HS/2 x WS/2``::
+
+        cy0 = y >> 1     cyn = clamp(cy0 + (y & 1 ? +1 : -1), 0, HS/2 - 1)
+        cx0 = x >> 1     cxn = clamp(cx0 + (x & 1 ? +1 : -1), 0, WS/2 - 1)
+        col(cx) = 3 C[cy0][cx] + C[cyn][cx]
+        C'(y, x) = (3 col(cx0) + col(cxn) + (x & 1 ? 7 : 8)) >> 4
+
+    ``U'`` and ``V'`` then go with ``Y[y][x]`` through ``YuvConvert``'s formulas unchanged, so a
+    frame gives the bits of a ``yuv444p`` frame that carries ``(Y, U', V')``.
+    ``codec::yuv420_linear_to_rgb_host`` and the ``b64_yuv_linear_instances`` kernel give the same
+    bits. b64 records only; WS at most ``YUV_LINEAR_MAX_WS`` (the kernel's LDS bound)."""
+
+    def engine_entries(self) -> Dict[str, Any]:
+        return dict(super().engine_entries(), yuv_chroma="linear")
+
+    @staticmethod
+    def upsample(C) -> np.ndarray:
+        """uint8 [..., HS/2, WS/2] -> int64 [..., HS, WS]: the formulas above, directly."""
+        C = np.asarray(C).astype(np.int64)
+        ch, cw = C.shape[-2:]
+        y, x = np.arange(2 * ch), np.arange(2 * cw)
+        cyn = np.clip((y >> 1) + np.where(y & 1, 1, -1), 0, ch - 1)
+        cxn = np.clip((x >> 1) + np.where(x & 1, 1, -1), 0, cw - 1)
+        col = 3 * C[..., y >> 1, :] + C[..., cyn, :]
+        return (3 * col[..., x >> 1] + col[..., cxn] + np.where(x & 1, 7, 8)) >> 4
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint8 [..., HS, WS, 3] RGB."""
+        Y, U, V = self.planes(frame, HS, WS)
+        acc = self.accumulators(Y, self.upsample(U), self.upsample(V))
+        assert all(np.abs(a).max(initial=0) < 1 << 31 for a in acc)
+        return np.stack([np.clip(a >> YUV_SHIFT, 0, 255) for a in acc], axis=-1).astype(np.uint8)
+
+
+YUV_LINEAR_MAX_WS = 8186  # (csrc/codec/yuv.h kYuv420LinearMaxWS)
+
 # the packed 4:2:2 formats: name -> byte offset in a macropixel of (Y0, Y1, U, V)
 YUV422_FORMATS = {"yuyv422": (0, 2, 1, 3), "uyvy422": (1, 3, 0, 2)}
 

@@ -369,6 +369,24 @@ def b64_yuv_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torc
     4 * (HS*WS*3/2) / 3 characters. ``yuv``: a ``gale.models.preprocess.YuvConvert`` (format and
     coefficient table). ``pairs``: row pairs per workgroup (0 = the launcher's choice). A shape or
     argument the launcher refuses raises ``ValueError`` before anything is launched."""
+    return _yuv420_instances("b64_yuv_instances", staged, table, size, out, status, yuv, images,
+                             d_images, prep, pairs)
+
+
+def b64_yuv_linear_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                             status: torch.Tensor, yuv, images: Optional[int] = None,
+                             d_images: Optional[torch.Tensor] = None, prep=None,
+                             pairs: int = 0) -> torch.Tensor:
+    """``b64_yuv_instances`` with triangle-filtered chroma (``--input-yuv-chroma linear``): the
+    same arguments; ``yuv``: a ``gale.models.preprocess.YuvLinearConvert`` (or any ``YuvConvert``
+    of i420 / nv12: format and coefficient table). WS is at most ``YUV_LINEAR_MAX_WS``. There is
+    no CPU path: a shape or argument the launcher refuses raises ``ValueError`` before anything is
+    launched."""
+    return _yuv420_instances("b64_yuv_linear_instances", staged, table, size, out, status, yuv,
+                             images, d_images, prep, pairs)
+
+
+def _yuv420_instances(name, staged, table, size, out, status, yuv, images, d_images, prep, pairs):
     HS, WS = (int(v) for v in size)
     _check(staged, torch.uint8, "staged")
     _check(table, torch.int32, "table")
@@ -384,15 +402,15 @@ def b64_yuv_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torc
     if d_images is not None:
         _check(d_images, torch.int32, "d_images")
     kw = prep.kernel_kwargs() if prep is not None else {}
-    err = native().b64_yuv_instances(n, table.data_ptr(), staged.data_ptr(), HS, WS, 3,
-                                     out.data_ptr(), status.data_ptr(), _stream(),
-                                     d_images.data_ptr() if d_images is not None else 0,
-                                     pairs=int(pairs), **yuv.kernel_kwargs(), **kw)
+    err = getattr(native(), name)(n, table.data_ptr(), staged.data_ptr(), HS, WS, 3,
+                                  out.data_ptr(), status.data_ptr(), _stream(),
+                                  d_images.data_ptr() if d_images is not None else 0,
+                                  pairs=int(pairs), **yuv.kernel_kwargs(), **kw)
     if err == native().HIP_ERROR_INVALID_VALUE:
-        raise ValueError(f"b64_yuv_instances: the launcher refused {HS}x{WS} {yuv.format} "
+        raise ValueError(f"{name}: the launcher refused {HS}x{WS} {yuv.format} "
                          f"(pairs={pairs}, images={n})")
     if err != 0:
-        raise RuntimeError(f"b64_yuv_instances: HIP error {err}")
+        raise RuntimeError(f"{name}: HIP error {err}")
     return out
 
 
