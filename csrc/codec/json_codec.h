@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "bayer.h"
 #include "elemtype.h"
 #include "pixfmt.h"
 #include "yuv.h"
@@ -169,6 +170,13 @@ int parse_instances_raw_yuvp_host(const uint8_t* p, size_t n, int HS, int WS, in
 int parse_instances_raw_yuv420p10_host(const uint8_t* p, size_t n, int HS, int WS, int format,
                                        const YuvCoeffs& k, float* out, int max_images,
                                        int* images);
+
+// Host decoder of raw 8-bit Bayer mosaic records (bayer.h; there is no b64 form): the value is N
+// frames of bayer_bytes(HS, WS) bytes, demosaiced by bayer_to_rgb_host to (float)RGB[c]. The
+// verdicts of parse_instances_raw_host; odd or non-positive sizes or an unknown order are
+// BAD_SHAPE.
+int parse_instances_raw_bayer_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                   float* out, int max_images, int* images);
 
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes

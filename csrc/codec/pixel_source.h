@@ -1,6 +1,7 @@
 // What the b64 strings of a topology carry (engine keys pixel_format and input_dtype):
 // interleaved RGB bytes, a YUV 4:2:0, packed 4:2:2, planar 4:2:2 / 4:4:4 or 10-bit 4:2:0 (raw
-// only) frame (yuv.h), packed pixels (pixfmt.h) or a typed tensor
+// only) frame (yuv.h), packed pixels (pixfmt.h), an 8-bit Bayer mosaic (bayer.h, raw only) or a
+// typed tensor
 // (elemtype.h: the rgb layout with 16-bit or float elements). PixelSource is the one holder of
 // {yuv format, YuvCoeffs, packed format, element type} and of the rules about them: the configuration names,
 // the bytes of a string, what a topology may combine them with, what the ingest sees and which
@@ -14,6 +15,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "bayer.h"
 #include "elemtype.h"
 #include "json_codec.h"
 #include "pixfmt.h"
@@ -23,7 +25,7 @@ namespace gale {
 
 class PixelSource {
  public:
-  enum Kind { RGB, YUV, PACKED, TYPED };
+  enum Kind { RGB, YUV, PACKED, TYPED, BAYER };
   // the dimensions of an image whose string is as long as this source's (ingest_dims)
   struct Dims {
     int H, W, C;
@@ -32,13 +34,15 @@ class PixelSource {
   PixelSource() = default;  // rgb
 
   // From the configuration names: pixel_format rgb | i420 | nv12 | yuyv422 | uyvy422 | yuv422p |
-  // yuv444p | p010le | yuv420p10le | bgr24 | rgba | bgra | gray;
+  // yuv444p | p010le | yuv420p10le | bgr24 | rgba | bgra | gray | bayer_rggb8 | bayer_bggr8 |
+  // bayer_grbg8 | bayer_gbrg8;
   // yuv_matrix bt601 | bt709 and yuv_range limited | full, null where the configuration does not
   // name one (bt601, limited; naming one with a packed format is refused).
   static PixelSource from_names(const std::string& pixel_format, const std::string* yuv_matrix,
                                 const std::string* yuv_range) {
     PixelSource s;
     s.packed_format_ = packed_format_of(pixel_format.c_str());
+    s.bayer_order_ = bayer_order_of(pixel_format.c_str());
     if (pixel_format == "i420" || pixel_format == "nv12")
       s.yuv_format_ = pixel_format == "i420" ? (int)YUV_I420 : (int)YUV_NV12;
     else if (pixel_format == "yuyv422" || pixel_format == "uyvy422")
@@ -47,9 +51,9 @@ class PixelSource {
       s.yuv_format_ = pixel_format == "yuv422p" ? (int)YUV_YUV422P : (int)YUV_YUV444P;
     else if (pixel_format == "p010le" || pixel_format == "yuv420p10le")
       s.yuv_format_ = pixel_format == "p010le" ? (int)YUV_P010LE : (int)YUV_YUV420P10LE;
-    else if (pixel_format != "rgb" && !s.packed_format_)
+    else if (pixel_format != "rgb" && !s.packed_format_ && !s.bayer_order_)
       throw std::invalid_argument("pixel_format: rgb, i420, nv12, bgr24, rgba, bgra or gray");
-    if (s.packed_format_ && (yuv_matrix || yuv_range))
+    if ((s.packed_format_ || s.bayer_order_) && (yuv_matrix || yuv_range))
       throw std::invalid_argument("yuv_matrix / yuv_range need pixel_format i420 or nv12");
     const std::string ym = yuv_matrix ? *yuv_matrix : "bt601";
     const std::string yr = yuv_range ? *yuv_range : "limited";
@@ -67,7 +71,7 @@ class PixelSource {
     PixelSource s = *this;
     s.elem_ = elem_type_of(input_dtype.c_str());
     if (s.elem_ < 0) throw std::invalid_argument("input_dtype: u8, u16, f16, bf16 or f32");
-    if (s.elem_ != ELEM_U8 && (packed_format_ || yuv_format_))
+    if (s.elem_ != ELEM_U8 && (packed_format_ || yuv_format_ || bayer_order_))
       throw std::invalid_argument("input_dtype " + input_dtype + " needs pixel_format rgb");
     return s;
   }
@@ -93,7 +97,11 @@ class PixelSource {
   bool raw() const { return raw_; }  // the encoding: raw bytes, else b64 strings
 
   Kind kind() const {
-    return packed_format_ ? PACKED : yuv_format_ ? YUV : elem_ != ELEM_U8 ? TYPED : RGB;
+    return bayer_order_    ? BAYER
+           : packed_format_ ? PACKED
+           : yuv_format_    ? YUV
+           : elem_ != ELEM_U8 ? TYPED
+                              : RGB;
   }
   int yuv_format() const { return yuv_format_; }        // YuvFormat (YUV_NONE unless YUV)
   bool yuv422() const { return yuv_is_422(yuv_format_); }  // a packed 4:2:2 frame (kind YUV)
@@ -102,10 +110,12 @@ class PixelSource {
   const YuvCoeffs& yuv() const { return yuv_; }
   int packed_format() const { return packed_format_; }  // PackedFormat (PACKED_NONE unless PACKED)
   int elem() const { return elem_; }                    // InputElem (ELEM_U8 unless TYPED)
+  int bayer_order() const { return bayer_order_; }      // BayerOrder (BAYER_NONE unless BAYER)
 
   // Bytes one string carries for record-side images of HS x WS (x C for rgb, x C x E typed).
   int64_t bytes(int HS, int WS, int C) const {
-    return kind() == PACKED ? packed_bytes(HS, WS, packed_format_)
+    return kind() == BAYER  ? bayer_bytes(HS, WS)
+           : kind() == PACKED ? packed_bytes(HS, WS, packed_format_)
            : yuv422()       ? yuv422_bytes(HS, WS)
            : planar()       ? yuvp_bytes(HS, WS, yuv_format_)
            : hi420()        ? yuv420p10_bytes(HS, WS)
@@ -117,7 +127,7 @@ class PixelSource {
   // record-side HS x WS, input_format b64 or raw (input_b64: one of the two). A raw source
   // carries no YUV 4:2:0 frame; a packed 4:2:2 frame goes with either encoding, any HS and an
   // even WS, and so does a planar frame (yuv444p: any WS); a 10-bit 4:2:0 frame goes with raw
-  // only and even HS, WS. std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
+  // only and even HS, WS, and so does a Bayer mosaic. std::invalid_argument otherwise; rgb goes with all, a typed tensor with everything
   // rgb b64 records go with.
   // uniform_prep: whether the prep's four coefficient pairs are equal (a typed tensor may have
   // C > 4, which the decoders serve with uniform coefficients only: b64::prep_fits; the Python
@@ -143,6 +153,15 @@ class PixelSource {
       if (C > 4 && !uniform_prep)
         throw std::invalid_argument(std::string("input_dtype ") + elem_type_name(elem_) +
                                     ": per-channel input_a / input_b need C <= 4");
+      return;
+    }
+    if (kind() == BAYER) {
+      const std::string what = "pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / bayer_gbrg8";
+      if (!input_b64 || !raw_) throw std::invalid_argument(what + " needs input_format raw");
+      if (nchw) throw std::invalid_argument(what + ": no nchw layout");
+      if (C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
+      if (HS <= 0 || WS <= 0 || ((HS | WS) & 1))
+        throw std::invalid_argument(what + " needs even record-side H, W");
       return;
     }
     const std::string what = yuv422()        ? "pixel_format yuyv422 / uyvy422"
@@ -171,11 +190,13 @@ class PixelSource {
   // 4:2:2 frame's that of an HS x WS x 2 one, a planar frame's that of an HS x WS x 2 (yuv422p)
   // or x 3 (yuv444p) one, a packed-pixel
   // string that of an HS x WS x P one, a typed tensor's string that of an HS x (WS E) x C one -
+  // a Bayer mosaic's that of an HS x WS x 1 one;
   // the element size widens a row, not the channel count, because the ingest's launcher applies
   // the C > 4 coefficient rule to the C it is given even when it decodes nothing.
   // (There is no arena for any of them, so nothing is decoded.)
   Dims ingest_dims(int HS, int WS, int C) const {
-    return kind() == PACKED ? Dims{HS, WS, packed_bpp(packed_format_)}
+    return kind() == BAYER  ? Dims{HS, WS, 1}
+           : kind() == PACKED ? Dims{HS, WS, packed_bpp(packed_format_)}
            : yuv422()       ? Dims{HS, WS, 2}
            : planar()       ? Dims{HS, WS, 3 - yuvp_shift(yuv_format_)}
            : hi420()        ? Dims{HS, WS, 3}
@@ -187,6 +208,10 @@ class PixelSource {
   // (json_codec.h), with its status, image count and floats.
   int parse_host(const uint8_t* p, size_t n, int HS, int WS, int C, float* out, int max_images,
                  int* images) const {
+    if (kind() == BAYER)  // (raw only: check() refuses the b64 form)
+      return raw_ ? codec::parse_instances_raw_bayer_host(p, n, HS, WS, bayer_order_, out,
+                                                          max_images, images)
+                  : (int)codec::BAD_SHAPE;
     if (yuv422())
       return raw_ ? codec::parse_instances_raw_yuv422_host(p, n, HS, WS, yuv_format_, yuv_, out,
                                                            max_images, images)
@@ -221,6 +246,7 @@ class PixelSource {
   int yuv_format_ = YUV_NONE;
   YuvCoeffs yuv_;
   int packed_format_ = PACKED_NONE;
+  int bayer_order_ = BAYER_NONE;
   int elem_ = ELEM_U8;
   bool raw_ = false;
   bool chroma_linear_ = false;

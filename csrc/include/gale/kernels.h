@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../codec/bayer.h"  // BayerOrder (no HIP: shared with the host codec)
 #include "../../codec/elemtype.h"  // InputElem (no HIP: shared with the host codec)
 #include "../../codec/pixfmt.h"  // PackedFormat (no HIP: shared with the host codec)
 #include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
@@ -380,6 +381,29 @@ hipError_t raw_yuv420p10_instances(int images, const B64Image* imgs, const uint8
                                    int WS, int C, float* out, int* status, hipStream_t stream,
                                    const int* d_images, const InputPrep* prep, int format,
                                    const YuvCoeffs& coeffs);
+
+// GPU demosaic of raw 8-bit Bayer mosaic records (input pixel formats "bayer_rggb8" /
+// "bayer_bggr8" / "bayer_grbg8" / "bayer_gbrg8", bayer.hip), with the arguments, descriptor table
+// and early exit of raw_yuv420p10_instances. A frame of HS x WS pixels (both even) is B = HS*WS
+// bytes S[HS][WS]; order (BayerOrder, csrc/codec/bayer.h) names the colours of the tile at
+// (0, 0). Pixel (y, x) becomes three floats of the fp32 NHWC batch tensor,
+// fmaf((float)RGB[c], a[c], b[c]) with RGB the rounded bilinear demosaic of bayer.h over the 3 x 3
+// neighbourhood at mirrored indices (-1 -> 1, n -> n - 2): the bits of codec::bayer_to_rgb_host.
+// imgs[].off is the byte offset of the frame's first byte, any phase, and `bytes` may be any
+// byte: only aligned dwords that hold a byte of the frame are read. status is never written (it
+// must still be given).
+// The grid is ceil((HS/2) ceil(WS/8) / T) x images, T = 64 threads for a frame of at most 64
+// blocks and 256 otherwise. A lane loads rows 2 r - 1 .. 2 r + 2 (mirrored rows are other rows of
+// the frame) around its block of 2 rows x 8 columns, converts the block once, in registers, and
+// the floats are re-staged through per-wave LDS one image row at a time: 16-byte stores when
+// WS mod 4 == 0 and the image's base is 16-byte aligned, 8-byte stores otherwise. No workgroup
+// barrier, no atomics.
+// hipErrorInvalidValue, before any launch: a null pointer, odd or non-positive HS / WS, C != 3,
+// an unknown order, an nchw prep, more than 65535 images, a frame of more than 2^30 floats.
+// images == 0 launches nothing.
+hipError_t raw_bayer_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                               int WS, int C, float* out, int* status, hipStream_t stream,
+                               const int* d_images, const InputPrep* prep, int order);
 
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard

@@ -36,6 +36,12 @@ inline hipError_t b64_source_instances(int images, const B64Image* imgs, const u
     return raw_yuv420p10_instances(images, imgs, bytes, HS, WS, C, out, status, stream, d_images,
                                    prep, src.yuv_format(), src.yuv());
   }
+  if (k == PixelSource::BAYER) {  // (a raw 8-bit Bayer mosaic: bayer.hip)
+    if (which) *which = "raw_bayer_instances";
+    if (!src.raw()) return hipErrorInvalidValue;  // (PixelSource::check refuses it)
+    return raw_bayer_instances(images, imgs, bytes, HS, WS, C, out, status, stream, d_images, prep,
+                               src.bayer_order());
+  }
   if (src.raw()) {
     if (which) *which = "raw_instances";
     if (k == PixelSource::YUV) return hipErrorInvalidValue;  // (PixelSource::check refuses it)

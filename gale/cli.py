@@ -15,7 +15,7 @@
                                                       raw: the images' bytes, no envelope
         [--size H,W]                                  images of that size (--input-size H,W)
         [--pixel-format rgb|i420|nv12|yuyv422|uyvy422|yuv422p|yuv444p|p010le|yuv420p10le|
-                        bgr24|rgba|bgra|gray]
+                        bgr24|rgba|bgra|gray|bayer_rggb8|bayer_bggr8|bayer_grbg8|bayer_gbrg8]
                                                       YUV 4:2:0 frames / packed pixels
                                                       (--encoding b64; --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
@@ -215,7 +215,8 @@ def cmd_produce(argv: List[str]) -> int:
     import numpy as np
 
     from gale._native import native
-    from gale.data import (encode_records, encode_records_b64, encode_records_text,
+    from gale.data import (encode_records, encode_records_b64, encode_records_bayer,
+                           encode_records_text,
                            encode_records_packed, encode_records_raw, encode_records_typed,
                            encode_records_yuv, encode_records_yuv420p10, encode_records_yuv422,
                            encode_records_yuvp, synthetic_images, synthetic_pixels,
@@ -254,7 +255,10 @@ def cmd_produce(argv: List[str]) -> int:
                          "--encoding b64 or raw, the nhwc layout, a 3-channel model and, for "
                          "yuv422p, an even width; p010le / yuv420p10le: synthetic 10-bit 4:2:0 "
                          "frames of 3*HS*WS bytes; --encoding raw only, the nhwc layout, a "
-                         "3-channel model and even sizes; bgr24 / rgba / bgra / gray: the "
+                         "3-channel model and even sizes; bayer_*8: the synthetic pixels of rgb "
+                         "sampled through that colour-filter mosaic, HS*WS bytes; --encoding raw "
+                         "only, the nhwc layout, a 3-channel model and even sizes; bgr24 / rgba "
+                         "/ bgra / gray: the "
                          "synthetic pixels of rgb in that byte order (alpha random; gray: their "
                          "first channel alone); needs --encoding b64, the nhwc layout and a "
                          "3-channel model")
@@ -273,9 +277,12 @@ def cmd_produce(argv: List[str]) -> int:
     packed = a.pixel_format in ("bgr24", "rgba", "bgra", "gray")
     planar = a.pixel_format in ("yuv422p", "yuv444p")
     yuv422 = a.pixel_format in ("yuyv422", "uyvy422") or planar  # (either encoding)
-    yuv = a.pixel_format != "rgb" and not packed
+    bayer = a.pixel_format.startswith("bayer_")
+    yuv = a.pixel_format != "rgb" and not packed and not bayer
     hi = a.pixel_format in ("p010le", "yuv420p10le")
-    if hi and not raw:
+    if bayer and a.layout != "nhwc":
+        ap.error(f"--pixel-format {a.pixel_format} has its own site order: no --layout nchw")
+    if (hi or bayer) and not raw:
         ap.error(f"--pixel-format {a.pixel_format} needs --encoding raw")
     if (yuv or packed) and a.encoding != "b64" and not (raw and (packed or yuv422 or hi)):
         ap.error(f"--pixel-format {a.pixel_format} needs --encoding b64"
@@ -291,7 +298,13 @@ def cmd_produce(argv: List[str]) -> int:
         shape = produce_shape(net.input_shape, a.size)
     except ValueError as e:
         ap.error(str(e))
-    if hi:
+    if bayer:
+        if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
+            ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
+                     f"{shape}")
+        recs = encode_records_bayer(synthetic_pixels(a.images, shape, a.seed), a.pixel_format,
+                                    a.images_per_record)
+    elif hi:
         if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
             ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
                      f"{shape}")

@@ -50,9 +50,11 @@ CHOICES = {
     # 4:4:4 frame (yuv422p / yuv444p: Y, U, V planes with full-height chroma, what a JPEG decoder
     # hands back; b64 or raw; YuvPlanarConvert), or a 10-bit 4:2:0 frame of 16-bit words (p010le:
     # what hardware video decoders write; yuv420p10le: what software decoders write; raw only;
-    # Yuv420HiConvert). The names are ffmpeg's pix_fmts
+    # Yuv420HiConvert), or an 8-bit Bayer mosaic, one byte a pixel (bayer_*8: what machine-vision
+    # cameras hand out; raw only; BayerConvert). The names are ffmpeg's pix_fmts
     "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray", "yuyv422",
-                           "uyvy422", "yuv422p", "yuv444p", "p010le", "yuv420p10le"),
+                           "uyvy422", "yuv422p", "yuv444p", "p010le", "yuv420p10le",
+                           "bayer_rggb8", "bayer_bggr8", "bayer_grbg8", "bayer_gbrg8"),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -93,7 +95,12 @@ HELP = {
                           "UV, the ten bits at the top; yuv420p10le: Y, U, V planes, the ten "
                           "bits at the bottom; HS, WS even; a 3-channel model; --input-format "
                           "raw only), converted on the GPU to RGB in quarter steps of the 8-bit "
-                          "scale; bgr24 / rgba / bgra / gray: every "
+                          "scale; bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / bayer_gbrg8: "
+                          "every raw image is an 8-bit Bayer mosaic of HS*WS bytes, the name "
+                          "giving the colours of the tile (0,0) (0,1) / (1,0) (1,1) (HS, WS "
+                          "even; a 3-channel model; --input-format raw only), demosaiced on the "
+                          "GPU by the rounded bilinear rule with mirrored edges; bgr24 / rgba / "
+                          "bgra / gray: every "
                           "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
                           "replicated; any HS,WS; a 3-channel model), unpacked to RGB on the GPU; "
@@ -246,6 +253,7 @@ class GaleConfig:
                                        # uyvy422: b64 strings / raw images are 4:2:2 frames;
                                        # yuv422p | yuv444p: planar 4:2:2 / 4:4:4 frames;
                                        # p010le | yuv420p10le: raw 10-bit 4:2:0 frames;
+                                       # bayer_*8: raw 8-bit Bayer mosaics;
                                        # bgr24 | rgba | bgra | gray: packed pixels (b64 or raw)
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
@@ -389,6 +397,10 @@ class GaleConfig:
             return
         from gale.models import get_model
 
+        bayer = fmt.startswith("bayer_")  # (raw only, even HS and WS)
+        if bayer and self.input_format != "raw":
+            raise ValueError(f"--input-pixel-format {fmt} needs --input-format raw: Bayer mosaics "
+                             f"are not served as {self.input_format} records")
         if hi and self.input_format != "raw":
             raise ValueError(f"--input-pixel-format {fmt} needs --input-format raw: 16-bit 4:2:0 "
                              f"frames are not served as {self.input_format} records")
@@ -397,7 +409,7 @@ class GaleConfig:
                              + (" or raw" if yuv422 else ""))
         if self.input_layout != "nhwc":
             raise ValueError(f"--input-pixel-format {fmt} has its own "
-                             f"{'plane' if yuv or planar else 'byte'} order: "
+                             f"{'plane' if yuv or planar else 'site' if bayer else 'byte'} order: "
                              "--input-layout nchw does not apply")
         C = get_model(self.model).input_shape[2]
         if C != 3:
@@ -408,6 +420,10 @@ class GaleConfig:
         if yuv and (rs.HS % 2 or rs.WS % 2):
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:0 frame (--input-pixel-format {fmt}) needs even "
+                             f"HS,WS, got {rs.HS},{rs.WS}")
+        if bayer and (rs.HS % 2 or rs.WS % 2):
+            opt = "--input-size" if self.input_size else "--input-pixel-format"
+            raise ValueError(f"{opt}: a Bayer mosaic (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
         if yuv422 and fmt != "yuv444p" and rs.WS % 2:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
@@ -445,10 +461,11 @@ class GaleConfig:
                 or YuvPlanarConvert.from_config(self) or Yuv420HiConvert.from_config(self))
 
     def input_unpack(self):
-        """The ``PixelUnpack`` of this configuration, None for rgb and the YUV formats."""
-        from gale.models.preprocess import PixelUnpack
+        """The ``PixelUnpack`` (packed pixels) or ``BayerConvert`` (Bayer mosaics) of this
+        configuration, None for rgb and the YUV formats."""
+        from gale.models.preprocess import BayerConvert, PixelUnpack
 
-        return PixelUnpack.from_config(self)
+        return PixelUnpack.from_config(self) or BayerConvert.from_config(self)
 
     def input_prep(self, C: Optional[int] = None):
         """The ``InputPrep`` of this configuration (C: the model's input channels)."""

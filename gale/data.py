@@ -266,6 +266,35 @@ def synthetic_yuv420p10_planes(n: int, HS: int, WS: int, seed: int = 0):
             rng.integers(0, 1024, (n, HS // 2, WS // 2), dtype=np.uint16))
 
 
+def mosaic_bayer(rgb_u8: np.ndarray, pixel_format: str) -> np.ndarray:
+    """uint8 RGB images [..., HS, WS, 3] (HS, WS even) -> uint8 [..., HS, WS]: the colour-filter
+    mosaic a sensor of that order sees, every site keeping its own colour of the image."""
+    from gale.models.preprocess import BAYER_FORMATS
+
+    rgb = np.asarray(rgb_u8)
+    if pixel_format not in BAYER_FORMATS:
+        raise ValueError(f"pixel_format={pixel_format!r}: expected one of {tuple(BAYER_FORMATS)}")
+    if rgb.dtype != np.uint8 or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] % 2 \
+            or rgb.shape[-2] % 2:
+        raise ValueError(f"mosaic_bayer: uint8 [..., HS, WS, 3] with even HS, WS, got {rgb.shape}")
+    green_first, blue_first = BAYER_FORMATS[pixel_format]
+    y, x = np.ogrid[:rgb.shape[-3], :rgb.shape[-2]]
+    green = ((x + y) & 1 == 1) != green_first
+    blue_row = (y & 1 == 1) != blue_first
+    return np.where(green, rgb[..., 1], np.where(blue_row, rgb[..., 2], rgb[..., 0]))
+
+
+def encode_records_bayer(rgb_u8: np.ndarray, pixel_format: str,
+                         images_per_record: int = 1) -> List[bytes]:
+    """uint8 RGB images [N, HS, WS, 3] -> raw records of Bayer mosaics (``mosaic_bayer``;
+    --input-pixel-format bayer_*8, --input-format raw): each record value is its frames' HS*WS
+    bytes back to back."""
+    frames = mosaic_bayer(rgb_u8, pixel_format)
+    frames = frames.reshape(frames.shape[0], -1)
+    return [frames[i:i + images_per_record].tobytes()
+            for i in range(0, frames.shape[0], images_per_record)]
+
+
 def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
                 alpha: Optional[np.ndarray] = None) -> np.ndarray:
     """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of

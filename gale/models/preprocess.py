@@ -819,6 +819,85 @@ class PixelUnpack:
         return np.ascontiguousarray(px[..., list(self.offsets)])
 
 
+# the Bayer orders: name -> (site (0, 0) is green, the even rows' non-green colour is blue)
+BAYER_FORMATS = {"bayer_rggb8": (False, False), "bayer_bggr8": (False, True),
+                 "bayer_grbg8": (True, False), "bayer_gbrg8": (True, True)}
+
+
+@dataclass(frozen=True)
+class BayerConvert:
+    """Raw 8-bit Bayer mosaic frames (``--input-pixel-format bayer_rggb8 | bayer_bggr8 |
+    bayer_grbg8 | bayer_gbrg8``) to interleaved RGB, in integers.
+
+    A frame of HS x WS pixels (both even) is ``B = HS*WS`` bytes ``S[HS][WS]``; the name gives the
+    colours of the tile (0,0) (0,1) / (1,0) (1,1). Indices outside the frame are mirrored without
+    repeating the edge sample (-1 -> 1, n -> n - 2), which keeps a neighbour's colour parity.
+    With ``s = S[y][x]`` and the eight neighbours at mirrored indices::
+
+        R or B site:  own = s,  G = (N+S+E+W+2) >> 2,  opposite = (NW+NE+SW+SE+2) >> 2
+        G site:       G = s,  this row's colour = (W+E+1) >> 1,  the other = (N+S+1) >> 1
+
+    the usual rounded bilinear demosaic. ``codec::bayer_to_rgb_host`` (csrc/codec/bayer.h) and the
+    ``raw_bayer_instances`` kernel give the same bytes; the ``InputPrep`` coefficients that
+    follow are indexed by model channel (R, G, B): per-channel scales are white-balance gains."""
+
+    format: str = "bayer_rggb8"
+
+    def __post_init__(self):
+        if self.format not in BAYER_FORMATS:
+            raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
+                             f"{tuple(BAYER_FORMATS)} for a Bayer mosaic")
+
+    @classmethod
+    def from_config(cls, cfg) -> Optional["BayerConvert"]:
+        """The demosaic of a configuration, None for every other pixel format."""
+        return cls(cfg.input_pixel_format) if cfg.input_pixel_format in BAYER_FORMATS else None
+
+    @staticmethod
+    def frame_bytes(HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or HS % 2 or WS % 2:
+            raise ValueError(f"a Bayer mosaic needs even, positive sizes, got {HS},{WS}")
+        return HS * WS
+
+    def engine_entries(self) -> Dict[str, Any]:
+        return dict(pixel_format=self.format)
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``raw_bayer_instances`` binding."""
+        return dict(order=self.format)
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint8 [..., HS, WS, 3] RGB."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        green_first, blue_first = BAYER_FORMATS[self.format]
+        s = f.reshape(*f.shape[:-1], HS, WS).astype(np.int32)
+        # rows / columns -1 and n are rows / columns 1 and n - 2
+        p = np.concatenate([s[..., 1:2, :], s, s[..., -2:-1, :]], axis=-2)
+        p = np.concatenate([p[..., :, 1:2], p, p[..., :, -2:-1]], axis=-1)
+        at = lambda dy, dx: p[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
+        h = (at(0, -1) + at(0, 1) + 1) >> 1
+        v = (at(-1, 0) + at(1, 0) + 1) >> 1
+        cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
+        diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
+        y, x = np.ogrid[:HS, :WS]
+        green = ((x + y) & 1 == 1) != green_first
+        blue_row = (y & 1 == 1) != blue_first  # the row's non-green colour is blue
+        own, opp = np.where(green, h, s), np.where(green, v, diag)
+        rgb = np.stack([np.where(blue_row, opp, own), np.where(green, s, cross),
+                        np.where(blue_row, own, opp)], axis=-1)
+        return rgb.astype(np.uint8)
+
+    @staticmethod
+    def to_float(rgb, prep=None) -> np.ndarray:
+        """The model-side floats of an RGB image: ``fmaf(float(RGB[c]), a[c], b[c])`` with the
+        coefficients of ``prep`` (an ``InputPrep``; None: the identity)."""
+        x = np.asarray(rgb).astype(np.float32)
+        return x if prep is None else prep.apply(x)
+
+
 # the element types of a typed tensor record: name -> (bytes per element, numpy wire dtype)
 ELEM_TYPES = {"u8": (1, "u1"), "u16": (2, "<u2"), "f16": (2, "<f2"), "bf16": (2, "<u2"),
               "f32": (4, "<f4")}

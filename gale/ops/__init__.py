@@ -505,6 +505,19 @@ def raw_yuv420p10_instances(staged: torch.Tensor, table: torch.Tensor, size, out
                              images, d_images, prep)
 
 
+def raw_bayer_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                        status: torch.Tensor, bayer, images: Optional[int] = None,
+                        d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Demosaic raw 8-bit Bayer frames (``--input-pixel-format bayer_*8``, input format ``raw``)
+    into the fp32 NHWC batch tensor ``out`` [slots, HS, WS, 3] as RGB, in place; returns ``out``.
+    Arguments as ``raw_yuvp_instances``; ``bayer``: a ``gale.models.preprocess.BayerConvert``;
+    ``size``: (HS, WS), both even; every frame is HS*WS bytes at any byte offset of ``staged``.
+    ``status`` is never written. There is no CPU path: a shape or argument the launcher refuses
+    raises ``ValueError`` before anything is launched."""
+    return _yuv422_instances("raw_bayer_instances", staged, table, size, out, status, bayer,
+                             images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
