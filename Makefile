@@ -50,6 +50,8 @@ $(OBJ)/kernels/yuv420_hi.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed
 $(OBJ)/kernels/b64_yuv_linear.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # and the Bayer demosaic: the same 24 independent fmas per row of a block
 $(OBJ)/kernels/bayer.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# and its gradient-corrected twin: the same store side
+$(OBJ)/kernels/bayer_malvar.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 gale/_C.so: $(HIP_OBJ) $(CXX_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lz -ldl -pthread \
@@ -131,6 +133,16 @@ build/asan/bayer_check: csrc/tests/bayer_check.cpp csrc/codec/json_codec.cpp \
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/bayer_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# the Malvar demosaic's host codec (csrc/tests/bayer_malvar_check.cpp): the twin against a
+# loop-form 5 x 5 filter, the raw parser's malvar form and PixelSource's rules for bayer_demosaic;
+# codec only, no engine, no HIP call
+build/asan/bayer_malvar_check: csrc/tests/bayer_malvar_check.cpp csrc/codec/json_codec.cpp \
+                               csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/bayer_malvar_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
 # linear chroma for i420 / nv12 (csrc/tests/yuv_chroma_check.cpp): the host twin against a
 # loop-form upsampler, the record parser's linear form and PixelSource's rules for yuv_chroma;

@@ -131,6 +131,12 @@ EngineConfig config_from_dict(const py::dict& d) {
       opt(d, "yuv_chroma", ch);
       c.pixels = c.pixels.with_chroma(ch);
     }
+    // the Bayer demosaic (BayerConvert.engine_entries; absent = bilinear)
+    if (d.contains("bayer_demosaic")) {
+      std::string dm = "bilinear";
+      opt(d, "bayer_demosaic", dm);
+      c.pixels = c.pixels.with_demosaic(dm);
+    }
     if (input_raw) c.pixels = c.pixels.as_raw();
   }
   opt(d, "max_batch", c.max_batch);

@@ -939,44 +939,53 @@ void bind_host(py::module_& m) {
         py::arg("max_images") = -1);
   // ---- 8-bit Bayer mosaic frames (csrc/codec/bayer.h, raw records) ----
   m.def("bayer_bytes", [](int HS, int WS) { return bayer_bytes(HS, WS); });
-  m.def("bayer_to_rgb_host",
-        [](py::bytes frame, int HS, int WS, const std::string& order,
-           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b) {
-          // one frame -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep
-          const std::string_view s = view(frame);
-          if ((a && a->size() < 3) || (b && b->size() < 3) || bool(a) != bool(b))
-            throw std::invalid_argument("bayer_to_rgb_host: a / b (>= 3 each)");
-          const int ord = bayer_order_of(order.c_str());
-          if (!ord || !bayer_bytes(HS, WS) || (int64_t)s.size() != bayer_bytes(HS, WS))
-            throw std::invalid_argument("bayer_to_rgb_host: order / size / byte count");
-          py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
-          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
-          codec::bayer_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, ord,
-                                   rgb.mutable_data(), f32.mutable_data(),
-                                   a ? a->data() : nullptr, b ? b->data() : nullptr);
-          return py::make_tuple(rgb, f32);
-        },
-        py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("order"),
-        py::arg("a") = py::none(), py::arg("b") = py::none());
+  // (the bilinear twin and the gradient-corrected one, bayer_malvar_to_rgb_host: HS, WS >= 4)
+  for (const bool malvar : {false, true}) {
+    const char* const name = malvar ? "bayer_malvar_to_rgb_host" : "bayer_to_rgb_host";
+    m.def(name,
+          [malvar, name](py::bytes frame, int HS, int WS, const std::string& order,
+                         std::optional<std::vector<float>> a, std::optional<std::vector<float>> b) {
+            // one frame -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep
+            const std::string_view s = view(frame);
+            if ((a && a->size() < 3) || (b && b->size() < 3) || bool(a) != bool(b))
+              throw std::invalid_argument(std::string(name) + ": a / b (>= 3 each)");
+            const int ord = bayer_order_of(order.c_str());
+            if (!ord || !bayer_bytes(HS, WS) || (int64_t)s.size() != bayer_bytes(HS, WS) ||
+                (malvar && (HS < 4 || WS < 4)))
+              throw std::invalid_argument(std::string(name) + ": order / size / byte count");
+            py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+            py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+            (malvar ? codec::bayer_malvar_to_rgb_host : codec::bayer_to_rgb_host)(
+                reinterpret_cast<const uint8_t*>(s.data()), HS, WS, ord, rgb.mutable_data(),
+                f32.mutable_data(), a ? a->data() : nullptr, b ? b->data() : nullptr);
+            return py::make_tuple(rgb, f32);
+          },
+          py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("order"),
+          py::arg("a") = py::none(), py::arg("b") = py::none());
+  }
   m.def("parse_instances_raw_bayer_host",
-        [](py::bytes b, int HS, int WS, const std::string& order, int max_images) {
+        [](py::bytes b, int HS, int WS, const std::string& order, int max_images,
+           const std::string& demosaic) {
           // (status, float32 [N, HS, WS, 3]: (float)RGB of every frame of the raw value)
           const std::string_view s = view(b);
           const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
           const int ord = bayer_order_of(order.c_str());
+          if (demosaic != "bilinear" && demosaic != "malvar")
+            throw std::invalid_argument("parse_instances_raw_bayer_host: demosaic bilinear | malvar");
+          const bool malvar = demosaic == "malvar";
           int n = 0;
-          int st = codec::parse_instances_raw_bayer_host(p, s.size(), HS, WS, ord, nullptr,
-                                                         max_images, &n);
+          int st = codec::parse_instances_raw_bayer_demosaic_host(p, s.size(), HS, WS, ord,
+                                                                  nullptr, max_images, &n, malvar);
           if (st != codec::OK) n = 0;
           py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
                                   (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
           if (st == codec::OK)
-            st = codec::parse_instances_raw_bayer_host(p, s.size(), HS, WS, ord,
-                                                       out.mutable_data(), max_images, &n);
+            st = codec::parse_instances_raw_bayer_demosaic_host(
+                p, s.size(), HS, WS, ord, out.mutable_data(), max_images, &n, malvar);
           return py::make_tuple(st, out);
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("order"),
-        py::arg("max_images") = -1);
+        py::arg("max_images") = -1, py::arg("demosaic") = "bilinear");
   // ---- packed pixel formats (csrc/codec/pixfmt.h) ----
   m.def("packed_bpp", [](const std::string& format) {
     return packed_bpp(packed_format_of(format.c_str()));

@@ -177,6 +177,11 @@ int parse_instances_raw_yuv420p10_host(const uint8_t* p, size_t n, int HS, int W
 // BAD_SHAPE.
 int parse_instances_raw_bayer_host(const uint8_t* p, size_t n, int HS, int WS, int order,
                                    float* out, int max_images, int* images);
+// The same with the demosaic named: malvar = demosaiced by bayer_malvar_to_rgb_host (a size under
+// 4: BAD_SHAPE), else parse_instances_raw_bayer_host. (A function of its own, not a defaulted
+// argument: callers take the address of the one above.)
+int parse_instances_raw_bayer_demosaic_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                            float* out, int max_images, int* images, bool malvar);
 
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes

@@ -87,6 +87,18 @@ class PixelSource {
   }
   bool chroma_linear() const { return chroma_linear_; }
 
+  // The same source with the demosaic of the configuration name bayer_demosaic: bilinear | malvar
+  // (bayer.h: the 5 x 5 gradient-corrected filter). check() refuses malvar on anything but a
+  // Bayer mosaic of at least 4 x 4.
+  PixelSource with_demosaic(const std::string& bayer_demosaic) const {
+    PixelSource s = *this;
+    if (bayer_demosaic != "bilinear" && bayer_demosaic != "malvar")
+      throw std::invalid_argument("bayer_demosaic: bilinear or malvar");
+    s.bayer_malvar_ = bayer_demosaic == "malvar";
+    return s;
+  }
+  bool bayer_malvar() const { return bayer_malvar_; }
+
   // The same source for raw binary records (input_format raw): the value is the images' bytes
   // themselves, with no base64 and no envelope around them.
   PixelSource as_raw() const {
@@ -140,6 +152,14 @@ class PixelSource {
       if (WS > kYuv420LinearMaxWS)
         throw std::invalid_argument("yuv_chroma linear needs a record-side W of at most " +
                                     std::to_string(kYuv420LinearMaxWS));
+    }
+    if (bayer_malvar_) {
+      if (kind() != BAYER)
+        throw std::invalid_argument(
+            "bayer_demosaic malvar needs pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / "
+            "bayer_gbrg8");
+      if (HS < 4 || WS < 4)
+        throw std::invalid_argument("bayer_demosaic malvar needs a record-side H, W of at least 4");
     }
     if (raw_ && kind() == YUV && !yuv422() && !planar() && !hi420())
       throw std::invalid_argument("input_format raw: no pixel_format i420 / nv12");
@@ -209,8 +229,9 @@ class PixelSource {
   int parse_host(const uint8_t* p, size_t n, int HS, int WS, int C, float* out, int max_images,
                  int* images) const {
     if (kind() == BAYER)  // (raw only: check() refuses the b64 form)
-      return raw_ ? codec::parse_instances_raw_bayer_host(p, n, HS, WS, bayer_order_, out,
-                                                          max_images, images)
+      return raw_ ? codec::parse_instances_raw_bayer_demosaic_host(p, n, HS, WS, bayer_order_, out,
+                                                                   max_images, images,
+                                                                   bayer_malvar_)
                   : (int)codec::BAD_SHAPE;
     if (yuv422())
       return raw_ ? codec::parse_instances_raw_yuv422_host(p, n, HS, WS, yuv_format_, yuv_, out,
@@ -250,6 +271,7 @@ class PixelSource {
   int elem_ = ELEM_U8;
   bool raw_ = false;
   bool chroma_linear_ = false;
+  bool bayer_malvar_ = false;
 };
 
 }  // namespace gale

@@ -405,6 +405,20 @@ hipError_t raw_bayer_instances(int images, const B64Image* imgs, const uint8_t* 
                                int WS, int C, float* out, int* status, hipStream_t stream,
                                const int* d_images, const InputPrep* prep, int order);
 
+// raw_bayer_instances with the gradient-corrected demosaic (configuration name bayer_demosaic
+// malvar, bayer_malvar.hip): the same arguments, descriptor table, early exit, grid and store
+// staging; RGB is the 5 x 5 filter of Malvar, He and Cutler as csrc/codec/bayer.h defines it in
+// integers over 16, at indices reflected two deep (-2 -> 2, -1 -> 1, n -> n - 2, n + 1 -> n - 3):
+// the bits of codec::bayer_malvar_to_rgb_host. A lane loads rows 2 r - 2 .. 2 r + 3 around its
+// block of 2 rows x 8 columns, each as the aligned dwords that cover columns 8 cb - 2 .. 8 cb + 9,
+// splits them into even- and odd-column 16-bit pairs and evaluates the four formulas in packed
+// signed 16-bit arithmetic, two pixels of one site type a register.
+// hipErrorInvalidValue, before any launch: what raw_bayer_instances refuses, and HS < 4 or WS < 4.
+hipError_t raw_bayer_malvar_instances(int images, const B64Image* imgs, const uint8_t* bytes,
+                                      int HS, int WS, int C, float* out, int* status,
+                                      hipStream_t stream, const int* d_images,
+                                      const InputPrep* prep, int order);
+
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard
 // base64, B = HS*WS*P bytes (csrc/codec/pixfmt.h), padded like an RGB string - becomes the

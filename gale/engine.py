@@ -72,6 +72,11 @@ class Engine:
         if cfg.b64_ingest and (cfg.stub or not cfg.gpu_ingest):
             log.info("b64_ingest has no effect %s", "with stub replicas" if cfg.stub
                      else "without gpu_ingest")
+        # (bilinear, the default: the log is what it was before the option existed)
+        if cfg.input_bayer_demosaic != "bilinear":
+            log.info("input pixel format %s: %s demosaic (%s)", cfg.input_pixel_format,
+                     cfg.input_bayer_demosaic,
+                     "on the host: stub replicas" if cfg.stub else "the batch step's decode launch")
         self.model_replicas: list = []
         self.devices: List[int] = []
         if cfg.stub:

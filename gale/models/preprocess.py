@@ -822,6 +822,7 @@ class PixelUnpack:
 # the Bayer orders: name -> (site (0, 0) is green, the even rows' non-green colour is blue)
 BAYER_FORMATS = {"bayer_rggb8": (False, False), "bayer_bggr8": (False, True),
                  "bayer_grbg8": (True, False), "bayer_gbrg8": (True, True)}
+BAYER_DEMOSAICS = ("bilinear", "malvar")
 
 
 @dataclass(frozen=True)
@@ -839,19 +840,44 @@ class BayerConvert:
 
     the usual rounded bilinear demosaic. ``codec::bayer_to_rgb_host`` (csrc/codec/bayer.h) and the
     ``raw_bayer_instances`` kernel give the same bytes; the ``InputPrep`` coefficients that
-    follow are indexed by model channel (R, G, B): per-channel scales are white-balance gains."""
+    follow are indexed by model channel (R, G, B): per-channel scales are white-balance gains.
+
+    ``demosaic="malvar"`` (``--input-bayer-demosaic malvar``) is the 5 x 5 gradient-corrected
+    linear filter of Malvar, He and Cutler (ICASSP 2004) instead, its four kernels times 2 so
+    that every coefficient is an integer over 16. HS, WS >= 4; indices are reflected the same way
+    two deep (-2 -> 2, -1 -> 1, n -> n - 2, n + 1 -> n - 3). With::
+
+        H1 = S[y][x-1] + S[y][x+1]    H2 = S[y][x-2] + S[y][x+2]
+        V1 = S[y-1][x] + S[y+1][x]    V2 = S[y-2][x] + S[y+2][x]
+        D  = S[y-1][x-1] + S[y-1][x+1] + S[y+1][x-1] + S[y+1][x+1]
+        q(n) = clamp((n + 8) >> 4, 0, 255)              (signed, >> arithmetic)
+
+        R or B site:  own = s,  G = q(8s + 4(H1 + V1) - 2(H2 + V2)),
+                      opposite = q(12s + 4D - 3(H2 + V2))
+        G site:       G = s,  this row's colour = q(10s + 8 H1 - 2D - 2 H2 + V2),
+                      the other = q(10s + 8 V1 - 2D - 2 V2 + H2)
+
+    Every numerator lies in [-3060, 7140] (G at R / B: [-2040, 6120]) and so does every partial
+    sum: signed 16-bit arithmetic is exact. ``codec::bayer_malvar_to_rgb_host`` and the
+    ``raw_bayer_malvar_instances`` kernel (csrc/kernels/bayer_malvar.hip) give the same bytes."""
 
     format: str = "bayer_rggb8"
+    demosaic: str = "bilinear"
 
     def __post_init__(self):
         if self.format not in BAYER_FORMATS:
             raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
                              f"{tuple(BAYER_FORMATS)} for a Bayer mosaic")
+        if self.demosaic not in BAYER_DEMOSAICS:
+            raise ValueError(f"input_bayer_demosaic={self.demosaic!r}: expected one of "
+                             f"{BAYER_DEMOSAICS}")
 
     @classmethod
     def from_config(cls, cfg) -> Optional["BayerConvert"]:
         """The demosaic of a configuration, None for every other pixel format."""
-        return cls(cfg.input_pixel_format) if cfg.input_pixel_format in BAYER_FORMATS else None
+        if cfg.input_pixel_format not in BAYER_FORMATS:
+            return None
+        return cls(cfg.input_pixel_format, cfg.input_bayer_demosaic)
 
     @staticmethod
     def frame_bytes(HS: int, WS: int) -> int:
@@ -860,10 +886,14 @@ class BayerConvert:
         return HS * WS
 
     def engine_entries(self) -> Dict[str, Any]:
-        return dict(pixel_format=self.format)
+        d = dict(pixel_format=self.format)
+        if self.demosaic != "bilinear":
+            d["bayer_demosaic"] = self.demosaic
+        return d
 
     def kernel_kwargs(self) -> Dict[str, Any]:
-        """Keyword arguments of the ``raw_bayer_instances`` binding."""
+        """Keyword arguments of the ``raw_bayer_instances`` / ``raw_bayer_malvar_instances``
+        bindings."""
         return dict(order=self.format)
 
     def apply(self, frame, HS: int, WS: int) -> np.ndarray:
@@ -874,14 +904,29 @@ class BayerConvert:
             raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
         green_first, blue_first = BAYER_FORMATS[self.format]
         s = f.reshape(*f.shape[:-1], HS, WS).astype(np.int32)
-        # rows / columns -1 and n are rows / columns 1 and n - 2
-        p = np.concatenate([s[..., 1:2, :], s, s[..., -2:-1, :]], axis=-2)
-        p = np.concatenate([p[..., :, 1:2], p, p[..., :, -2:-1]], axis=-1)
-        at = lambda dy, dx: p[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
-        h = (at(0, -1) + at(0, 1) + 1) >> 1
-        v = (at(-1, 0) + at(1, 0) + 1) >> 1
-        cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
-        diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
+        if self.demosaic == "malvar":
+            if HS < 4 or WS < 4:
+                raise ValueError(f"the malvar demosaic needs HS, WS >= 4, got {HS},{WS}")
+            # rows / columns -2, -1, n, n + 1 are rows / columns 2, 1, n - 2, n - 3
+            p = np.pad(s, [(0, 0)] * (s.ndim - 2) + [(2, 2), (2, 2)], mode="reflect")
+            at = lambda dy, dx: p[..., 2 + dy:2 + dy + HS, 2 + dx:2 + dx + WS]  # noqa: E731
+            q = lambda n: np.clip((n + 8) >> 4, 0, 255)  # noqa: E731
+            h1, h2 = at(0, -1) + at(0, 1), at(0, -2) + at(0, 2)
+            v1, v2 = at(-1, 0) + at(1, 0), at(-2, 0) + at(2, 0)
+            d = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
+            h = q(10 * s + 8 * h1 - 2 * d - 2 * h2 + v2)
+            v = q(10 * s + 8 * v1 - 2 * d - 2 * v2 + h2)
+            cross = q(8 * s + 4 * (h1 + v1) - 2 * (h2 + v2))
+            diag = q(12 * s + 4 * d - 3 * (h2 + v2))
+        else:
+            # rows / columns -1 and n are rows / columns 1 and n - 2
+            p = np.concatenate([s[..., 1:2, :], s, s[..., -2:-1, :]], axis=-2)
+            p = np.concatenate([p[..., :, 1:2], p, p[..., :, -2:-1]], axis=-1)
+            at = lambda dy, dx: p[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
+            h = (at(0, -1) + at(0, 1) + 1) >> 1
+            v = (at(-1, 0) + at(1, 0) + 1) >> 1
+            cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
+            diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
         y, x = np.ogrid[:HS, :WS]
         green = ((x + y) & 1 == 1) != green_first
         blue_row = (y & 1 == 1) != blue_first  # the row's non-green colour is blue

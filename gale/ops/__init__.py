@@ -518,6 +518,18 @@ def raw_bayer_instances(staged: torch.Tensor, table: torch.Tensor, size, out: to
                              images, d_images, prep)
 
 
+def raw_bayer_malvar_instances(staged: torch.Tensor, table: torch.Tensor, size,
+                               out: torch.Tensor, status: torch.Tensor, bayer,
+                               images: Optional[int] = None,
+                               d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """``raw_bayer_instances`` with the gradient-corrected 5 x 5 demosaic of Malvar, He and Cutler
+    (``--input-bayer-demosaic malvar``; ``BayerConvert(order, "malvar")`` is its oracle): the same
+    arguments; ``size``: (HS, WS), both even and at least 4. There is no CPU path: a shape or
+    argument the launcher refuses raises ``ValueError`` before anything is launched."""
+    return _yuv422_instances("raw_bayer_malvar_instances", staged, table, size, out, status,
+                             bayer, images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
