@@ -144,6 +144,16 @@ build/asan/bayer_malvar_check: csrc/tests/bayer_malvar_check.cpp csrc/codec/json
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/bayer_malvar_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
+# the 10/12/16-bit Bayer host codec (csrc/tests/bayer_hi_check.cpp): the unpack of words and
+# MIPI groups against a loop form, the twin, the raw parser and PixelSource's rules for the deep
+# mosaics on random, truncated and extended records; codec only, no engine, no HIP call
+build/asan/bayer_hi_check: csrc/tests/bayer_hi_check.cpp csrc/codec/json_codec.cpp \
+                           csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/bayer_hi_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
 # linear chroma for i420 / nv12 (csrc/tests/yuv_chroma_check.cpp): the host twin against a
 # loop-form upsampler, the record parser's linear form and PixelSource's rules for yuv_chroma;
 # codec only, no engine, no HIP call

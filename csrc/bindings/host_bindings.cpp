@@ -986,6 +986,62 @@ void bind_host(py::module_& m) {
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("order"),
         py::arg("max_images") = -1, py::arg("demosaic") = "bilinear");
+  // ---- 10/12/16-bit Bayer mosaic frames (csrc/codec/bayer_hi.h, raw records) ----
+  // (format: "bayer_<order>{10le,12le,16le,10p,12p}"; 0 bytes for anything that is no frame)
+  m.def("bayer_hi_bytes", [](int HS, int WS, const std::string& format) {
+    const BayerHiFormat f = bayer_hi_format_of(format.c_str());
+    return f.order ? bayer_hi_bytes(HS, WS, f.bits, f.packing) : (int64_t)0;
+  });
+  m.def("bayer_hi_to_rgb_host",
+        [](py::bytes frame, int HS, int WS, const std::string& format, const std::string& demosaic,
+           std::optional<std::vector<float>> a, std::optional<std::vector<float>> b) {
+          // one frame -> (uint16 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep
+          const std::string_view s = view(frame);
+          if ((a && a->size() < 3) || (b && b->size() < 3) || bool(a) != bool(b))
+            throw std::invalid_argument("bayer_hi_to_rgb_host: a / b (>= 3 each)");
+          if (demosaic != "bilinear" && demosaic != "malvar")
+            throw std::invalid_argument("bayer_hi_to_rgb_host: demosaic bilinear | malvar");
+          const bool malvar = demosaic == "malvar";
+          const BayerHiFormat f = bayer_hi_format_of(format.c_str());
+          const int64_t B = f.order ? bayer_hi_bytes(HS, WS, f.bits, f.packing) : 0;
+          if (!B || (int64_t)s.size() != B || (malvar && (HS < 4 || WS < 4)))
+            throw std::invalid_argument("bayer_hi_to_rgb_host: format / size / byte count");
+          py::array_t<uint16_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
+          codec::bayer_hi_to_rgb_host(reinterpret_cast<const uint8_t*>(s.data()), HS, WS, f.order,
+                                      f.bits, f.packing, malvar, rgb.mutable_data(),
+                                      f32.mutable_data(), a ? a->data() : nullptr,
+                                      b ? b->data() : nullptr);
+          return py::make_tuple(rgb, f32);
+        },
+        py::arg("frame"), py::arg("HS"), py::arg("WS"), py::arg("format"),
+        py::arg("demosaic") = "bilinear", py::arg("a") = py::none(), py::arg("b") = py::none());
+  m.def("parse_instances_raw_bayer_hi_host",
+        [](py::bytes b, int HS, int WS, const std::string& format, int max_images,
+           const std::string& demosaic) {
+          // (status, float32 [N, HS, WS, 3]: (float)RGB of every frame of the raw value)
+          const std::string_view s = view(b);
+          const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
+          if (demosaic != "bilinear" && demosaic != "malvar")
+            throw std::invalid_argument(
+                "parse_instances_raw_bayer_hi_host: demosaic bilinear | malvar");
+          const bool malvar = demosaic == "malvar";
+          const BayerHiFormat f = bayer_hi_format_of(format.c_str());
+          int n = 0;
+          int st = codec::parse_instances_raw_bayer_hi_host(p, s.size(), HS, WS, f.order, f.bits,
+                                                            f.packing, nullptr, max_images, &n,
+                                                            malvar);
+          if (st != codec::OK) n = 0;
+          py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
+                                  (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
+          if (st == codec::OK)
+            st = codec::parse_instances_raw_bayer_hi_host(p, s.size(), HS, WS, f.order, f.bits,
+                                                          f.packing, out.mutable_data(),
+                                                          max_images, &n, malvar);
+          return py::make_tuple(st, out);
+        },
+        py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("format"),
+        py::arg("max_images") = -1, py::arg("demosaic") = "bilinear");
   // ---- packed pixel formats (csrc/codec/pixfmt.h) ----
   m.def("packed_bpp", [](const std::string& format) {
     return packed_bpp(packed_format_of(format.c_str()));

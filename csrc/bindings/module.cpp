@@ -412,6 +412,29 @@ PYBIND11_MODULE(_C, m) {
           py::arg("d_images") = 0, py::arg("order") = "bayer_rggb8", py::arg("a") = py::none(),
           py::arg("b") = py::none(), py::arg("nchw") = false);
   }
+  // The raw 10/12/16-bit Bayer demosaic (bayer_hi.hip): the arguments of raw_bayer_instances with
+  // format "bayer_<order>{10le,12le,16le,10p,12p}" (csrc/codec/bayer_hi.h; anything else reaches
+  // the launcher as an unknown order and form) and the demosaic. bits / packing, when not 0,
+  // replace what the name says: the launcher's refusal of a pair that no name spells
+  m.def("raw_bayer_hi_instances",
+        [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
+           uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,
+           bool malvar, int bits, int packing, std::optional<std::vector<float>> a,
+           std::optional<std::vector<float>> b, bool nchw) {
+          const auto prep = prep_from("raw_bayer_hi_instances", a, b, nchw);
+          const gale::BayerHiFormat f = gale::bayer_hi_format_of(format.c_str());
+          return (int)gale::raw_bayer_hi_instances(
+              images, static_cast<const gale::B64Image*>(P(imgs)),
+              static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
+              static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),
+              prep ? &*prep : nullptr, f.order, bits ? bits : f.bits,
+              packing ? packing : f.packing, malvar);
+        },
+        py::arg("images"), py::arg("imgs"), py::arg("bytes"), py::arg("HS"), py::arg("WS"),
+        py::arg("C"), py::arg("out"), py::arg("status"), py::arg("stream"),
+        py::arg("d_images") = 0, py::arg("format") = "bayer_rggb16le", py::arg("malvar") = false,
+        py::arg("bits") = 0, py::arg("packing") = 0, py::arg("a") = py::none(),
+        py::arg("b") = py::none(), py::arg("nchw") = false);
   m.def("b64_packed_instances",
         [](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C, uintptr_t out,
            uintptr_t status, uintptr_t stream, uintptr_t d_images, const std::string& format,

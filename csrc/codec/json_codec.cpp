@@ -755,6 +755,23 @@ int parse_instances_raw_bayer_demosaic_host(const uint8_t* p, size_t n, int HS, 
   return OK;
 }
 
+int parse_instances_raw_bayer_hi_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                      int bits, int packing, float* out, int max_images,
+                                      int* images, bool malvar) {
+  *images = 0;
+  const int64_t B = bayer_hi_bytes(HS, WS, bits, packing);
+  if (!B || !bayer_is_order(order) || (malvar && (HS < 4 || WS < 4))) return BAD_SHAPE;
+  const Scan s = scan_instances_raw(n, B);
+  if (s.status != OK) return s.status;
+  if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
+  const size_t per = (size_t)HS * WS * 3;
+  for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
+    bayer_hi_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, order, bits, packing, malvar, nullptr,
+                         out + (size_t)e * per);
+  *images = s.images;
+  return OK;
+}
+
 void apply_input_prep(float* x, int images, int H, int W, int C, bool nchw, const float* a,
                       const float* b) {
   const size_t hw = (size_t)H * W, per = hw * (size_t)C;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "bayer.h"
+#include "bayer_hi.h"
 #include "elemtype.h"
 #include "pixfmt.h"
 #include "yuv.h"
@@ -182,6 +183,14 @@ int parse_instances_raw_bayer_host(const uint8_t* p, size_t n, int HS, int WS, i
 // argument: callers take the address of the one above.)
 int parse_instances_raw_bayer_demosaic_host(const uint8_t* p, size_t n, int HS, int WS, int order,
                                             float* out, int max_images, int* images, bool malvar);
+// Host decoder of raw 10/12/16-bit Bayer mosaic records (bayer_hi.h; there is no b64 form): the
+// value is N frames of bayer_hi_bytes(HS, WS, bits, packing) bytes, demosaiced by
+// bayer_hi_to_rgb_host to (float)RGB[c] at full depth. The verdicts of
+// parse_instances_raw_bayer_demosaic_host: EMPTY, BAD_SHAPE (a length that is not a multiple of a
+// frame; a size, order or form that is no frame; malvar under 4), TOO_LARGE, OK.
+int parse_instances_raw_bayer_hi_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                      int bits, int packing, float* out, int max_images,
+                                      int* images, bool malvar);
 
 // Full host decoder of packed-pixel records (pixfmt.h: bgr24 / rgba / bgra / gray): the same
 // envelope, element list and verdicts with strings of packed_bytes(HS, WS, format) bytes

@@ -1,7 +1,7 @@
 // What the b64 strings of a topology carry (engine keys pixel_format and input_dtype):
 // interleaved RGB bytes, a YUV 4:2:0, packed 4:2:2, planar 4:2:2 / 4:4:4 or 10-bit 4:2:0 (raw
-// only) frame (yuv.h), packed pixels (pixfmt.h), an 8-bit Bayer mosaic (bayer.h, raw only) or a
-// typed tensor
+// only) frame (yuv.h), packed pixels (pixfmt.h), an 8-bit Bayer mosaic (bayer.h, raw only), a
+// 10/12/16-bit one in words or MIPI-packed groups (bayer_hi.h, raw only) or a typed tensor
 // (elemtype.h: the rgb layout with 16-bit or float elements). PixelSource is the one holder of
 // {yuv format, YuvCoeffs, packed format, element type} and of the rules about them: the configuration names,
 // the bytes of a string, what a topology may combine them with, what the ingest sees and which
@@ -16,6 +16,7 @@
 #include <string>
 
 #include "bayer.h"
+#include "bayer_hi.h"
 #include "elemtype.h"
 #include "json_codec.h"
 #include "pixfmt.h"
@@ -35,7 +36,7 @@ class PixelSource {
 
   // From the configuration names: pixel_format rgb | i420 | nv12 | yuyv422 | uyvy422 | yuv422p |
   // yuv444p | p010le | yuv420p10le | bgr24 | rgba | bgra | gray | bayer_rggb8 | bayer_bggr8 |
-  // bayer_grbg8 | bayer_gbrg8;
+  // bayer_grbg8 | bayer_gbrg8 | bayer_<order>{10le,12le,16le,10p,12p};
   // yuv_matrix bt601 | bt709 and yuv_range limited | full, null where the configuration does not
   // name one (bt601, limited; naming one with a packed format is refused).
   static PixelSource from_names(const std::string& pixel_format, const std::string* yuv_matrix,
@@ -43,6 +44,10 @@ class PixelSource {
     PixelSource s;
     s.packed_format_ = packed_format_of(pixel_format.c_str());
     s.bayer_order_ = bayer_order_of(pixel_format.c_str());
+    if (!s.bayer_order_) {  // (the deeper mosaics: kind BAYER with bits and packing of their own)
+      const BayerHiFormat hi = bayer_hi_format_of(pixel_format.c_str());
+      if (hi.order) s.bayer_order_ = hi.order, s.bayer_bits_ = hi.bits, s.bayer_packing_ = hi.packing;
+    }
     if (pixel_format == "i420" || pixel_format == "nv12")
       s.yuv_format_ = pixel_format == "i420" ? (int)YUV_I420 : (int)YUV_NV12;
     else if (pixel_format == "yuyv422" || pixel_format == "uyvy422")
@@ -123,10 +128,18 @@ class PixelSource {
   int packed_format() const { return packed_format_; }  // PackedFormat (PACKED_NONE unless PACKED)
   int elem() const { return elem_; }                    // InputElem (ELEM_U8 unless TYPED)
   int bayer_order() const { return bayer_order_; }      // BayerOrder (BAYER_NONE unless BAYER)
+  int bayer_bits() const { return bayer_bits_; }        // 8, or 10 / 12 / 16 (bayer_hi.h)
+  int bayer_packing() const { return bayer_packing_; }  // BayerPacking (BAYER_PACK_NONE: 8-bit)
+  bool bayer_hi() const { return bayer_packing_ != BAYER_PACK_NONE; }
+  // bytes of one row of a deep mosaic: 2 WS, 5 WS / 4 or 3 WS / 2
+  int bayer_hi_row_bytes(int WS) const {
+    return bayer_packing_ == BAYER_PACK_LE16 ? 2 * WS : bayer_bits_ == 10 ? WS / 4 * 5 : WS / 2 * 3;
+  }
 
   // Bytes one string carries for record-side images of HS x WS (x C for rgb, x C x E typed).
   int64_t bytes(int HS, int WS, int C) const {
-    return kind() == BAYER  ? bayer_bytes(HS, WS)
+    return bayer_hi()       ? bayer_hi_bytes(HS, WS, bayer_bits_, bayer_packing_)
+           : kind() == BAYER ? bayer_bytes(HS, WS)
            : kind() == PACKED ? packed_bytes(HS, WS, packed_format_)
            : yuv422()       ? yuv422_bytes(HS, WS)
            : planar()       ? yuvp_bytes(HS, WS, yuv_format_)
@@ -157,7 +170,7 @@ class PixelSource {
       if (kind() != BAYER)
         throw std::invalid_argument(
             "bayer_demosaic malvar needs pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / "
-            "bayer_gbrg8");
+            "bayer_gbrg8");  // (or a deeper mosaic, bayer_hi.h)
       if (HS < 4 || WS < 4)
         throw std::invalid_argument("bayer_demosaic malvar needs a record-side H, W of at least 4");
     }
@@ -176,12 +189,17 @@ class PixelSource {
       return;
     }
     if (kind() == BAYER) {
-      const std::string what = "pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / bayer_gbrg8";
+      const std::string what =
+          bayer_hi() ? "pixel_format bayer_*10le / 12le / 16le / 10p / 12p"
+                     : "pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / bayer_gbrg8";
       if (!input_b64 || !raw_) throw std::invalid_argument(what + " needs input_format raw");
       if (nchw) throw std::invalid_argument(what + ": no nchw layout");
       if (C != 3) throw std::invalid_argument(what + " needs a 3-channel model");
       if (HS <= 0 || WS <= 0 || ((HS | WS) & 1))
         throw std::invalid_argument(what + " needs even record-side H, W");
+      if (bayer_hi() && bayer_packing_ == BAYER_PACK_MIPI && bayer_bits_ == 10 && (WS & 3))
+        throw std::invalid_argument(
+            "pixel_format bayer_*10p needs a record-side W that is a multiple of 4");
       return;
     }
     const std::string what = yuv422()        ? "pixel_format yuyv422 / uyvy422"
@@ -210,12 +228,13 @@ class PixelSource {
   // 4:2:2 frame's that of an HS x WS x 2 one, a planar frame's that of an HS x WS x 2 (yuv422p)
   // or x 3 (yuv444p) one, a packed-pixel
   // string that of an HS x WS x P one, a typed tensor's string that of an HS x (WS E) x C one -
-  // a Bayer mosaic's that of an HS x WS x 1 one;
+  // a Bayer mosaic's that of an HS x WS x 1 one (a deep one: HS x its row bytes x 1);
   // the element size widens a row, not the channel count, because the ingest's launcher applies
   // the C > 4 coefficient rule to the C it is given even when it decodes nothing.
   // (There is no arena for any of them, so nothing is decoded.)
   Dims ingest_dims(int HS, int WS, int C) const {
-    return kind() == BAYER  ? Dims{HS, WS, 1}
+    return bayer_hi()       ? Dims{HS, bayer_hi_row_bytes(WS), 1}
+           : kind() == BAYER ? Dims{HS, WS, 1}
            : kind() == PACKED ? Dims{HS, WS, packed_bpp(packed_format_)}
            : yuv422()       ? Dims{HS, WS, 2}
            : planar()       ? Dims{HS, WS, 3 - yuvp_shift(yuv_format_)}
@@ -228,6 +247,11 @@ class PixelSource {
   // (json_codec.h), with its status, image count and floats.
   int parse_host(const uint8_t* p, size_t n, int HS, int WS, int C, float* out, int max_images,
                  int* images) const {
+    if (bayer_hi())  // (raw only: check() refuses the b64 form)
+      return raw_ ? codec::parse_instances_raw_bayer_hi_host(p, n, HS, WS, bayer_order_,
+                                                             bayer_bits_, bayer_packing_, out,
+                                                             max_images, images, bayer_malvar_)
+                  : (int)codec::BAD_SHAPE;
     if (kind() == BAYER)  // (raw only: check() refuses the b64 form)
       return raw_ ? codec::parse_instances_raw_bayer_demosaic_host(p, n, HS, WS, bayer_order_, out,
                                                                    max_images, images,
@@ -268,6 +292,8 @@ class PixelSource {
   YuvCoeffs yuv_;
   int packed_format_ = PACKED_NONE;
   int bayer_order_ = BAYER_NONE;
+  int bayer_bits_ = 8;
+  int bayer_packing_ = BAYER_PACK_NONE;
   int elem_ = ELEM_U8;
   bool raw_ = false;
   bool chroma_linear_ = false;

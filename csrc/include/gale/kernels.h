@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../codec/bayer.h"  // BayerOrder (no HIP: shared with the host codec)
+#include "../../codec/bayer_hi.h"  // BayerPacking, the deep mosaics' forms (no HIP either)
 #include "../../codec/elemtype.h"  // InputElem (no HIP: shared with the host codec)
 #include "../../codec/pixfmt.h"  // PackedFormat (no HIP: shared with the host codec)
 #include "../../codec/yuv.h"  // YuvFormat, YuvCoeffs (no HIP: shared with the host codec)
@@ -418,6 +419,27 @@ hipError_t raw_bayer_malvar_instances(int images, const B64Image* imgs, const ui
                                       int HS, int WS, int C, float* out, int* status,
                                       hipStream_t stream, const int* d_images,
                                       const InputPrep* prep, int order);
+
+// GPU demosaic of raw 10-, 12- and 16-bit Bayer mosaic records (input pixel formats
+// "bayer_<order>10le" / "12le" / "16le" / "10p" / "12p", bayer_hi.hip): the arguments, descriptor
+// table and early exit of raw_bayer_instances plus the sample depth `bits`, the `packing`
+// (BayerPacking, csrc/codec/bayer_hi.h: little-endian 16-bit words masked to the depth, or MIPI
+// CSI-2 groups of 5 bytes for 4 pixels / 3 bytes for 2) and the demosaic (malvar: the 5 x 5
+// filter of bayer.h clamped to 2^bits - 1, else the bilinear rule). Pixel (y, x) becomes
+// fmaf((float)RGB[c], a[c], b[c]) with RGB at full depth: the bits of
+// codec::bayer_hi_to_rgb_host. imgs[].off and `bytes` may have any byte phase: only aligned
+// dwords that hold a byte of the frame are read. status is never written (it must still be given).
+// The grid is (ceil(HS/16) ceil(WS/64)) x images workgroups of 256 threads. A workgroup unpacks
+// its tile of 16 rows x 64 columns with a halo of 2 (bilinear: 1), reflected rows and columns
+// included, once into LDS as 16-bit samples; after a barrier a lane evaluates one 2 x 2 quad from
+// its 6 x 6 (4 x 4) window in int32 and the tile's floats leave through LDS in 16-byte units
+// (WS mod 4 == 0 and a 16-byte aligned image base) or 8-byte units. No atomics, no scratch.
+// hipErrorInvalidValue, before any launch: what raw_bayer_instances refuses, an unknown bits /
+// packing pair, WS mod 4 != 0 with 10-bit MIPI groups, HS < 4 or WS < 4 with malvar.
+hipError_t raw_bayer_hi_instances(int images, const B64Image* imgs, const uint8_t* bytes, int HS,
+                                  int WS, int C, float* out, int* status, hipStream_t stream,
+                                  const int* d_images, const InputPrep* prep, int order, int bits,
+                                  int packing, bool malvar);
 
 // GPU decoder of base64 packed-pixel records (input pixel formats "bgr24" / "rgba" / "bgra" /
 // "gray", b64_packed.hip): every image's string - L = 4 ceil(B / 3) characters of standard

@@ -15,7 +15,8 @@
                                                       raw: the images' bytes, no envelope
         [--size H,W]                                  images of that size (--input-size H,W)
         [--pixel-format rgb|i420|nv12|yuyv422|uyvy422|yuv422p|yuv444p|p010le|yuv420p10le|
-                        bgr24|rgba|bgra|gray|bayer_rggb8|bayer_bggr8|bayer_grbg8|bayer_gbrg8]
+                        bgr24|rgba|bgra|gray|bayer_rggb8|bayer_bggr8|bayer_grbg8|bayer_gbrg8|
+                        bayer_<order>{10le,12le,16le,10p,12p}]
                                                       YUV 4:2:0 frames / packed pixels
                                                       (--encoding b64; --input-pixel-format)
     python -m gale consume <TOPIC> [--max N] [--from-beginning]          print output records
@@ -216,6 +217,7 @@ def cmd_produce(argv: List[str]) -> int:
 
     from gale._native import native
     from gale.data import (encode_records, encode_records_b64, encode_records_bayer,
+                           encode_records_bayer_hi,
                            encode_records_text,
                            encode_records_packed, encode_records_raw, encode_records_typed,
                            encode_records_yuv, encode_records_yuv420p10, encode_records_yuv422,
@@ -257,7 +259,10 @@ def cmd_produce(argv: List[str]) -> int:
                          "frames of 3*HS*WS bytes; --encoding raw only, the nhwc layout, a "
                          "3-channel model and even sizes; bayer_*8: the synthetic pixels of rgb "
                          "sampled through that colour-filter mosaic, HS*WS bytes; --encoding raw "
-                         "only, the nhwc layout, a 3-channel model and even sizes; bgr24 / rgba "
+                         "only, the nhwc layout, a 3-channel model and even sizes; "
+                         "bayer_<order>10le / 12le / 16le / 10p / 12p: synthetic mosaics of that "
+                         "depth in 16-bit words or MIPI packed groups, under the same rules (10p: "
+                         "a width that is a multiple of 4); bgr24 / rgba "
                          "/ bgra / gray: the "
                          "synthetic pixels of rgb in that byte order (alpha random; gray: their "
                          "first channel alone); needs --encoding b64, the nhwc layout and a "
@@ -298,7 +303,18 @@ def cmd_produce(argv: List[str]) -> int:
         shape = produce_shape(net.input_shape, a.size)
     except ValueError as e:
         ap.error(str(e))
-    if bayer:
+    if bayer and not a.pixel_format.endswith("8"):
+        from gale.models.preprocess import BayerHiConvert
+
+        bc = BayerHiConvert(a.pixel_format)
+        if shape[2] != 3 or shape[0] % 2 or shape[1] % 2 or (a.pixel_format.endswith("10p")
+                                                              and shape[1] % 4):
+            ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes (10p: a "
+                     f"width that is a multiple of 4), got {shape}")
+        recs = encode_records_bayer_hi(
+            np.random.default_rng(a.seed).integers(0, 1 << bc.bits, (a.images, *shape[:2])),
+            a.pixel_format, a.images_per_record)
+    elif bayer:
         if shape[2] != 3 or shape[0] % 2 or shape[1] % 2:
             ap.error(f"--pixel-format {a.pixel_format} needs 3 channels and even sizes, got "
                      f"{shape}")

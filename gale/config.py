@@ -51,10 +51,14 @@ CHOICES = {
     # hands back; b64 or raw; YuvPlanarConvert), or a 10-bit 4:2:0 frame of 16-bit words (p010le:
     # what hardware video decoders write; yuv420p10le: what software decoders write; raw only;
     # Yuv420HiConvert), or an 8-bit Bayer mosaic, one byte a pixel (bayer_*8: what machine-vision
-    # cameras hand out; raw only; BayerConvert). The names are ffmpeg's pix_fmts
+    # cameras hand out; raw only; BayerConvert), or a 10/12/16-bit one in little-endian words
+    # (bayer_*10le / 12le / 16le: V4L2 SRGGB10 / 12 / 16) or MIPI CSI-2 packed groups (bayer_*10p /
+    # 12p: SRGGB10P / 12P; raw only; BayerHiConvert). The names are ffmpeg's pix_fmts
     "input_pixel_format": ("rgb", "i420", "nv12", "bgr24", "rgba", "bgra", "gray", "yuyv422",
                            "uyvy422", "yuv422p", "yuv444p", "p010le", "yuv420p10le",
-                           "bayer_rggb8", "bayer_bggr8", "bayer_grbg8", "bayer_gbrg8"),
+                           "bayer_rggb8", "bayer_bggr8", "bayer_grbg8", "bayer_gbrg8")
+                          + tuple(f"bayer_{o}{f}" for o in ("rggb", "bggr", "grbg", "gbrg")
+                                  for f in ("10le", "12le", "16le", "10p", "12p")),
     # the YUV formats' matrix and range; "" = not given (bt601, limited)
     "input_yuv_matrix": ("", "bt601", "bt709"),
     "input_yuv_range": ("", "limited", "full"),
@@ -102,7 +106,13 @@ HELP = {
                           "every raw image is an 8-bit Bayer mosaic of HS*WS bytes, the name "
                           "giving the colours of the tile (0,0) (0,1) / (1,0) (1,1) (HS, WS "
                           "even; a 3-channel model; --input-format raw only), demosaiced on the "
-                          "GPU by the rounded bilinear rule with mirrored edges; bgr24 / rgba / "
+                          "GPU by the rounded bilinear rule with mirrored edges; "
+                          "bayer_<order>10le / 12le / 16le: the same mosaic in little-endian "
+                          "16-bit words of 2*HS*WS bytes, the bits above the depth ignored; "
+                          "bayer_<order>10p / 12p: the MIPI CSI-2 packed forms, 5 bytes for 4 "
+                          "pixels (WS a multiple of 4) / 3 bytes for 2; RGB keeps the full "
+                          "depth, so --input-scale is 1/1023, 1/4095 or 1/65535 for a 0..1 "
+                          "model; bgr24 / rgba / "
                           "bgra / gray: every "
                           "b64 string or raw image is HS*WS pixels of "
                           "3 / 4 / 4 / 1 bytes in that byte order (alpha ignored, gray "
@@ -121,7 +131,7 @@ HELP = {
     "input_bayer_demosaic": "bilinear (default): the rounded two- and four-tap averages over the "
                             "3x3 neighbourhood; malvar: the 5x5 gradient-corrected linear filter "
                             "of Malvar, He and Cutler (integer coefficients over 16, clamped), "
-                            "on the GPU; malvar needs a bayer_*8 --input-pixel-format and HS, WS "
+                            "on the GPU; malvar needs a bayer_* --input-pixel-format and HS, WS "
                             ">= 4",
     "input_dtype": "the element type of every b64 string or raw image: u8 (default) one byte a value; u16 / f16 "
                    "/ bf16 / f32: HS*WS*C little-endian elements of 2 / 2 / 2 / 4 bytes, converted "
@@ -441,6 +451,10 @@ class GaleConfig:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a Bayer mosaic (--input-pixel-format {fmt}) needs even "
                              f"HS,WS, got {rs.HS},{rs.WS}")
+        if bayer and fmt.endswith("10p") and rs.WS % 4:
+            opt = "--input-size" if self.input_size else "--input-pixel-format"
+            raise ValueError(f"{opt}: --input-pixel-format {fmt} packs four pixels in five bytes "
+                             f"and needs WS % 4 == 0, got {rs.HS},{rs.WS}")
         if yuv422 and fmt != "yuv444p" and rs.WS % 2:
             opt = "--input-size" if self.input_size else "--input-pixel-format"
             raise ValueError(f"{opt}: a 4:2:2 frame (--input-pixel-format {fmt}) needs an even "
@@ -477,11 +491,13 @@ class GaleConfig:
                 or YuvPlanarConvert.from_config(self) or Yuv420HiConvert.from_config(self))
 
     def input_unpack(self):
-        """The ``PixelUnpack`` (packed pixels) or ``BayerConvert`` (Bayer mosaics) of this
-        configuration, None for rgb and the YUV formats."""
-        from gale.models.preprocess import BayerConvert, PixelUnpack
+        """The ``PixelUnpack`` (packed pixels), ``BayerConvert`` (8-bit Bayer mosaics) or
+        ``BayerHiConvert`` (10/12/16-bit ones) of this configuration, None for rgb and the YUV
+        formats."""
+        from gale.models.preprocess import BayerConvert, BayerHiConvert, PixelUnpack
 
-        return PixelUnpack.from_config(self) or BayerConvert.from_config(self)
+        return (PixelUnpack.from_config(self) or BayerConvert.from_config(self)
+                or BayerHiConvert.from_config(self))
 
     def input_prep(self, C: Optional[int] = None):
         """The ``InputPrep`` of this configuration (C: the model's input channels)."""

@@ -295,6 +295,43 @@ def encode_records_bayer(rgb_u8: np.ndarray, pixel_format: str,
             for i in range(0, frames.shape[0], images_per_record)]
 
 
+def pack_bayer_hi(mosaic: np.ndarray, pixel_format: str,
+                  junk: Optional[np.ndarray] = None) -> np.ndarray:
+    """Samples [N, HS, WS] (integers 0 .. 2**bits - 1) -> uint8 [N, B] frames of a 10/12/16-bit
+    Bayer format (``gale.models.preprocess.BayerHiConvert``: little-endian words, or the MIPI
+    groups of 5 bytes for 4 pixels / 3 bytes for 2). ``junk`` (uint16 [N, HS, WS], optional, the
+    10le / 12le words only): its bits above the depth, which a reader ignores, are set."""
+    from gale.models.preprocess import BayerHiConvert
+
+    bc, m = BayerHiConvert(pixel_format), np.asarray(mosaic)
+    if m.ndim != 3 or m.dtype.kind not in "iu" or m.min(initial=0) < 0 \
+            or m.max(initial=0) >> bc.bits:
+        raise ValueError(f"pack_bayer_hi: integer [N, HS, WS] samples of {bc.bits} bits")
+    N, HS, WS = m.shape
+    bc.frame_bytes(HS, WS)  # (ValueError on a size that is no frame)
+    s = m.astype(np.uint16)
+    if bc.packing == "le16":
+        if junk is not None:
+            s = s | (np.asarray(junk, np.uint16) & np.uint16(0xFFFF >> bc.bits << bc.bits))
+        return np.ascontiguousarray(s.astype("<u2")).view(np.uint8).reshape(N, -1)
+    if junk is not None:
+        raise ValueError(f"pack_bayer_hi: {pixel_format} has no ignored bits")
+    n, low = (4, 2) if bc.bits == 10 else (2, 4)  # pixels a group, their bits in the last byte
+    g = s.reshape(N, -1, n)
+    last = (((g & ((1 << low) - 1)) << (low * np.arange(n, dtype=np.uint16))).sum(-1))
+    return np.concatenate([g >> low, last[..., None]], axis=-1).astype(np.uint8).reshape(N, -1)
+
+
+def encode_records_bayer_hi(mosaic: np.ndarray, pixel_format: str, images_per_record: int = 1,
+                            junk: Optional[np.ndarray] = None) -> List[bytes]:
+    """Samples (``pack_bayer_hi``) -> raw records of 10/12/16-bit Bayer mosaics
+    (--input-pixel-format bayer_*10le | 12le | 16le | 10p | 12p, --input-format raw): each record
+    value is its frames' bytes back to back."""
+    frames = pack_bayer_hi(mosaic, pixel_format, junk)
+    return [frames[i:i + images_per_record].tobytes()
+            for i in range(0, frames.shape[0], images_per_record)]
+
+
 def pack_pixels(rgb_u8: np.ndarray, pixel_format: str,
                 alpha: Optional[np.ndarray] = None) -> np.ndarray:
     """uint8 RGB images [N, HS, WS, 3] -> uint8 [N, HS*WS*P] packed images (the inverse of

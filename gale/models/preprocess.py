@@ -825,6 +825,42 @@ BAYER_FORMATS = {"bayer_rggb8": (False, False), "bayer_bggr8": (False, True),
 BAYER_DEMOSAICS = ("bilinear", "malvar")
 
 
+def _demosaic(s: np.ndarray, green_first: bool, blue_first: bool, demosaic: str,
+              M: int) -> np.ndarray:
+    """Integer samples [..., HS, WS] of 0 .. M -> RGB [..., HS, WS, 3] by the rules that
+    ``BayerConvert`` writes out; ``M`` is the clamp of the malvar filter."""
+    HS, WS = s.shape[-2:]
+    if demosaic == "malvar":
+        if HS < 4 or WS < 4:
+            raise ValueError(f"the malvar demosaic needs HS, WS >= 4, got {HS},{WS}")
+        # rows / columns -2, -1, n, n + 1 are rows / columns 2, 1, n - 2, n - 3
+        p = np.pad(s, [(0, 0)] * (s.ndim - 2) + [(2, 2), (2, 2)], mode="reflect")
+        at = lambda dy, dx: p[..., 2 + dy:2 + dy + HS, 2 + dx:2 + dx + WS]  # noqa: E731
+        q = lambda n: np.clip((n + 8) >> 4, 0, M)  # noqa: E731
+        h1, h2 = at(0, -1) + at(0, 1), at(0, -2) + at(0, 2)
+        v1, v2 = at(-1, 0) + at(1, 0), at(-2, 0) + at(2, 0)
+        d = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
+        h = q(10 * s + 8 * h1 - 2 * d - 2 * h2 + v2)
+        v = q(10 * s + 8 * v1 - 2 * d - 2 * v2 + h2)
+        cross = q(8 * s + 4 * (h1 + v1) - 2 * (h2 + v2))
+        diag = q(12 * s + 4 * d - 3 * (h2 + v2))
+    else:
+        # rows / columns -1 and n are rows / columns 1 and n - 2
+        p = np.concatenate([s[..., 1:2, :], s, s[..., -2:-1, :]], axis=-2)
+        p = np.concatenate([p[..., :, 1:2], p, p[..., :, -2:-1]], axis=-1)
+        at = lambda dy, dx: p[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
+        h = (at(0, -1) + at(0, 1) + 1) >> 1
+        v = (at(-1, 0) + at(1, 0) + 1) >> 1
+        cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
+        diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
+    y, x = np.ogrid[:HS, :WS]
+    green = ((x + y) & 1 == 1) != green_first
+    blue_row = (y & 1 == 1) != blue_first  # the row's non-green colour is blue
+    own, opp = np.where(green, h, s), np.where(green, v, diag)
+    return np.stack([np.where(blue_row, opp, own), np.where(green, s, cross),
+                     np.where(blue_row, own, opp)], axis=-1)
+
+
 @dataclass(frozen=True)
 class BayerConvert:
     """Raw 8-bit Bayer mosaic frames (``--input-pixel-format bayer_rggb8 | bayer_bggr8 |
@@ -904,35 +940,7 @@ class BayerConvert:
             raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
         green_first, blue_first = BAYER_FORMATS[self.format]
         s = f.reshape(*f.shape[:-1], HS, WS).astype(np.int32)
-        if self.demosaic == "malvar":
-            if HS < 4 or WS < 4:
-                raise ValueError(f"the malvar demosaic needs HS, WS >= 4, got {HS},{WS}")
-            # rows / columns -2, -1, n, n + 1 are rows / columns 2, 1, n - 2, n - 3
-            p = np.pad(s, [(0, 0)] * (s.ndim - 2) + [(2, 2), (2, 2)], mode="reflect")
-            at = lambda dy, dx: p[..., 2 + dy:2 + dy + HS, 2 + dx:2 + dx + WS]  # noqa: E731
-            q = lambda n: np.clip((n + 8) >> 4, 0, 255)  # noqa: E731
-            h1, h2 = at(0, -1) + at(0, 1), at(0, -2) + at(0, 2)
-            v1, v2 = at(-1, 0) + at(1, 0), at(-2, 0) + at(2, 0)
-            d = at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1)
-            h = q(10 * s + 8 * h1 - 2 * d - 2 * h2 + v2)
-            v = q(10 * s + 8 * v1 - 2 * d - 2 * v2 + h2)
-            cross = q(8 * s + 4 * (h1 + v1) - 2 * (h2 + v2))
-            diag = q(12 * s + 4 * d - 3 * (h2 + v2))
-        else:
-            # rows / columns -1 and n are rows / columns 1 and n - 2
-            p = np.concatenate([s[..., 1:2, :], s, s[..., -2:-1, :]], axis=-2)
-            p = np.concatenate([p[..., :, 1:2], p, p[..., :, -2:-1]], axis=-1)
-            at = lambda dy, dx: p[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
-            h = (at(0, -1) + at(0, 1) + 1) >> 1
-            v = (at(-1, 0) + at(1, 0) + 1) >> 1
-            cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
-            diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
-        y, x = np.ogrid[:HS, :WS]
-        green = ((x + y) & 1 == 1) != green_first
-        blue_row = (y & 1 == 1) != blue_first  # the row's non-green colour is blue
-        own, opp = np.where(green, h, s), np.where(green, v, diag)
-        rgb = np.stack([np.where(blue_row, opp, own), np.where(green, s, cross),
-                        np.where(blue_row, own, opp)], axis=-1)
+        rgb = _demosaic(s, green_first, blue_first, self.demosaic, 255)
         return rgb.astype(np.uint8)
 
     @staticmethod
@@ -941,6 +949,109 @@ class BayerConvert:
         coefficients of ``prep`` (an ``InputPrep``; None: the identity)."""
         x = np.asarray(rgb).astype(np.float32)
         return x if prep is None else prep.apply(x)
+
+
+# the deeper Bayer mosaics: name -> (green_first, blue_first, bits, packing); packing "le16":
+# little-endian 16-bit words masked to the depth, "mipi": the CSI-2 packed groups
+BAYER_HI_FORMATS = {
+    f"bayer_{order}{form}": (*BAYER_FORMATS[f"bayer_{order}8"], bits, packing)
+    for order in ("rggb", "bggr", "grbg", "gbrg")
+    for form, bits, packing in (("10le", 10, "le16"), ("12le", 12, "le16"), ("16le", 16, "le16"),
+                                ("10p", 10, "mipi"), ("12p", 12, "mipi"))}
+
+
+@dataclass(frozen=True)
+class BayerHiConvert:
+    """Raw 10-, 12- and 16-bit Bayer mosaic frames (``--input-pixel-format bayer_<order><form>``,
+    order ``rggb | bggr | grbg | gbrg``) to interleaved RGB at full depth, in integers.
+
+    A frame of HS x WS samples (both even) of ``bits`` bits, ``M = 2**bits - 1``::
+
+        10le 12le 16le  2*HS*WS bytes    little-endian 16-bit words, sample = word & M (the upper
+                                         bits of a 10- / 12-bit word are ignored)
+        10p             5*HS*WS/4 bytes  WS % 4 == 0, no row padding; 4 pixels in 5 bytes: bytes
+                                         0..3 hold bits 9:2 of pixels 0..3, byte 4 their bits 1:0
+                                         (pixel 0 in bits 1:0, pixel 3 in bits 7:6)
+        12p             3*HS*WS/2 bytes  2 pixels in 3 bytes: p0[11:4], p1[11:4],
+                                         p1[3:0] << 4 | p0[3:0]
+
+    (V4L2 SRGGB10 / 12 / 16, SRGGB10P, SRGGB12P.) Every bit pattern is a frame. RGB is
+    ``BayerConvert``'s bilinear or malvar rule on the samples, the malvar clamp being
+    ``q(n) = clamp((n + 8) >> 4, 0, M)``; nothing is scaled to 8 bits, ``--input-scale`` is the
+    user's for their depth. ``codec::bayer_hi_to_rgb_host`` (csrc/codec/bayer_hi.h) and the
+    ``raw_bayer_hi_instances`` kernel (csrc/kernels/bayer_hi.hip) give the same bits."""
+
+    format: str = "bayer_rggb16le"
+    demosaic: str = "bilinear"
+
+    def __post_init__(self):
+        if self.format not in BAYER_HI_FORMATS:
+            raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
+                             f"{tuple(BAYER_HI_FORMATS)} for a 10/12/16-bit Bayer mosaic")
+        if self.demosaic not in BAYER_DEMOSAICS:
+            raise ValueError(f"input_bayer_demosaic={self.demosaic!r}: expected one of "
+                             f"{BAYER_DEMOSAICS}")
+
+    @classmethod
+    def from_config(cls, cfg) -> Optional["BayerHiConvert"]:
+        """The demosaic of a configuration, None for every other pixel format."""
+        if cfg.input_pixel_format not in BAYER_HI_FORMATS:
+            return None
+        return cls(cfg.input_pixel_format, cfg.input_bayer_demosaic)
+
+    @property
+    def bits(self) -> int:
+        return BAYER_HI_FORMATS[self.format][2]
+
+    @property
+    def packing(self) -> str:
+        return BAYER_HI_FORMATS[self.format][3]
+
+    def frame_bytes(self, HS: int, WS: int) -> int:
+        if HS <= 0 or WS <= 0 or HS % 2 or WS % 2:
+            raise ValueError(f"a Bayer mosaic needs even, positive sizes, got {HS},{WS}")
+        if self.packing == "le16":
+            return 2 * HS * WS
+        if self.bits == 10 and WS % 4:
+            raise ValueError(f"{self.format}: four pixels in five bytes need WS % 4 == 0, got {WS}")
+        return HS * WS * self.bits // 8
+
+    def engine_entries(self) -> Dict[str, Any]:
+        d = dict(pixel_format=self.format)
+        if self.demosaic != "bilinear":
+            d["bayer_demosaic"] = self.demosaic
+        return d
+
+    def kernel_kwargs(self) -> Dict[str, Any]:
+        """Keyword arguments of the ``raw_bayer_hi_instances`` binding."""
+        return dict(format=self.format, malvar=self.demosaic == "malvar")
+
+    def unpack(self, frame, HS: int, WS: int) -> np.ndarray:
+        """uint8 [..., B] frames -> uint16 [..., HS, WS] samples."""
+        B = self.frame_bytes(HS, WS)
+        f = np.asarray(frame, np.uint8)
+        if f.shape[-1] != B:
+            raise ValueError(f"expected [..., {B}] bytes, got {f.shape}")
+        lead = f.shape[:-1]
+        if self.packing == "le16":
+            w = f.reshape(*lead, HS * WS, 2).astype(np.uint16)
+            s = (w[..., 0] | w[..., 1] << 8) & ((1 << self.bits) - 1)
+        elif self.bits == 10:
+            g = f.reshape(*lead, HS * WS // 4, 5).astype(np.uint16)
+            s = g[..., :4] << 2 | (g[..., 4:] >> np.arange(0, 8, 2, dtype=np.uint16)) & 3
+        else:
+            g = f.reshape(*lead, HS * WS // 2, 3).astype(np.uint16)
+            s = g[..., :2] << 4 | (g[..., 2:] >> np.arange(0, 8, 4, dtype=np.uint16)) & 15
+        return s.reshape(*lead, HS, WS).astype(np.uint16)
+
+    def apply(self, frame, HS: int, WS: int) -> np.ndarray:
+        """The numpy oracle: uint8 [..., B] frames -> uint16 [..., HS, WS, 3] RGB."""
+        green_first, blue_first, bits, _ = BAYER_HI_FORMATS[self.format]
+        s = self.unpack(frame, HS, WS).astype(np.int64)
+        return _demosaic(s, green_first, blue_first, self.demosaic,
+                         (1 << bits) - 1).astype(np.uint16)
+
+    to_float = staticmethod(BayerConvert.to_float)
 
 
 # the element types of a typed tensor record: name -> (bytes per element, numpy wire dtype)

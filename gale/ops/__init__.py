@@ -530,6 +530,21 @@ def raw_bayer_malvar_instances(staged: torch.Tensor, table: torch.Tensor, size,
                              bayer, images, d_images, prep)
 
 
+def raw_bayer_hi_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
+                           status: torch.Tensor, bayer, images: Optional[int] = None,
+                           d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
+    """Demosaic raw 10/12/16-bit Bayer frames (``--input-pixel-format bayer_*10le | 12le | 16le |
+    10p | 12p``, input format ``raw``) into the fp32 NHWC batch tensor ``out`` [slots, HS, WS, 3]
+    as RGB at full depth, in place; returns ``out``. Arguments as ``raw_bayer_instances``;
+    ``bayer``: a ``gale.models.preprocess.BayerHiConvert`` (format and demosaic, its oracle);
+    ``size``: (HS, WS), both even, at least 4 for malvar, WS a multiple of 4 for ``10p``; every
+    frame is ``bayer.frame_bytes(HS, WS)`` bytes at any byte offset of ``staged``. ``status`` is
+    never written. There is no CPU path: a shape or argument the launcher refuses raises
+    ``ValueError`` before anything is launched."""
+    return _yuv422_instances("raw_bayer_hi_instances", staged, table, size, out, status, bayer,
+                             images, d_images, prep)
+
+
 def b64_packed_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                          status: torch.Tensor, unpack, images: Optional[int] = None,
                          d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
