@@ -52,6 +52,8 @@ $(OBJ)/kernels/b64_yuv_linear.o: HIP_FLAGS += -Xclang -target-feature -Xclang -p
 $(OBJ)/kernels/bayer.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 # and its gradient-corrected twin: the same store side
 $(OBJ)/kernels/bayer_malvar.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# and the edge-directed one: 12 independent fmas a lane in front of its stores
+$(OBJ)/kernels/bayer_hamilton.o: HIP_FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 gale/_C.so: $(HIP_OBJ) $(CXX_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lz -ldl -pthread \
@@ -143,6 +145,16 @@ build/asan/bayer_malvar_check: csrc/tests/bayer_malvar_check.cpp csrc/codec/json
 	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
 	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    csrc/tests/bayer_malvar_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
+
+# the edge-directed demosaic's host codec (csrc/tests/bayer_hamilton_check.cpp): the twin against
+# a loop form that builds the green and colour-difference planes, the raw parser's hamilton form
+# and PixelSource's rules for bayer_demosaic hamilton; codec only, no engine, no HIP call
+build/asan/bayer_hamilton_check: csrc/tests/bayer_hamilton_check.cpp csrc/codec/json_codec.cpp \
+                                 csrc/codec/java8_float.cpp $(HDRS)
+	@mkdir -p $(dir $@)
+	$(SAN_CXX) -O1 -g -fno-omit-frame-pointer -std=c++17 -mavx2 -mfma -msse4.2 \
+	    -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    csrc/tests/bayer_hamilton_check.cpp csrc/codec/json_codec.cpp csrc/codec/java8_float.cpp -o $@
 
 # the 10/12/16-bit Bayer host codec (csrc/tests/bayer_hi_check.cpp): the unpack of words and
 # MIPI groups against a loop form, the twin, the raw parser and PixelSource's rules for the deep

@@ -939,12 +939,17 @@ void bind_host(py::module_& m) {
         py::arg("max_images") = -1);
   // ---- 8-bit Bayer mosaic frames (csrc/codec/bayer.h, raw records) ----
   m.def("bayer_bytes", [](int HS, int WS) { return bayer_bytes(HS, WS); });
-  // (the bilinear twin and the gradient-corrected one, bayer_malvar_to_rgb_host: HS, WS >= 4)
-  for (const bool malvar : {false, true}) {
-    const char* const name = malvar ? "bayer_malvar_to_rgb_host" : "bayer_to_rgb_host";
+  // (the bilinear twin, the gradient-corrected one, bayer_malvar_to_rgb_host, and the
+  // edge-directed one, bayer_hamilton_to_rgb_host: HS, WS >= 4 for the last two)
+  for (const int dm : {BAYER_BILINEAR, BAYER_MALVAR, BAYER_HAMILTON}) {
+    const char* const name = dm == BAYER_HAMILTON ? "bayer_hamilton_to_rgb_host"
+                             : dm == BAYER_MALVAR ? "bayer_malvar_to_rgb_host"
+                                                  : "bayer_to_rgb_host";
+    const bool malvar = dm != BAYER_BILINEAR;  // (the size rule of both 5-wide filters)
     m.def(name,
-          [malvar, name](py::bytes frame, int HS, int WS, const std::string& order,
-                         std::optional<std::vector<float>> a, std::optional<std::vector<float>> b) {
+          [dm, malvar, name](py::bytes frame, int HS, int WS, const std::string& order,
+                             std::optional<std::vector<float>> a,
+                             std::optional<std::vector<float>> b) {
             // one frame -> (uint8 [HS, WS, 3], float32 [HS, WS, 3]); a / b: the prep
             const std::string_view s = view(frame);
             if ((a && a->size() < 3) || (b && b->size() < 3) || bool(a) != bool(b))
@@ -955,8 +960,8 @@ void bind_host(py::module_& m) {
               throw std::invalid_argument(std::string(name) + ": order / size / byte count");
             py::array_t<uint8_t> rgb({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
             py::array_t<float> f32({(py::ssize_t)HS, (py::ssize_t)WS, (py::ssize_t)3});
-            (malvar ? codec::bayer_malvar_to_rgb_host : codec::bayer_to_rgb_host)(
-                reinterpret_cast<const uint8_t*>(s.data()), HS, WS, ord, rgb.mutable_data(),
+            codec::bayer_demosaic_to_rgb_host(
+                reinterpret_cast<const uint8_t*>(s.data()), HS, WS, ord, dm, rgb.mutable_data(),
                 f32.mutable_data(), a ? a->data() : nullptr, b ? b->data() : nullptr);
             return py::make_tuple(rgb, f32);
           },
@@ -970,18 +975,19 @@ void bind_host(py::module_& m) {
           const std::string_view s = view(b);
           const uint8_t* p = reinterpret_cast<const uint8_t*>(s.data());
           const int ord = bayer_order_of(order.c_str());
-          if (demosaic != "bilinear" && demosaic != "malvar")
-            throw std::invalid_argument("parse_instances_raw_bayer_host: demosaic bilinear | malvar");
-          const bool malvar = demosaic == "malvar";
+          const int dm = bayer_demosaic_of(demosaic.c_str());
+          if (dm < 0)
+            throw std::invalid_argument(
+                "parse_instances_raw_bayer_host: demosaic bilinear | malvar | hamilton");
           int n = 0;
-          int st = codec::parse_instances_raw_bayer_demosaic_host(p, s.size(), HS, WS, ord,
-                                                                  nullptr, max_images, &n, malvar);
+          int st = codec::parse_instances_raw_bayer_named_host(p, s.size(), HS, WS, ord, nullptr,
+                                                               max_images, &n, dm);
           if (st != codec::OK) n = 0;
           py::array_t<float> out({(py::ssize_t)n, (py::ssize_t)std::max(HS, 0),
                                   (py::ssize_t)std::max(WS, 0), (py::ssize_t)3});
           if (st == codec::OK)
-            st = codec::parse_instances_raw_bayer_demosaic_host(
-                p, s.size(), HS, WS, ord, out.mutable_data(), max_images, &n, malvar);
+            st = codec::parse_instances_raw_bayer_named_host(
+                p, s.size(), HS, WS, ord, out.mutable_data(), max_images, &n, dm);
           return py::make_tuple(st, out);
         },
         py::arg("data"), py::arg("HS"), py::arg("WS"), py::arg("order"),

@@ -390,18 +390,23 @@ PYBIND11_MODULE(_C, m) {
         py::arg("d_images") = 0, py::arg("format") = "p010le",
         py::arg("coeffs") = std::vector<int32_t>{305236, 418389, -102698, -213115, 528805, 64},
         py::arg("a") = py::none(), py::arg("b") = py::none(), py::arg("nchw") = false);
-  // The raw Bayer demosaics (bayer.hip: bilinear; bayer_malvar.hip: gradient-corrected 5 x 5):
-  // the arguments of raw_yuv420p10_instances with order "bayer_rggb8" | "bayer_bggr8" |
-  // "bayer_grbg8" | "bayer_gbrg8" and no coefficient table
-  for (const bool malvar : {false, true}) {
-    const char* const name = malvar ? "raw_bayer_malvar_instances" : "raw_bayer_instances";
+  // The raw Bayer demosaics (bayer.hip: bilinear; bayer_malvar.hip: gradient-corrected 5 x 5;
+  // bayer_hamilton.hip: edge-directed): the arguments of raw_yuv420p10_instances with order
+  // "bayer_rggb8" | "bayer_bggr8" | "bayer_grbg8" | "bayer_gbrg8" and no coefficient table
+  for (const int dm : {gale::BAYER_BILINEAR, gale::BAYER_MALVAR, gale::BAYER_HAMILTON}) {
+    const char* const name = dm == gale::BAYER_HAMILTON ? "raw_bayer_hamilton_instances"
+                             : dm == gale::BAYER_MALVAR ? "raw_bayer_malvar_instances"
+                                                        : "raw_bayer_instances";
+    const auto launcher = dm == gale::BAYER_HAMILTON ? gale::raw_bayer_hamilton_instances
+                          : dm == gale::BAYER_MALVAR ? gale::raw_bayer_malvar_instances
+                                                     : gale::raw_bayer_instances;
     m.def(name,
-          [malvar, name](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C,
-                         uintptr_t out, uintptr_t status, uintptr_t stream, uintptr_t d_images,
-                         const std::string& order, std::optional<std::vector<float>> a,
-                         std::optional<std::vector<float>> b, bool nchw) {
+          [launcher, name](int images, uintptr_t imgs, uintptr_t bytes, int HS, int WS, int C,
+                           uintptr_t out, uintptr_t status, uintptr_t stream, uintptr_t d_images,
+                           const std::string& order, std::optional<std::vector<float>> a,
+                           std::optional<std::vector<float>> b, bool nchw) {
             const auto prep = prep_from(name, a, b, nchw);
-            return (int)(malvar ? gale::raw_bayer_malvar_instances : gale::raw_bayer_instances)(
+            return (int)launcher(
                 images, static_cast<const gale::B64Image*>(P(imgs)),
                 static_cast<const uint8_t*>(P(bytes)), HS, WS, C, static_cast<float*>(P(out)),
                 static_cast<int*>(P(status)), S(stream), static_cast<const int*>(P(d_images)),

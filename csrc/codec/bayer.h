@@ -12,7 +12,8 @@
 //     R or B site:  own = s,  G = (N + S + E + W + 2) >> 2,  opposite = (NW + NE + SW + SE + 2) >> 2
 //     G site:       G = s,  this row's colour = (W + E + 1) >> 1,  the other = (N + S + 1) >> 1
 // and the model input of channel c is fmaf((float)RGB[c], a[c], b[c]). The gradient-corrected
-// 5 x 5 filter (bayer_demosaic malvar) is written out at bayer_malvar_to_rgb_host below.
+// 5 x 5 filter (bayer_demosaic malvar) is written out at bayer_malvar_to_rgb_host below, the
+// edge-directed one (bayer_demosaic hamilton) at bayer_hamilton_to_rgb_host.
 // No HIP in this header: the sanitizer programs of the host codec include it.
 #pragma once
 #include <stddef.h>
@@ -27,6 +28,21 @@ constexpr bool bayer_is_order(int order) { return order >= BAYER_RGGB && order <
 // the even rows is blue.
 constexpr bool bayer_green_first(int order) { return order == BAYER_GRBG || order == BAYER_GBRG; }
 constexpr bool bayer_blue_first(int order) { return order == BAYER_BGGR || order == BAYER_GBRG; }
+
+// The demosaics of the configuration name bayer_demosaic. (BILINEAR and MALVAR are 0 and 1: the
+// `bool malvar` of the older signatures converts to them.)
+enum BayerDemosaic : int { BAYER_BILINEAR = 0, BAYER_MALVAR = 1, BAYER_HAMILTON = 2 };
+
+// "bilinear" | "malvar" | "hamilton"; -1 for anything else.
+inline int bayer_demosaic_of(const char* s) {
+  static const char* const kNames[] = {"bilinear", "malvar", "hamilton"};
+  for (int f = BAYER_BILINEAR; f <= BAYER_HAMILTON; ++f) {
+    const char *a = kNames[f], *b = s;
+    while (*a && *a == *b) ++a, ++b;
+    if (!*a && !*b) return f;
+  }
+  return -1;
+}
 
 // Bytes of one frame; 0 for odd or non-positive sizes.
 inline int64_t bayer_bytes(int HS, int WS) {
@@ -140,6 +156,86 @@ inline bool bayer_malvar_to_rgb_host(const uint8_t* src, int HS, int WS, int ord
       }
     }
   return true;
+}
+
+// The edge-directed demosaic (configuration name bayer_demosaic hamilton): the adaptive colour
+// plane interpolation of Hamilton and Adams (US 5,629,734) in integers. HS, WS >= 4; S is
+// reflected two deep as for malvar. Green at an R or B site, s = S[y][x]:
+//     dH = |W - E| + |2 s - WW - EE|            dV = |N - S| + |2 s - NN - SS|
+//     gH = (2 (W + E) + 2 s - WW - EE + 2) >> 2     gV = (2 (N + S) + 2 s - NN - SS + 2) >> 2
+//     gA = (2 (W + E + N + S) + 4 s - WW - EE - NN - SS + 4) >> 3      (signed, >> arithmetic)
+//     G^ = clamp(dH < dV ? gH : dV < dH ? gV : gA, 0, 255)
+// and G^ = s at a G site. The colour difference K[y][x] = S[y][x] - G^[y][x] (the clamped G^) is
+// formed at R / B sites only, never read at a G site, and its indices are reflected one deep
+// (-1 -> 1, n -> n - 2); dH / gH and dV / gV are symmetric, so that equals G^ of S reflected three
+// deep. Then
+//     G site:    this row's colour = clamp(s + ((K[y][x-1] + K[y][x+1] + 1) >> 1), 0, 255),
+//                the other         = clamp(s + ((K[y-1][x] + K[y+1][x] + 1) >> 1), 0, 255)
+//     R/B site:  own = s,  G = G^,  opposite = clamp(G^ + ((K[y-1][x-1] + K[y-1][x+1] +
+//                                                K[y+1][x-1] + K[y+1][x+1] + 2) >> 2), 0, 255)
+// (no diagonal direction decision). gH, gV lie in [-127, 383], K in [-255, 255], a sum of four K
+// in [-1020, 1020]: 16-bit lanes are exact (the kernel, csrc/kernels/bayer_hamilton.hip). The
+// signature and the optional outputs of bayer_to_rgb_host; false (nothing written) also for a size
+// under 4. *choice (optional, [HS][WS]): 0 at a G site, 1 / 2 / 3 where gH / gV / gA was taken.
+inline bool bayer_hamilton_to_rgb_host(const uint8_t* src, int HS, int WS, int order, uint8_t* rgb,
+                                       float* f32, const float* a = nullptr,
+                                       const float* b = nullptr, uint8_t* choice = nullptr) {
+  if (!bayer_bytes(HS, WS) || HS < 4 || WS < 4 || !bayer_is_order(order)) return false;
+  const int gf = bayer_green_first(order), bf = bayer_blue_first(order);
+  const auto refl = [](int i, int n) { return i < 0 ? -i : i >= n ? 2 * n - 2 - i : i; };
+  const auto at = [&](int y, int x) { return (int)src[(size_t)refl(y, HS) * WS + refl(x, WS)]; };
+  const auto clamp = [](int n) { return n < 0 ? 0 : n > 255 ? 255 : n; };
+  const auto iabs = [](int n) { return n < 0 ? -n : n; };
+  // G^ at the R / B site (y, x) of the frame; which: 1 / 2 / 3
+  const auto green = [&](int y, int x, int* which) {
+    const int s = at(y, x), w = at(y, x - 1), e = at(y, x + 1), n = at(y - 1, x), so = at(y + 1, x);
+    const int hd = 2 * s - at(y, x - 2) - at(y, x + 2), vd = 2 * s - at(y - 2, x) - at(y + 2, x);
+    const int dh = iabs(w - e) + iabs(hd), dv = iabs(n - so) + iabs(vd);
+    *which = dh < dv ? 1 : dv < dh ? 2 : 3;
+    return clamp(dh < dv   ? (2 * (w + e) + hd + 2) >> 2
+                 : dv < dh ? (2 * (n + so) + vd + 2) >> 2
+                           : (2 * (w + e + n + so) + hd + vd + 4) >> 3);
+  };
+  // K at an R / B site, its indices reflected one deep
+  const auto k = [&](int y, int x) {
+    int which;
+    y = refl(y, HS), x = refl(x, WS);
+    return (int)src[(size_t)y * WS + x] - green(y, x, &which);
+  };
+  for (int y = 0; y < HS; ++y)
+    for (int x = 0; x < WS; ++x) {
+      const int s = at(y, x);
+      int own, g, opp, which = 0;  // own: the non-green colour of row y; opp: that of the rows next to it
+      if ((((x + y) & 1) != 0) != (gf != 0)) {
+        g = s;
+        own = clamp(s + ((k(y, x - 1) + k(y, x + 1) + 1) >> 1));
+        opp = clamp(s + ((k(y - 1, x) + k(y + 1, x) + 1) >> 1));
+      } else {
+        own = s;
+        g = green(y, x, &which);
+        opp = clamp(g + ((k(y - 1, x - 1) + k(y - 1, x + 1) + k(y + 1, x - 1) + k(y + 1, x + 1) + 2) >> 2));
+      }
+      const bool blue_row = ((y & 1) != 0) != (bf != 0);
+      const uint8_t px[3] = {(uint8_t)(blue_row ? opp : own), (uint8_t)g,
+                             (uint8_t)(blue_row ? own : opp)};
+      const size_t o = ((size_t)y * WS + x) * 3;
+      if (choice) choice[(size_t)y * WS + x] = (uint8_t)which;
+      for (int c = 0; c < 3; ++c) {
+        if (rgb) rgb[o + c] = px[c];
+        if (f32) f32[o + c] = a ? __builtin_fmaf((float)px[c], a[c], b[c]) : (float)px[c];
+      }
+    }
+  return true;
+}
+
+// One frame by the named demosaic (BayerDemosaic): the three twins above behind one signature.
+inline bool bayer_demosaic_to_rgb_host(const uint8_t* src, int HS, int WS, int order, int demosaic,
+                                       uint8_t* rgb, float* f32, const float* a = nullptr,
+                                       const float* b = nullptr) {
+  return demosaic == BAYER_HAMILTON ? bayer_hamilton_to_rgb_host(src, HS, WS, order, rgb, f32, a, b)
+         : demosaic == BAYER_MALVAR ? bayer_malvar_to_rgb_host(src, HS, WS, order, rgb, f32, a, b)
+         : demosaic == BAYER_BILINEAR ? bayer_to_rgb_host(src, HS, WS, order, rgb, f32, a, b)
+                                      : false;
 }
 
 }  // namespace codec

@@ -741,16 +741,24 @@ int parse_instances_raw_bayer_host(const uint8_t* p, size_t n, int HS, int WS, i
 
 int parse_instances_raw_bayer_demosaic_host(const uint8_t* p, size_t n, int HS, int WS, int order,
                                             float* out, int max_images, int* images, bool malvar) {
+  return parse_instances_raw_bayer_named_host(p, n, HS, WS, order, out, max_images, images,
+                                              malvar ? BAYER_MALVAR : BAYER_BILINEAR);
+}
+
+int parse_instances_raw_bayer_named_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                         float* out, int max_images, int* images, int demosaic) {
   *images = 0;
   const int64_t B = bayer_bytes(HS, WS);
-  if (!B || !bayer_is_order(order) || (malvar && (HS < 4 || WS < 4))) return BAD_SHAPE;
+  if (!B || !bayer_is_order(order) || demosaic < BAYER_BILINEAR || demosaic > BAYER_HAMILTON ||
+      (demosaic != BAYER_BILINEAR && (HS < 4 || WS < 4)))
+    return BAD_SHAPE;
   const Scan s = scan_instances_raw(n, B);
   if (s.status != OK) return s.status;
   if (max_images >= 0 && s.images > max_images) return TOO_LARGE;
   const size_t per = (size_t)B * 3;
   for (int e = 0; out && e < s.images; ++e)  // (every byte pattern is a frame)
-    (malvar ? bayer_malvar_to_rgb_host : bayer_to_rgb_host)(
-        p + (size_t)e * (size_t)B, HS, WS, order, nullptr, out + (size_t)e * per, nullptr, nullptr);
+    bayer_demosaic_to_rgb_host(p + (size_t)e * (size_t)B, HS, WS, order, demosaic, nullptr,
+                               out + (size_t)e * per);
   *images = s.images;
   return OK;
 }

@@ -183,6 +183,11 @@ int parse_instances_raw_bayer_host(const uint8_t* p, size_t n, int HS, int WS, i
 // argument: callers take the address of the one above.)
 int parse_instances_raw_bayer_demosaic_host(const uint8_t* p, size_t n, int HS, int WS, int order,
                                             float* out, int max_images, int* images, bool malvar);
+// The same with any of the three demosaics (bayer.h BayerDemosaic; hamilton:
+// bayer_hamilton_to_rgb_host, a size under 4 BAD_SHAPE as well; an unknown value: BAD_SHAPE). A
+// name of its own for the same reason: callers take the address of the bool form too.
+int parse_instances_raw_bayer_named_host(const uint8_t* p, size_t n, int HS, int WS, int order,
+                                         float* out, int max_images, int* images, int demosaic);
 // Host decoder of raw 10/12/16-bit Bayer mosaic records (bayer_hi.h; there is no b64 form): the
 // value is N frames of bayer_hi_bytes(HS, WS, bits, packing) bytes, demosaiced by
 // bayer_hi_to_rgb_host to (float)RGB[c] at full depth. The verdicts of

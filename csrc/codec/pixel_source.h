@@ -93,16 +93,19 @@ class PixelSource {
   bool chroma_linear() const { return chroma_linear_; }
 
   // The same source with the demosaic of the configuration name bayer_demosaic: bilinear | malvar
-  // (bayer.h: the 5 x 5 gradient-corrected filter). check() refuses malvar on anything but a
-  // Bayer mosaic of at least 4 x 4.
+  // (bayer.h: the 5 x 5 gradient-corrected filter) | hamilton (bayer.h: the edge-directed one).
+  // check() refuses malvar on anything but a Bayer mosaic of at least 4 x 4, and hamilton on
+  // anything but an 8-bit one of that size. (The refusal's text is what it was before hamilton:
+  // a check program compares it whole.)
   PixelSource with_demosaic(const std::string& bayer_demosaic) const {
     PixelSource s = *this;
-    if (bayer_demosaic != "bilinear" && bayer_demosaic != "malvar")
-      throw std::invalid_argument("bayer_demosaic: bilinear or malvar");
-    s.bayer_malvar_ = bayer_demosaic == "malvar";
+    s.bayer_demosaic_ = bayer_demosaic_of(bayer_demosaic.c_str());
+    if (s.bayer_demosaic_ < 0) throw std::invalid_argument("bayer_demosaic: bilinear or malvar");
     return s;
   }
-  bool bayer_malvar() const { return bayer_malvar_; }
+  int bayer_demosaic() const { return bayer_demosaic_; }  // BayerDemosaic
+  bool bayer_malvar() const { return bayer_demosaic_ == BAYER_MALVAR; }
+  bool bayer_hamilton() const { return bayer_demosaic_ == BAYER_HAMILTON; }
 
   // The same source for raw binary records (input_format raw): the value is the images' bytes
   // themselves, with no base64 and no envelope around them.
@@ -166,7 +169,16 @@ class PixelSource {
         throw std::invalid_argument("yuv_chroma linear needs a record-side W of at most " +
                                     std::to_string(kYuv420LinearMaxWS));
     }
-    if (bayer_malvar_) {
+    if (bayer_hamilton()) {  // (8-bit mosaics only: bayer_hi.h has no edge-directed form)
+      if (kind() != BAYER || bayer_hi())
+        throw std::invalid_argument(
+            "bayer_demosaic hamilton needs pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / "
+            "bayer_gbrg8");
+      if (HS < 4 || WS < 4)
+        throw std::invalid_argument(
+            "bayer_demosaic hamilton needs a record-side H, W of at least 4");
+    }
+    if (bayer_malvar()) {
       if (kind() != BAYER)
         throw std::invalid_argument(
             "bayer_demosaic malvar needs pixel_format bayer_rggb8 / bayer_bggr8 / bayer_grbg8 / "
@@ -250,12 +262,12 @@ class PixelSource {
     if (bayer_hi())  // (raw only: check() refuses the b64 form)
       return raw_ ? codec::parse_instances_raw_bayer_hi_host(p, n, HS, WS, bayer_order_,
                                                              bayer_bits_, bayer_packing_, out,
-                                                             max_images, images, bayer_malvar_)
+                                                             max_images, images, bayer_malvar())
                   : (int)codec::BAD_SHAPE;
     if (kind() == BAYER)  // (raw only: check() refuses the b64 form)
-      return raw_ ? codec::parse_instances_raw_bayer_demosaic_host(p, n, HS, WS, bayer_order_, out,
-                                                                   max_images, images,
-                                                                   bayer_malvar_)
+      return raw_ ? codec::parse_instances_raw_bayer_named_host(p, n, HS, WS, bayer_order_, out,
+                                                                max_images, images,
+                                                                bayer_demosaic_)
                   : (int)codec::BAD_SHAPE;
     if (yuv422())
       return raw_ ? codec::parse_instances_raw_yuv422_host(p, n, HS, WS, yuv_format_, yuv_, out,
@@ -297,7 +309,7 @@ class PixelSource {
   int elem_ = ELEM_U8;
   bool raw_ = false;
   bool chroma_linear_ = false;
-  bool bayer_malvar_ = false;
+  int bayer_demosaic_ = BAYER_BILINEAR;
 };
 
 }  // namespace gale

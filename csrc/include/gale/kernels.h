@@ -420,6 +420,21 @@ hipError_t raw_bayer_malvar_instances(int images, const B64Image* imgs, const ui
                                       hipStream_t stream, const int* d_images,
                                       const InputPrep* prep, int order);
 
+// raw_bayer_instances with the edge-directed demosaic of Hamilton and Adams (configuration name
+// bayer_demosaic hamilton, bayer_hamilton.hip): the same arguments, descriptor table and early
+// exit; RGB as csrc/codec/bayer.h defines it in integers - green at an R or B site chosen between
+// a horizontal, a vertical and an averaged estimate by two gradients, red and blue interpolated
+// as colour differences against that green - the bits of codec::bayer_hamilton_to_rgb_host. Not a
+// stencil: a workgroup stages a tile of 32 x 32 bytes with a halo of 3 in LDS (reflections
+// resolved there), computes the colour difference once a site for the tile and a ring of 1 in
+// packed signed 16-bit arithmetic, and after one barrier a lane forms 1 x 4 pixels from LDS and
+// stores their 48 bytes. grid = (tiles of an image, images).
+// hipErrorInvalidValue, before any launch: what raw_bayer_malvar_instances refuses.
+hipError_t raw_bayer_hamilton_instances(int images, const B64Image* imgs, const uint8_t* bytes,
+                                        int HS, int WS, int C, float* out, int* status,
+                                        hipStream_t stream, const int* d_images,
+                                        const InputPrep* prep, int order);
+
 // GPU demosaic of raw 10-, 12- and 16-bit Bayer mosaic records (input pixel formats
 // "bayer_<order>10le" / "12le" / "16le" / "10p" / "12p", bayer_hi.hip): the arguments, descriptor
 // table and early exit of raw_bayer_instances plus the sample depth `bits`, the `packing`

@@ -10,7 +10,8 @@ namespace gale {
 // the b64 launchers of gale/kernels.h, or raw_instances for a raw source (a packed 4:2:2 frame:
 // b64_yuv422_instances or raw_yuv422_instances; a planar 4:2:2 / 4:4:4 frame: b64_yuvp_instances
 // or raw_yuvp_instances; a raw 10-bit 4:2:0 frame: raw_yuv420p10_instances; a raw Bayer mosaic:
-// raw_bayer_instances, or raw_bayer_malvar_instances with bayer_demosaic malvar; a raw 10/12/16-bit
+// raw_bayer_instances, or raw_bayer_malvar_instances with bayer_demosaic malvar, or
+// raw_bayer_hamilton_instances with bayer_demosaic hamilton; a raw 10/12/16-bit
 // Bayer mosaic: raw_bayer_hi_instances with either demosaic; a b64 4:2:0 frame with
 // linear chroma: b64_yuv_linear_instances), with these arguments. *which (optional): that
 // launcher's name.
@@ -44,6 +45,12 @@ inline hipError_t b64_source_instances(int images, const B64Image* imgs, const u
     return raw_bayer_hi_instances(images, imgs, bytes, HS, WS, C, out, status, stream, d_images,
                                   prep, src.bayer_order(), src.bayer_bits(), src.bayer_packing(),
                                   src.bayer_malvar());
+  }
+  if (k == PixelSource::BAYER && src.bayer_hamilton()) {  // (edge-directed: bayer_hamilton.hip)
+    if (which) *which = "raw_bayer_hamilton_instances";
+    if (!src.raw()) return hipErrorInvalidValue;  // (PixelSource::check refuses it)
+    return raw_bayer_hamilton_instances(images, imgs, bytes, HS, WS, C, out, status, stream,
+                                        d_images, prep, src.bayer_order());
   }
   if (k == PixelSource::BAYER) {  // (a raw 8-bit Bayer mosaic: bayer.hip / bayer_malvar.hip)
     if (which) *which = src.bayer_malvar() ? "raw_bayer_malvar_instances" : "raw_bayer_instances";

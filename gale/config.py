@@ -66,8 +66,9 @@ CHOICES = {
     # centre-sited 3:1 triangle filter (gale/models/preprocess.py YuvLinearConvert)
     "input_yuv_chroma": ("nearest", "linear"),
     # how a Bayer mosaic becomes RGB: the rounded bilinear filter, or the 5x5 gradient-corrected
-    # linear filter of Malvar, He and Cutler (gale/models/preprocess.py BayerConvert)
-    "input_bayer_demosaic": ("bilinear", "malvar"),
+    # linear filter of Malvar, He and Cutler, or the edge-directed interpolation of Hamilton and
+    # Adams (gale/models/preprocess.py BayerConvert)
+    "input_bayer_demosaic": ("bilinear", "malvar", "hamilton"),
     # the element type of an rgb b64 string or raw image (gale/models/preprocess.py ElemType): one uint8 a
     # value, or little-endian 16-bit / float elements converted exactly on the GPU
     "input_dtype": ("u8", "u16", "f16", "bf16", "f32"),
@@ -132,7 +133,10 @@ HELP = {
                             "3x3 neighbourhood; malvar: the 5x5 gradient-corrected linear filter "
                             "of Malvar, He and Cutler (integer coefficients over 16, clamped), "
                             "on the GPU; malvar needs a bayer_* --input-pixel-format and HS, WS "
-                            ">= 4",
+                            ">= 4; hamilton: the edge-directed interpolation of Hamilton and "
+                            "Adams (green chosen per site between a horizontal, a vertical and "
+                            "an averaged estimate, red and blue as colour differences), on the "
+                            "GPU; hamilton needs a bayer_*8 --input-pixel-format and HS, WS >= 4",
     "input_dtype": "the element type of every b64 string or raw image: u8 (default) one byte a value; u16 / f16 "
                    "/ bf16 / f32: HS*WS*C little-endian elements of 2 / 2 / 2 / 4 bytes, converted "
                    "exactly to float32 on the GPU before --input-scale / --input-mean / "
@@ -276,7 +280,8 @@ class GaleConfig:
     input_yuv_matrix: str = ""         # bt601 (default) | bt709, YUV formats only
     input_yuv_range: str = ""          # limited (default) | full, YUV formats only
     input_yuv_chroma: str = "nearest"  # linear: triangle-filtered chroma, b64 i420 | nv12 only
-    input_bayer_demosaic: str = "bilinear"  # malvar: gradient-corrected 5x5, bayer_*8 only
+    input_bayer_demosaic: str = "bilinear"  # malvar: gradient-corrected 5x5; hamilton:
+                                            # edge-directed, bayer_*8 only
     input_dtype: str = "u8"            # u16 | f16 | bf16 | f32: rgb b64 strings or raw images carry
                                        # little-endian elements of that type
     b64_ingest: bool = False           # input_format b64: GPU ingest of each fetch (batch CRCs on
@@ -420,6 +425,13 @@ class GaleConfig:
             if rs.HS < 4 or rs.WS < 4:
                 raise ValueError("--input-bayer-demosaic malvar: the 5x5 filter needs HS,WS >= 4, "
                                  f"got {rs.HS},{rs.WS}")
+        if self.input_bayer_demosaic == "hamilton":  # (8-bit mosaics only)
+            if fmt not in ("bayer_rggb8", "bayer_bggr8", "bayer_grbg8", "bayer_gbrg8"):
+                raise ValueError("--input-bayer-demosaic hamilton needs --input-pixel-format "
+                                 f"bayer_rggb8, bayer_bggr8, bayer_grbg8 or bayer_gbrg8, not {fmt}")
+            if rs.HS < 4 or rs.WS < 4:
+                raise ValueError("--input-bayer-demosaic hamilton: the gradients reach two "
+                                 f"samples out and need HS,WS >= 4, got {rs.HS},{rs.WS}")
         if fmt == "rgb":
             return
         from gale.models import get_model

@@ -822,19 +822,50 @@ class PixelUnpack:
 # the Bayer orders: name -> (site (0, 0) is green, the even rows' non-green colour is blue)
 BAYER_FORMATS = {"bayer_rggb8": (False, False), "bayer_bggr8": (False, True),
                  "bayer_grbg8": (True, False), "bayer_gbrg8": (True, True)}
-BAYER_DEMOSAICS = ("bilinear", "malvar")
+BAYER_DEMOSAICS = ("bilinear", "malvar", "hamilton")
+
+
+def _hamilton_green(p: np.ndarray):
+    """The edge-directed green of ``BayerConvert``'s hamilton rule at every position of ``p`` two
+    or more from its border, as if each were an R / B site: (the unclamped estimate, the choice
+    1 = gH, 2 = gV, 3 = gA), int arrays [..., H - 4, W - 4]."""
+    H, W = p.shape[-2:]
+    at = lambda dy, dx: p[..., 2 + dy:H - 2 + dy, 2 + dx:W - 2 + dx]  # noqa: E731
+    s = at(0, 0)
+    hs, hd = at(0, -1) + at(0, 1), 2 * s - at(0, -2) - at(0, 2)
+    vs, vd = at(-1, 0) + at(1, 0), 2 * s - at(-2, 0) - at(2, 0)
+    dh = np.abs(at(0, -1) - at(0, 1)) + np.abs(hd)
+    dv = np.abs(at(-1, 0) - at(1, 0)) + np.abs(vd)
+    choice = np.where(dh < dv, 1, np.where(dv < dh, 2, 3))
+    g = np.where(choice == 1, (2 * hs + hd + 2) >> 2,
+                 np.where(choice == 2, (2 * vs + vd + 2) >> 2,
+                          (2 * (hs + vs) + hd + vd + 4) >> 3))
+    return g, choice
 
 
 def _demosaic(s: np.ndarray, green_first: bool, blue_first: bool, demosaic: str,
               M: int) -> np.ndarray:
     """Integer samples [..., HS, WS] of 0 .. M -> RGB [..., HS, WS, 3] by the rules that
-    ``BayerConvert`` writes out; ``M`` is the clamp of the malvar filter."""
+    ``BayerConvert`` writes out; ``M`` is the clamp of the malvar and hamilton filters."""
     HS, WS = s.shape[-2:]
-    if demosaic == "malvar":
+    y, x = np.ogrid[:HS, :WS]
+    green = ((x + y) & 1 == 1) != green_first
+    lead = [(0, 0)] * (s.ndim - 2)
+    if demosaic == "hamilton":
+        if HS < 4 or WS < 4:
+            raise ValueError(f"the hamilton demosaic needs HS, WS >= 4, got {HS},{WS}")
+        # S reflected two deep; K = S - G^ at R / B sites (0 elsewhere, never read) one deep
+        cross = np.clip(_hamilton_green(np.pad(s, lead + [(2, 2), (2, 2)], mode="reflect"))[0], 0, M)
+        kp = np.pad(np.where(green, 0, s - cross), lead + [(1, 1), (1, 1)], mode="reflect")
+        k = lambda dy, dx: kp[..., 1 + dy:1 + dy + HS, 1 + dx:1 + dx + WS]  # noqa: E731
+        h = np.clip(s + ((k(0, -1) + k(0, 1) + 1) >> 1), 0, M)
+        v = np.clip(s + ((k(-1, 0) + k(1, 0) + 1) >> 1), 0, M)
+        diag = np.clip(cross + ((k(-1, -1) + k(-1, 1) + k(1, -1) + k(1, 1) + 2) >> 2), 0, M)
+    elif demosaic == "malvar":
         if HS < 4 or WS < 4:
             raise ValueError(f"the malvar demosaic needs HS, WS >= 4, got {HS},{WS}")
         # rows / columns -2, -1, n, n + 1 are rows / columns 2, 1, n - 2, n - 3
-        p = np.pad(s, [(0, 0)] * (s.ndim - 2) + [(2, 2), (2, 2)], mode="reflect")
+        p = np.pad(s, lead + [(2, 2), (2, 2)], mode="reflect")
         at = lambda dy, dx: p[..., 2 + dy:2 + dy + HS, 2 + dx:2 + dx + WS]  # noqa: E731
         q = lambda n: np.clip((n + 8) >> 4, 0, M)  # noqa: E731
         h1, h2 = at(0, -1) + at(0, 1), at(0, -2) + at(0, 2)
@@ -853,8 +884,6 @@ def _demosaic(s: np.ndarray, green_first: bool, blue_first: bool, demosaic: str,
         v = (at(-1, 0) + at(1, 0) + 1) >> 1
         cross = (at(-1, 0) + at(1, 0) + at(0, -1) + at(0, 1) + 2) >> 2
         diag = (at(-1, -1) + at(-1, 1) + at(1, -1) + at(1, 1) + 2) >> 2
-    y, x = np.ogrid[:HS, :WS]
-    green = ((x + y) & 1 == 1) != green_first
     blue_row = (y & 1 == 1) != blue_first  # the row's non-green colour is blue
     own, opp = np.where(green, h, s), np.where(green, v, diag)
     return np.stack([np.where(blue_row, opp, own), np.where(green, s, cross),
@@ -895,7 +924,34 @@ class BayerConvert:
 
     Every numerator lies in [-3060, 7140] (G at R / B: [-2040, 6120]) and so does every partial
     sum: signed 16-bit arithmetic is exact. ``codec::bayer_malvar_to_rgb_host`` and the
-    ``raw_bayer_malvar_instances`` kernel (csrc/kernels/bayer_malvar.hip) give the same bytes."""
+    ``raw_bayer_malvar_instances`` kernel (csrc/kernels/bayer_malvar.hip) give the same bytes.
+
+    ``demosaic="hamilton"`` (``--input-bayer-demosaic hamilton``) is the edge-directed
+    interpolation of Hamilton and Adams (US 5,629,734) in integers: green is chosen per site
+    between a horizontal, a vertical and an averaged estimate, red and blue are interpolated as
+    colour differences against that green. HS, WS >= 4; ``S`` is reflected two deep as for malvar.
+    Green at an R or B site, with ``s = S[y][x]`` and W, E, N, S / WW, EE, NN, SS the samples one
+    and two away::
+
+        dH = |W - E| + |2s - WW - EE|              dV = |N - S| + |2s - NN - SS|
+        gH = (2(W + E) + 2s - WW - EE + 2) >> 2    gV = (2(N + S) + 2s - NN - SS + 2) >> 2
+        gA = (2(W + E + N + S) + 4s - WW - EE - NN - SS + 4) >> 3   (signed, >> arithmetic)
+        G^ = clamp(dH < dV ? gH : dV < dH ? gV : gA, 0, 255)
+
+    and ``G^ = s`` at a G site. The colour difference ``K[y][x] = S[y][x] - G^[y][x]`` uses the
+    clamped ``G^``, exists at R / B sites only, is never read at a G site, and its indices are
+    reflected one deep (-1 -> 1, n -> n - 2); dH / gH and dV / gV are symmetric, so this equals
+    ``G^`` on a three-deep reflection of ``S``. Then::
+
+        G site:    this row's colour = clamp(s + ((K[y][x-1] + K[y][x+1] + 1) >> 1), 0, 255)
+                   the other         = clamp(s + ((K[y-1][x] + K[y+1][x] + 1) >> 1), 0, 255)
+        R/B site:  own = s,  G = G^,  opposite = clamp(G^ + ((K[y-1][x-1] + K[y-1][x+1]
+                                                 + K[y+1][x-1] + K[y+1][x+1] + 2) >> 2), 0, 255)
+
+    There is no diagonal direction decision. gH and gV lie in [-127, 383] (gA within them), K in
+    [-255, 255], a sum of four K in [-1020, 1020]: signed 16-bit arithmetic is exact.
+    ``codec::bayer_hamilton_to_rgb_host`` and the ``raw_bayer_hamilton_instances`` kernel
+    (csrc/kernels/bayer_hamilton.hip) give the same bytes. 8-bit mosaics only."""
 
     format: str = "bayer_rggb8"
     demosaic: str = "bilinear"
@@ -928,8 +984,8 @@ class BayerConvert:
         return d
 
     def kernel_kwargs(self) -> Dict[str, Any]:
-        """Keyword arguments of the ``raw_bayer_instances`` / ``raw_bayer_malvar_instances``
-        bindings."""
+        """Keyword arguments of the ``raw_bayer_instances`` / ``raw_bayer_malvar_instances`` /
+        ``raw_bayer_hamilton_instances`` bindings."""
         return dict(order=self.format)
 
     def apply(self, frame, HS: int, WS: int) -> np.ndarray:
@@ -942,6 +998,15 @@ class BayerConvert:
         s = f.reshape(*f.shape[:-1], HS, WS).astype(np.int32)
         rgb = _demosaic(s, green_first, blue_first, self.demosaic, 255)
         return rgb.astype(np.uint8)
+
+    def green_choice(self, frame, HS: int, WS: int) -> np.ndarray:
+        """Which green estimate the hamilton rule takes: uint8 [..., HS, WS], 0 at a G site,
+        1 / 2 / 3 where gH / gV / gA is chosen at an R / B site."""
+        s = np.asarray(frame, np.uint8).reshape(-1, HS, WS).astype(np.int32)
+        choice = _hamilton_green(np.pad(s, [(0, 0), (2, 2), (2, 2)], mode="reflect"))[1]
+        y, x = np.ogrid[:HS, :WS]
+        green = ((x + y) & 1 == 1) != BAYER_FORMATS[self.format][0]
+        return np.where(green, 0, choice).astype(np.uint8)
 
     @staticmethod
     def to_float(rgb, prep=None) -> np.ndarray:
@@ -988,9 +1053,9 @@ class BayerHiConvert:
         if self.format not in BAYER_HI_FORMATS:
             raise ValueError(f"input_pixel_format={self.format!r}: expected one of "
                              f"{tuple(BAYER_HI_FORMATS)} for a 10/12/16-bit Bayer mosaic")
-        if self.demosaic not in BAYER_DEMOSAICS:
-            raise ValueError(f"input_bayer_demosaic={self.demosaic!r}: expected one of "
-                             f"{BAYER_DEMOSAICS}")
+        if self.demosaic not in ("bilinear", "malvar"):  # (hamilton: 8-bit mosaics only)
+            raise ValueError(f"input_bayer_demosaic={self.demosaic!r}: expected bilinear or "
+                             f"malvar for a 10/12/16-bit Bayer mosaic ({self.format})")
 
     @classmethod
     def from_config(cls, cfg) -> Optional["BayerHiConvert"]:

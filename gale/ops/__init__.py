@@ -530,6 +530,19 @@ def raw_bayer_malvar_instances(staged: torch.Tensor, table: torch.Tensor, size,
                              bayer, images, d_images, prep)
 
 
+def raw_bayer_hamilton_instances(staged: torch.Tensor, table: torch.Tensor, size,
+                                 out: torch.Tensor, status: torch.Tensor, bayer,
+                                 images: Optional[int] = None,
+                                 d_images: Optional[torch.Tensor] = None,
+                                 prep=None) -> torch.Tensor:
+    """``raw_bayer_instances`` with the edge-directed demosaic of Hamilton and Adams
+    (``--input-bayer-demosaic hamilton``; ``BayerConvert(order, "hamilton")`` is its oracle): the
+    same arguments; ``size``: (HS, WS), both even and at least 4. There is no CPU path: a shape or
+    argument the launcher refuses raises ``ValueError`` before anything is launched."""
+    return _yuv422_instances("raw_bayer_hamilton_instances", staged, table, size, out, status,
+                             bayer, images, d_images, prep)
+
+
 def raw_bayer_hi_instances(staged: torch.Tensor, table: torch.Tensor, size, out: torch.Tensor,
                            status: torch.Tensor, bayer, images: Optional[int] = None,
                            d_images: Optional[torch.Tensor] = None, prep=None) -> torch.Tensor:
